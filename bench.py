@@ -28,6 +28,12 @@ every rank owns SF100 rows (weak scaling), rank 0 prints ONE JSON line.
   q6_sf10_parquet        BASELINE configs[1]: SF10 Q6 from snappy / zstd Parquet end to end (tools/parquet_q6.py)
   snappy_pipeline        the device snappy decompressor alone on 1 MiB pages (tools/snappy_bench.py)
   zstd_pipeline          the device zstd decompressor alone on 1 MiB pages (tools/snappy_bench.py --codec zstd)
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) measures the headline and nothing else: it generates the shard, warms up, times
+the N steps and prints the line (`value`, `ms_per_step`, and the `roofline` of the kernel times libcomet records inside those steps).
+Everything else above — the declared-length variant, the torch check of the result and the Final on rank 0, `cpu_baseline`, every extra
+leg and the PMC passes — runs only with --full.  --dump-outputs DIR writes the last timed step's Partial aggregate states as
+DIR/<column>.npy (float64, rows in group-key order); the shard is generated from a fixed seed, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -78,7 +84,13 @@ def main():
     ap.add_argument("--allow-fallback", action="store_true", help="N > 1: exit 0 even if the multi-GPU legs ran over torch's all_to_all instead of the in-library RCCL exchange")
     ap.add_argument("--no-executor-leg", action="store_true", help="skip the 8 / 16 concurrent-tasks leg")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip every extra leg (Q6, Q3, paths, PMC): headline + cpu_baseline only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the declared-length variant, the result check, cpu_baseline, the extra legs and the PMC passes (the --no-* options "
+                         "trim this set); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output columns to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import datafusion_comet_amd  # noqa: F401 — before torch: the JIT compiles with the installed ROCm's compiler, as under Spark (see that module)
     import pyarrow as pa
@@ -100,7 +112,7 @@ def main():
     # that the two CHAR(1) key columns hold one byte per value (utf8_uniform_kernel, 4 B/row of offsets per column) before the fused kernel
     # addresses the bytes directly.  The same loop over the table whose owner DECLARES the length (field metadata comet:utf8_fixed_len,
     # verified once per buffer and cached, exec_input.cpp) is timed afterwards and reported as a sub-object, never as `value`.
-    dtab_hinted = None if args.no_string_hints else dtab.with_string_hints()
+    dtab_hinted = None if (args.no_string_hints or not args.full) else dtab.with_string_hints()
     torch.cuda.synchronize()
     ncols = tpch.Q1_NUM_OUTPUT_COLS
 
@@ -140,6 +152,8 @@ def main():
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
 
     # the same tasks over the table WITH the owner's fixed-length declaration (first task verifies it, the rest hit the cached verdict)
     elapsed_hinted = None
@@ -157,33 +171,36 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed_hinted = float(tmax.item())
 
-    # ---- outside the timed region -------------------------------------------------------------------------------------------
-    # (1) every aggregate of every group of this rank's Partial states against exact torch reductions of the generating tensors
-    out_tab = pa.Table.from_batches(result)
-    problems = tpch.q1_check_against_torch(out_tab, chk)
-    ok_local = torch.tensor([0 if problems else 1], device=dev)
-    if world > 1:
-        dist.all_reduce(ok_local, op=dist.ReduceOp.MIN)
-    verified = bool(ok_local.item())
-    # (2) the only cross-rank step of a Q1-shaped plan: gather the Partial states on rank 0, Final there
-    states = parallel.gather_partial_states(out_tab, 0)
-    final_rows = None
-    if rank == 0 and states is not None:
-        fplan = S.final_of(plan, states.schema)
-        fin = pa.Table.from_batches(native.execute_to_table([native.HostInput.from_table(states)], 10, fplan.encode(), device_id=local_rank))
-        final_rows = sorted([[str(v) for v in r] for r in zip(*[fin.column(i).to_pylist() for i in range(fin.num_columns)])])
+    # ---- outside the timed region (--full only) ------------------------------------------------------------------------------
+    result_check, cpu = None, None
+    if args.full:
+        # (1) every aggregate of every group of this rank's Partial states against exact torch reductions of the generating tensors
+        out_tab = pa.Table.from_batches(result)
+        problems = tpch.q1_check_against_torch(out_tab, chk)
+        ok_local = torch.tensor([0 if problems else 1], device=dev)
+        if world > 1:
+            dist.all_reduce(ok_local, op=dist.ReduceOp.MIN)
+        verified = bool(ok_local.item())
+        # (2) the only cross-rank step of a Q1-shaped plan: gather the Partial states on rank 0, Final there
+        states = parallel.gather_partial_states(out_tab, 0)
+        final_rows = None
+        if rank == 0 and states is not None:
+            fplan = S.final_of(plan, states.schema)
+            fin = pa.Table.from_batches(native.execute_to_table([native.HostInput.from_table(states)], 10, fplan.encode(), device_id=local_rank))
+            final_rows = sorted([[str(v) for v in r] for r in zip(*[fin.column(i).to_pylist() for i in range(fin.num_columns)])])
+        result_check = {"all_8_aggregates_of_all_groups_match_torch_on_every_rank": verified, "mismatches_rank0": problems[:4],
+                        "groups_rank0": out_tab.num_rows, "final_rows_all_ranks": final_rows}
 
-    # (3) CPU baseline on the first rows of the same shard, and the GPU's answer for exactly those rows as a parity check
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(args, dtab, plan_bytes, local_rank)
+        # (3) CPU baseline on the first rows of the same shard, and the GPU's answer for exactly those rows as a parity check
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(args, dtab, plan_bytes, local_rank)
 
     del dtab, dtab_hinted, chk
     torch.cuda.empty_cache()
 
     legs = {}
     exchange = "native"
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         if world == 1:
             legs["q6"] = run_child_leg([os.path.join(ROOT, "tools", "resident.py"), "--query", "q6", "--rows", str(args.rows), "--steps", "5"],
                                        rank, local_rank, world, args.leg_timeout, 2017)
@@ -295,9 +312,9 @@ def main():
                        "rows_per_gpu": n, "bytes_per_row_algorithmic": tpch.Q1_BYTES_PER_ROW, "parallelism": f"row-range shards x{world}",
                        "jit_toolchain": native.jit_toolchain()},
             "roofline": roof,
-            "result_check": {"all_8_aggregates_of_all_groups_match_torch_on_every_rank": verified, "mismatches_rank0": problems[:4],
-                             "groups_rank0": out_tab.num_rows, "final_rows_all_ranks": final_rows},
         }
+        if result_check is not None:
+            line["result_check"] = result_check
         if cpu is not None:
             line["cpu_baseline"] = cpu.pop("one_thread")
             line["cpu_baseline_all_cores"] = cpu.pop("all_threads")
@@ -371,22 +388,24 @@ def main():
             line["exchange_probe"] = legs["exchange_probe"]
         if pmc:
             line["pmc"] = pmc
-        # the complete record (per-kernel lists, notes, PMC tables) next to the run; the printed line is its short form (< 6 KB: what the driver's record keeps)
-        full_path = None
-        try:
-            out_dir = os.path.join(ROOT, "gpurun_out")
-            os.makedirs(out_dir, exist_ok=True)
-            full_path = os.path.join(out_dir, f"bench_full_n{world}.json")
-            with open(full_path, "w") as f:
-                json.dump(line, f)
-        except OSError:
-            full_path = None
+        # --full: the complete record (per-kernel lists, notes, PMC tables) under bench_out/; the printed line is its short form (< 6 KB: what the driver's record keeps)
         short = compact_line(line)
-        short["full_record"] = os.path.relpath(full_path, ROOT) if full_path else None
+        if args.full:
+            full_path = None
+            try:
+                out_dir = os.path.join(ROOT, "bench_out")
+                os.makedirs(out_dir, exist_ok=True)
+                full_path = os.path.join(out_dir, f"bench_full_n{world}.json")
+                with open(full_path, "w") as f:
+                    json.dump(line, f)
+            except OSError:
+                full_path = None
+            short["full_record"] = os.path.relpath(full_path, ROOT) if full_path else None
         print(json.dumps(short, separators=(",", ":")))
     if world > 1:
         dist.destroy_process_group()
-        rc = multi_gpu_exit_code(world, not args.no_extra_legs, args.q3_orders > 0 or args.q95_orders > 0, exchange, legs if rank == 0 else None, args.allow_fallback)
+        rc = multi_gpu_exit_code(world, args.full and not args.no_extra_legs, args.q3_orders > 0 or args.q95_orders > 0, exchange, legs if rank == 0 else None,
+                                 args.allow_fallback)
         if rc:
             sys.exit(rc)      # the multi-GPU legs did not run over the in-library RCCL exchange: the line says so, and so does the exit code
 
@@ -526,6 +545,29 @@ def compact_line(full: dict) -> dict:
         put("exchange_probe_ok", (full["exchange_probe"] or {}).get("ok"))
     line["legs"] = legs
     return line
+
+
+def dump_outputs(out_dir: str, batches) -> None:
+    """What the caller of the timed path receives — this rank's Partial aggregate states — as out_dir/<column>.npy, one float64 value per group:
+    decimals as their value, booleans and counts as numbers, the one-character Utf8 keys as their code point.  The engine emits groups in no
+    particular order, so the rows are put in key order (the Utf8 columns) first; two builds then compare array for array."""
+    import numpy as np
+    import pyarrow as pa
+    tab = pa.Table.from_batches(batches)
+    cols = {f.name: tab.column(i).to_pylist() for i, f in enumerate(tab.schema)}
+    keys = [name for f, name in zip(tab.schema, cols) if pa.types.is_string(f.type)]
+    order = sorted(range(tab.num_rows), key=lambda r: tuple(cols[k][r] for k in keys))
+
+    def num(v):
+        if v is None:
+            return float("nan")
+        if isinstance(v, str):
+            assert len(v) == 1, f"string output {v!r}: only one-character keys are dumped"
+            return float(ord(v))
+        return float(v)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, vals in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.array([num(vals[r]) for r in order], dtype=np.float64))
 
 
 def cpu_baseline(args, dtab, plan_bytes, local_rank):

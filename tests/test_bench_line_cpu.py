@@ -45,3 +45,17 @@ def test_compact_line_survives_missing_and_failed_legs():
     line = _bench().compact_line(full)
     assert "q3_ms" not in line["legs"] and line["legs"]["q95_error"].startswith("leg timed out") and "cpu_baseline" not in line
     assert len(json.dumps(line)) < 5500
+
+
+def test_dump_outputs_writes_float64_columns_in_key_order(tmp_path):
+    import numpy as np
+    import pyarrow as pa
+    from decimal import Decimal
+    b = pa.record_batch([pa.array(["R", "A", "N"]), pa.array(["F", "F", "O"]), pa.array([Decimal("1.25"), Decimal("-3.50"), None], pa.decimal128(22, 2)),
+                         pa.array([False, True, False]), pa.array([7, 9, 11], pa.int64())], names=["col_0", "col_1", "col_2", "col_3", "col_4"])
+    _bench().dump_outputs(str(tmp_path / "out"), [b.slice(0, 2), b.slice(2, 1)])
+    got = {f.name[:-4]: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["col_0", "col_1", "col_2", "col_3", "col_4"] and all(a.dtype == np.float64 for a in got.values())
+    assert got["col_0"].tolist() == [ord("A"), ord("N"), ord("R")] and got["col_1"].tolist() == [ord("F"), ord("O"), ord("F")]
+    assert got["col_2"][0] == -3.5 and np.isnan(got["col_2"][1]) and got["col_2"][2] == 1.25
+    assert got["col_3"].tolist() == [1.0, 0.0, 0.0] and got["col_4"].tolist() == [9.0, 11.0, 7.0]

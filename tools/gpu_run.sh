@@ -20,8 +20,8 @@ tests_forced() {   # the Parquet files of the GPU suite with every scan treated 
 smoke() {
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
 }
-bench() {          # the bench line as the driver runs it
-  timeout 1500 python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 400 $OUT/bench.json; echo; tail -3 $OUT/bench.err
+bench() {          # the bench line with every leg and check
+  timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 400 $OUT/bench.json; echo; tail -3 $OUT/bench.err
 }
 bench_stats() {    # rocprofv3 kernel statistics of the headline loop only
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o b -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-extra-legs --no-cpu-baseline > $OUT/bench_stats.json 2> /dev/null)
