@@ -2894,6 +2894,74 @@ struct AggLowering {
   std::string fread(const FSum& f) const {
     return "comet::fix192_to_f64(acc + " + std::to_string(f.word) + ", " + fscale(f.fidx) + ", acc[" + std::to_string(f.cls) + "])";
   }
+  // the sum's scale and class word, for the statistical finishers
+  std::string fargs(const FSum& f) const { return "acc + " + std::to_string(f.word) + ", " + fscale(f.fidx) + ", acc[" + std::to_string(f.cls) + "]"; }
+  // a sum that takes k > 1 addends per row (x² as the two doubles of two_prod, a merged state's n·mean·mean as five): the ungrouped path feeds
+  // each addend; the grouped path adds the row's addends exactly first and splits that into the four limbs, so a limb word still takes less
+  // than 2^43 per row.  Every addend feeds the exponent words, so the window covers each of them.
+  FSum get_fsum(const std::string& vkey, const std::string& fkey, const std::string& cond, const std::vector<std::string>& xs) {
+    if (xs.size() == 1) return get_fsum(vkey, fkey, cond, xs[0]);
+    const std::string key = "fsum|" + vkey + "|" + fkey;
+    auto it = fsums.find(key);
+    if (it != fsums.end()) return it->second;
+    if ((int)fix_sums.size() >= kFixMaxSums) throw CometError("more than " + std::to_string(kFixMaxSums) + " distinct Float64 sums / averages in one aggregate are not supported by the GPU pipeline yet");
+    const int fidx = (int)fix_sums.size();
+    const int k = (int)xs.size();
+    const std::string c = cond.empty() ? "true" : cond, S = fscale(fidx), K = std::to_string(k);
+    std::string decl = "const double ad_[" + K + "] = {";
+    for (int i = 0; i < k; i++) decl += (i ? ", (double)(" : "(double)(") + xs[(size_t)i] + ")";
+    decl += "};";
+    FSum f;
+    f.fidx = fidx;
+    f.word = nw;
+    nw += 3;
+    f.cls = nw;
+    nw += 1;
+    const std::string w = std::to_string(f.word), w1 = std::to_string(f.word + 1), w2 = std::to_string(f.word + 2), cw = std::to_string(f.cls);
+    init_code += "    a[" + w + "] = 0; a[" + w1 + "] = 0; a[" + w2 + "] = 0; a[" + cw + "] = 0;\n";
+    combine_code += "    comet::acc_add192(a + " + w + ", b + " + w + "); comet::acc_or64(a + " + cw + ", b + " + cw + ");\n";
+    for (auto* q : {"G_ADD192", "G_CONT", "G_CONT", "G_OR64"}) gops.push_back(q);
+    for (int t = 0; t < 4; t++) gident.push_back("0ull");
+    PipelineDesc::FixSum fs;
+    fs.word = f.word;
+    if (grouped) {
+      int j[4];
+      for (int t = 0; t < 4; t++) j[t] = pword("G_ADD64", "0ull");
+      const int jc = pword("G_OR64", "0ull");
+      pv_code += "        { u64 l_[4] = {0ull, 0ull, 0ull, 0ull}; u64 c_ = 0ull; if (" + c + ") { " + decl + " comet::fix_addends_limbs(ad_, " + K + ", " + S +
+                 ", l_); for (int i_ = 0; i_ < " + K + "; i_++) c_ |= comet::f64_class(ad_[i_]); }\n";
+      for (int t = 0; t < 4; t++) pv_code += "          pv[" + std::to_string(j[t]) + "] = l_[" + std::to_string(t) + "];\n";
+      pv_code += "          pv[" + std::to_string(jc) + "] = c_; }\n";
+      fold_code += "    { u64 t3_[3]; comet::limbs_to_i192(pw + " + std::to_string(j[0]) + ", 4, t3_); val[" + w + "] = t3_[0]; val[" + w1 + "] = t3_[1]; val[" + w2 +
+                   "] = t3_[2]; val[" + cw + "] = pw[" + std::to_string(jc) + "]; }\n";
+      fs.aux_hi = nkw++;
+      fs.aux_lo = nkw++;
+      kops.push_back("G_UMAX64");
+      kops.push_back("G_UMAX64");
+      const std::string H = std::to_string(fs.aux_hi), L = std::to_string(fs.aux_lo);
+      kfeed_code += "        if (" + c + ") { " + decl + " for (int i_ = 0; i_ < " + K + "; i_++) { u64 h_ = comet::f64_exp_hi(ad_[i_]), l_ = comet::f64_exp_lo(ad_[i_]); if (h_ > kacc[" + H +
+                    "]) kacc[" + H + "] = h_; if (l_ > kacc[" + L + "]) kacc[" + L + "] = l_; } }\n";
+    } else {
+      const int hw = nw, lw = nw + 1;
+      nw += 2;
+      const std::string H = std::to_string(hw), L = std::to_string(lw);
+      init_code += "    a[" + H + "] = 0; a[" + L + "] = 0;\n";
+      combine_code += "    if (b[" + H + "] > a[" + H + "]) a[" + H + "] = b[" + H + "]; if (b[" + L + "] > a[" + L + "]) a[" + L + "] = b[" + L + "];\n";
+      gops.push_back("G_UMAX64"); gops.push_back("G_UMAX64");
+      gident.push_back("0ull"); gident.push_back("0ull");
+      const std::string body = "{ " + decl + " _Pragma(\"unroll\") for (int i_ = 0; i_ < " + K + "; i_++) { const double xd_ = ad_[i_]; comet::acc_feed_fix192(acc + " + w + ", xd_, " + S +
+                               "); acc[" + cw + "] |= comet::f64_class(xd_); const u64 h_ = comet::f64_exp_hi(xd_), l_ = comet::f64_exp_lo(xd_); if (h_ > acc[" + H + "]) acc[" + H +
+                               "] = h_; if (l_ > acc[" + L + "]) acc[" + L + "] = l_; } }";
+      g.stmt(cond.empty() ? body : "if (" + cond + ") " + body);
+      fs.aux_hi = 2 * fidx;
+      fs.aux_lo = 2 * fidx + 1;
+      kexport_code += "    atomicMax(aux + " + std::to_string(fs.aux_hi) + ", (unsigned long long)acc[" + H + "]); atomicMax(aux + " + std::to_string(fs.aux_lo) +
+                      ", (unsigned long long)acc[" + L + "]);\n";
+    }
+    fix_sums.push_back(fs);
+    fsums[key] = f;
+    return f;
+  }
   FSum get_fsum(const std::string& vkey, const std::string& fkey, const std::string& cond, const std::string& x) {
     const std::string key = "fsum|" + vkey + "|" + fkey;
     auto it = fsums.find(key);
@@ -3205,6 +3273,9 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
           int arity = 1;
           if (a.kind == AggKind::Avg) arity = 2;
           if (a.kind == AggKind::Sum && a.dtype.id == TypeId::Decimal) arity = 2;
+          if (a.kind == AggKind::Variance || a.kind == AggKind::Stddev) arity = 3;     // (count, mean, m2)
+          if (a.kind == AggKind::Covariance) arity = 4;                                // (count, mean1, mean2, algo_const)
+          if (a.kind == AggKind::Correlation) arity = 6;                               // … + (m2_1, m2_2)
           for (int k = 0; k < arity; k++) {
             size_t idx = state_base + final_state_pos++;
             if (idx >= cols.size()) throw CometError("Final aggregate: state column " + std::to_string(idx) + " is out of bound");
@@ -3529,6 +3600,69 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
     }
   }
 
+  // ---- statistical aggregates (var_* / stddev_* / covar_* / corr): exact moment sums (comet_device.hpp "Statistical aggregates") ----
+  struct StatSums { PrimSlot n; AggLowering::FSum sx, sy, sxx, syy, sxy; bool has_sxx = false, has_syy = false, has_sxy = false; };
+  // state columns and the explain text's shape of each function (variance.rs / stddev.rs / covariance.rs / correlation.rs state_fields)
+  auto stat_state_names = [](AggKind k) -> std::string {
+    if (k == AggKind::Covariance) return "count, mean1, mean2, algo_const";
+    if (k == AggKind::Correlation) return "count, mean1, mean2, algo_const, m2_1, m2_2";
+    return "count, mean, m2";
+  };
+  // the finished moments of one group (n, mean1, mean2, c, m2_1, m2_2 as expressions), then either the state columns or the result
+  auto stat_emit = [&](const AggExpr& a, const StatSums& ss, bool as_state, const char* label) {
+    const std::string N = "acc[" + std::to_string(ss.n.word) + "]";
+    const std::string MEAN1 = "comet::fix_mean(" + al.fargs(ss.sx) + ", " + N + ")";
+    std::vector<std::string> cols = {"(double)" + N, MEAN1};
+    if (a.kind == AggKind::Variance || a.kind == AggKind::Stddev) {
+      cols.push_back("comet::fix_m2(" + al.fargs(ss.sxx) + ", " + al.fargs(ss.sx) + ", " + N + ")");
+    } else {
+      cols.push_back("comet::fix_mean(" + al.fargs(ss.sy) + ", " + N + ")");
+      cols.push_back("comet::fix_comoment(" + al.fargs(ss.sxy) + ", " + al.fargs(ss.sx) + ", " + al.fargs(ss.sy) + ", " + N + ")");
+      if (a.kind == AggKind::Correlation) {
+        cols.push_back("comet::fix_m2(" + al.fargs(ss.sxx) + ", " + al.fargs(ss.sx) + ", " + N + ")");
+        cols.push_back("comet::fix_m2(" + al.fargs(ss.syy) + ", " + al.fargs(ss.sy) + ", " + N + ")");
+      }
+    }
+    const char* name = stat_agg_name(a);
+    if (as_state) {
+      // Partial / PartialMerge: the state columns, all Float64 and never NULL (an empty group is (0, 0, 0 …))
+      fin += "    {\n";
+      for (size_t c = 0; c < cols.size(); c++) {
+        fin += "      ((double*)" + out_val(out_j) + ")" + ROW + " = " + cols[c] + ";\n";
+        OutCol oc; oc.type = DType::of(TypeId::Double); oc.nullable = false;
+        d.out_cols.push_back(oc);
+        out_j++;
+      }
+      fin += "    }\n";
+      ex << "  agg" << label << ": " << name << "_f64 -> (" << stat_state_names(a.kind) << ")\n";
+      return;
+    }
+    const std::string sample = a.stats_type == 0 ? "true" : "false", nodz = a.null_on_divide_by_zero ? "true" : "false";
+    fin += "    { bool v_ = false; double r_ = 0.0;\n";
+    if (a.kind == AggKind::Correlation)
+      fin += "      r_ = comet::corr_finalize(" + cols[3] + ", " + cols[4] + ", " + cols[5] + ", " + N + ", " + (grouped ? "true" : "false") + ", " + nodz + ", v_);\n";
+    else
+      fin += "      r_ = comet::stat_finalize(" + cols[a.kind == AggKind::Covariance ? 3 : 2] + ", " + N + ", " + sample + ", " + nodz + ", v_);\n";
+    if (a.kind == AggKind::Stddev) fin += "      r_ = __dsqrt_rn(r_);\n";
+    fin += "      ((double*)" + out_val(out_j) + ")" + ROW + " = r_;\n";
+    fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = v_ ? 1 : 0; }\n";
+    OutCol oc; oc.type = DType::of(TypeId::Double); oc.nullable = true;
+    d.out_cols.push_back(oc);
+    out_j++;
+    ex << "  agg" << label << ": " << name << "_f64 -> Float64\n";
+  };
+  auto stat_check = [&](const AggExpr& a, size_t nchildren, bool final_mode) {
+    if (a.stats_type != 0 && a.stats_type != 1)
+      throw CometError("Unknown StatisticsType " + std::to_string(a.stats_type) + " for " + (a.kind == AggKind::Covariance ? "Covariance" : a.kind == AggKind::Stddev ? "Stddev" : "Variance"));
+    const bool two = a.kind == AggKind::Covariance || a.kind == AggKind::Correlation;
+    const size_t want = final_mode ? (a.kind == AggKind::Correlation ? 6 : two ? 4 : 3) : (two ? 2 : 1);
+    if (nchildren != want) throw CometError(std::string(stat_agg_name(a)) + " expects " + std::to_string(want) + (final_mode ? " state columns" : " children"));
+  };
+  auto stat_f64 = [&](const AggExpr& a, const Val& v, const char* what) {
+    if (v.rep != Rep::F64 || v.t.id != TypeId::Double)
+      throw CometError(std::string(stat_agg_name(a)) + " over " + v.t.str() + " is not supported: its " + what + " must be Float64 (Spark casts the input to double)");
+  };
+
   // rows that reach the aggregate
   PrimSlot rowcnt = al.get(Prim::RowCnt, "*", "", "", "");
   const std::string rowcnt_word = std::to_string(rowcnt.word);
@@ -3754,6 +3888,45 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
           ex << "  agg(final): " << (mn ? "min" : "max") << " -> " << v.t.str() << "\n";
           break;
         }
+        case AggKind::Variance: case AggKind::Stddev: case AggKind::Covariance: case AggKind::Correlation: {
+          // merge_batch of the Welford states as an EXACT merge of the states as they were rounded: N = Σ n_i (integers), S1 = Σ n_i·mean_i,
+          // S2 = Σ (m2_i + n_i·mean_i²) (co-moments: c_i + n_i·mean1_i·mean2_i), every product split into doubles that add up to it exactly
+          // (two_prod of two_prod: five addends); states with n_i = 0 are skipped (variance.rs merge_batch).  Then the Partial finisher.
+          stat_check(a, in.children.size(), true);
+          std::vector<Val> sv;
+          for (auto& c : in.children) {
+            sv.push_back(g.named(g.gen(c)));
+            stat_f64(a, sv.back(), "state column");
+          }
+          std::string cond;
+          for (auto& v : sv) cond = Gen::and_ok(cond, v.ok);
+          cond = Gen::and_ok(cond, "(" + sv[0].v + " != 0.0)");
+          const std::string vk = "fin:" + g.key_of(in.children[0]), n = sv[0].v;
+          // m + n·mean·other exactly: m, then the hi and lo of (hi of n·mean)·other and of (lo of n·mean)·other
+          auto merged = [&](const std::string& m, const std::string& mean, const std::string& other) {
+            const std::string ph = "comet::fp_mul(" + n + ", " + mean + ")", pl = "comet::two_prod_lo(" + n + ", " + mean + ")";
+            return std::vector<std::string>{m, "comet::fp_mul(" + ph + ", " + other + ")", "comet::two_prod_lo(" + ph + ", " + other + ")",
+                                            "comet::fp_mul(" + pl + ", " + other + ")", "comet::two_prod_lo(" + pl + ", " + other + ")"};
+          };
+          auto first_moment = [&](const std::string& mean) {
+            return std::vector<std::string>{"comet::fp_mul(" + n + ", " + mean + ")", "comet::two_prod_lo(" + n + ", " + mean + ")"};
+          };
+          StatSums ss;
+          ss.n = al.get(Prim::SumI64, vk + "#n", "", cond, "(i64)(" + n + ")", (u128)1 << 63);
+          ss.sx = al.get_fsum(vk + "#s1", "", cond, first_moment(sv[1].v));
+          if (a.kind == AggKind::Variance || a.kind == AggKind::Stddev) {
+            ss.sxx = al.get_fsum(vk + "#s2", "", cond, merged(sv[2].v, sv[1].v, sv[1].v));
+          } else {
+            ss.sy = al.get_fsum(vk + "#s1y", "", cond, first_moment(sv[2].v));
+            ss.sxy = al.get_fsum(vk + "#sxy", "", cond, merged(sv[3].v, sv[1].v, sv[2].v));
+            if (a.kind == AggKind::Correlation) {
+              ss.sxx = al.get_fsum(vk + "#s2", "", cond, merged(sv[4].v, sv[1].v, sv[1].v));
+              ss.syy = al.get_fsum(vk + "#s2y", "", cond, merged(sv[5].v, sv[2].v, sv[2].v));
+            }
+          }
+          stat_emit(a, ss, emit_state, emit_state ? "(partial-merge)" : "(final)");
+          break;
+        }
         default:
           throw CometError("Final mode of aggregate (tag " + std::to_string(a.proto_tag) + ") is not supported by the MI355X native engine");
       }
@@ -3929,6 +4102,35 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
         d.out_cols.push_back(s0);
         out_j++;
         ex << "  agg: " << (mn ? "min" : "max") << " -> " << v.t.str() << "\n";
+        break;
+      }
+      case AggKind::Variance: case AggKind::Stddev: case AggKind::Covariance: case AggKind::Correlation: {
+        // update_batch (variance.rs / covariance.rs / correlation.rs): rows where every child is non-NULL (and the FILTER holds) count.  The
+        // sums are keyed like avg's — "f64:" + the value's key — so avg(x), var_samp(x) and stddev_samp(x) over one x and filter share Σx and
+        // the count; a pair's sums also carry the other child's validity in their key
+        stat_check(a, in.children.size(), false);
+        const bool two = a.kind == AggKind::Covariance || a.kind == AggKind::Correlation;
+        Val x = g.named(g.gen(in.children[0]));
+        stat_f64(a, x, two ? "first child" : "child");
+        Val y = x;
+        if (two) {
+          y = g.named(g.gen(in.children[1]));
+          stat_f64(a, y, "second child");
+        }
+        const std::string kx = g.key_of(in.children[0]), ky = two ? g.key_of(in.children[1]) : kx;
+        const std::string cond = guarded(two ? Gen::and_ok(x.ok, y.ok) : x.ok);
+        const std::string vx = two && !y.ok.empty() ? kx + "|valid:" + ky : kx, vy = two && !x.ok.empty() ? ky + "|valid:" + kx : ky;
+        auto sq = [](const std::string& u, const std::string& v) {
+          return std::vector<std::string>{"comet::fp_mul(" + u + ", " + v + ")", "comet::two_prod_lo(" + u + ", " + v + ")"};
+        };
+        StatSums ss;
+        ss.n = al.get(Prim::Cnt, vx, fkey, cond, "");
+        ss.sx = al.get_fsum("f64:" + vx, fkey, cond, x.v);
+        if (two) ss.sy = al.get_fsum("f64:" + vy, fkey, cond, y.v);
+        if (a.kind != AggKind::Covariance) ss.sxx = al.get_fsum("f64sq:" + vx, fkey, cond, sq(x.v, x.v));
+        if (a.kind == AggKind::Correlation) ss.syy = al.get_fsum("f64sq:" + vy, fkey, cond, sq(y.v, y.v));
+        if (two) ss.sxy = al.get_fsum("f64xy:" + kx + "," + ky, fkey, cond, sq(x.v, y.v));
+        stat_emit(a, ss, true, "");
         break;
       }
       default:

@@ -1971,6 +1971,209 @@ CDEV void limbs_to_i192(const u64* w, int nl, u64* out3) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Statistical aggregates (var_* / stddev_* / covar_* / corr) from EXACT moment sums.  The reference runs Welford's recurrence row after row
+// and merges states pairwise (welford.rs), so its state moves with batch boundaries and its m2 loses about log2(mean² / variance) bits.
+// Here every moment is a function of a count and the exact Float64 sums above: Σx, Σy, and Σx², Σy², Σxy, where a product x·y enters
+// as the two doubles hi + lo that equal it EXACTLY (two_prod: the translation unit is compiled with -ffp-contract=off, so fma is the only
+// fused operation), and one fixed-point sum takes several such addends per row.  The finisher turns the exact sums into mean = Σx / n and
+// the co-moment Σxy − Σx·Σy / n in 512-bit integer arithmetic, exact up to one truncation far below the result's last bit: the state is
+// the same for every grid, chunking and row order, and mean and m2 are within an ULP of the exact moments of the rows.
+// ---------------------------------------------------------------------------------------------
+CDEV void two_prod(double a, double b, double& hi, double& lo) {   // hi + lo = a · b exactly (no underflow / overflow)
+  hi = fp_mul(a, b);
+  lo = fma(a, b, -hi);
+}
+CDEV double two_prod_lo(double a, double b) { double h, l; two_prod(a, b, h, l); return l; }
+// the k addends of one row, each truncated to the window 2^s, added EXACTLY (192 bits), then split into the four kLimbBits-bit limbs of the
+// grouped path's private words: limbs 0-2 unsigned, limb 3 the signed rest.  Each addend lies below 2^(s + kFixW), so for k ≤ 8 every limb
+// of a row is below 2^43 in magnitude — one row adds no more to a limb word than a single-addend row does, and kMaxRowsPerBlock still holds
+CDEV void fix_addends_limbs(const double* x, int k, int s, u64* limb) {
+  u64 t[3] = {0, 0, 0};
+  for (int i = 0; i < k; i++) acc_feed_fix192(t, x[i], s);
+  const u64 m = (1ull << kLimbBits) - 1;
+  limb[0] = t[0] & m;
+  limb[1] = ((t[0] >> 43) | (t[1] << 21)) & m;
+  limb[2] = ((t[1] >> 22) | (t[2] << 42)) & m;
+  limb[3] = (u64)((i64)t[2] >> 1);        // bits 129 … 191, signed
+}
+// (−1)^neg · m · 2^e with a 512-bit magnitude
+struct wide512 { u64 m[8]; int e; bool neg; };
+CDEV void w512_set_i192(wide512& w, const u64* t, int s) {
+  u64 a0 = t[0], a1 = t[1], a2 = t[2];
+  w.neg = (a2 >> 63) != 0;
+  if (w.neg) {
+    a0 = ~a0; a1 = ~a1; a2 = ~a2;
+    if (++a0 == 0) { if (++a1 == 0) ++a2; }
+  }
+  w.m[0] = a0; w.m[1] = a1; w.m[2] = a2;
+  for (int i = 3; i < 8; i++) w.m[i] = 0;
+  w.e = s;
+}
+CDEV void w512_set_u64(wide512& w, u64 v) {
+  w.m[0] = v;
+  for (int i = 1; i < 8; i++) w.m[i] = 0;
+  w.e = 0;
+  w.neg = false;
+}
+CDEV int w512_bits(const wide512& w) {
+  for (int i = 7; i >= 0; i--)
+    if (w.m[i]) return 64 * i + 64 - __builtin_clzll(w.m[i]);
+  return 0;
+}
+// r = a · b; both magnitudes must fit 256 bits (limbs 4-7 zero)
+CDEV void w512_mul(const wide512& a, const wide512& b, wide512& r) {
+  u64 p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 4; i++) {
+    u64 carry = 0;
+    for (int j = 0; j < 4; j++) {
+      const u128 t = (u128)a.m[i] * b.m[j] + p[i + j] + carry;
+      p[i + j] = (u64)t;
+      carry = (u64)(t >> 64);
+    }
+    p[i + 4] = carry;
+  }
+  for (int i = 0; i < 8; i++) r.m[i] = p[i];
+  r.e = a.e + b.e;
+  r.neg = a.neg != b.neg;
+}
+// the magnitude shifted so that its top bit is bit 511 (m ≠ 0)
+CDEV void w512_normalize(wide512& w) {
+  const int sh = 512 - w512_bits(w);
+  const int ws = sh >> 6, bs = sh & 63;
+  for (int k = 7; k >= 0; k--) {
+    const int src = k - ws;
+    u64 v = src >= 0 ? w.m[src] << bs : 0;
+    if (bs && src > 0) v |= w.m[src - 1] >> (64 - bs);
+    w.m[k] = v;
+  }
+  w.e -= sh;
+}
+// m >>= sh, truncating (0 ≤ sh < 512)
+CDEV void w512_shr(wide512& w, int sh) {
+  const int ws = sh >> 6, bs = sh & 63;
+  for (int k = 0; k < 8; k++) {
+    const int src = k + ws;
+    u64 v = src < 8 ? w.m[src] >> bs : 0;
+    if (bs && src + 1 < 8) v |= w.m[src + 1] << (64 - bs);
+    w.m[k] = v;
+  }
+  w.e += sh;
+}
+// r = a − b.  Operands of at most 384 significant bits: exact when their tops lie within 128 bits of each other (the only case in which
+// they can cancel), else the smaller loses bits more than 2^510 times below the result
+CDEV void w512_sub(wide512 a, wide512 b, wide512& r) {
+  b.neg = !b.neg;
+  if (w512_bits(b) == 0) { r = a; return; }
+  if (w512_bits(a) == 0) { r = b; return; }
+  w512_normalize(a);
+  w512_normalize(b);
+  if (a.e < b.e) { const wide512 t = a; a = b; b = t; }
+  const int d = a.e - b.e;
+  if (d >= 512) { r = a; return; }
+  w512_shr(b, d);
+  if (a.neg == b.neg) {
+    u64 c = 0;
+    for (int i = 0; i < 8; i++) {
+      const u128 t = (u128)a.m[i] + b.m[i] + c;
+      r.m[i] = (u64)t;
+      c = (u64)(t >> 64);
+    }
+    r.e = a.e;
+    r.neg = a.neg;
+    if (c) { w512_shr(r, 1); r.m[7] |= 1ull << 63; }
+    return;
+  }
+  bool a_ge = true;
+  for (int i = 7; i >= 0; i--)
+    if (a.m[i] != b.m[i]) { a_ge = a.m[i] > b.m[i]; break; }
+  const wide512& x = a_ge ? a : b;
+  const wide512& y = a_ge ? b : a;
+  u64 bw = 0;
+  for (int i = 0; i < 8; i++) {
+    const u64 xi = x.m[i], yi = y.m[i];
+    const u64 t = xi - yi - bw;
+    bw = (xi < yi || (xi == yi && bw)) ? 1 : 0;
+    r.m[i] = t;
+  }
+  r.e = a.e;
+  r.neg = x.neg;
+}
+// w / n rounded to the nearest double (ties to even; a subnormal result may round twice)
+CDEV double w512_div_u64_to_f64(wide512 w, u64 n) {
+  if (w512_bits(w) == 0) return 0.0;
+  w512_normalize(w);
+  const u128 top = ((u128)w.m[7] << 64) | w.m[6];
+  bool sticky = false;
+  for (int i = 0; i < 6; i++) sticky |= w.m[i] != 0;
+  const u128 q = top / (u128)n;                  // ≥ 2^63: at least 11 bits below the mantissa
+  sticky |= (top % (u128)n) != 0;
+  const u64 qh = (u64)(q >> 64);
+  const int L = qh ? 128 - __builtin_clzll(qh) : 64 - __builtin_clzll((u64)q);
+  const int sh = L - 53;
+  u64 mant = (u64)(q >> sh);
+  const bool guard = (u64)(q >> (sh - 1)) & 1;
+  sticky |= (q & ((((u128)1) << (sh - 1)) - 1)) != 0;
+  if (guard && (sticky || (mant & 1))) mant += 1;
+  const double r = ldexp((double)mant, w.e + 384 + sh);
+  return w.neg ? -r : r;
+}
+// mean = S / n of an exact sum S = t · 2^s; with inf / NaN addends the IEEE outcome of the sum, divided by n
+CDEV double fix_mean(const u64* t, int s, u64 cls, u64 n) {
+  if (n == 0) return 0.0;
+  if (cls) return fix192_to_f64(t, s, cls) / (double)n;
+  wide512 w;
+  w512_set_i192(w, t, s);
+  return w512_div_u64_to_f64(w, n);
+}
+// co-moment Σ(x − x̄)(y − ȳ) = (n · Sxy − Sx · Sy) / n from exact sums; NaN once an addend of any of them was inf or NaN
+CDEV double fix_comoment(const u64* sxy, int sxy_s, u64 sxy_cls, const u64* sx, int sx_s, u64 sx_cls, const u64* sy, int sy_s, u64 sy_cls, u64 n) {
+  if (n == 0) return 0.0;
+  if (sxy_cls | sx_cls | sy_cls) return __longlong_as_double(0x7ff8000000000000ll);
+  wide512 a, b, c, p, q;
+  w512_set_u64(c, n);
+  w512_set_i192(a, sxy, sxy_s);
+  w512_mul(c, a, p);
+  w512_set_i192(a, sx, sx_s);
+  w512_set_i192(b, sy, sy_s);
+  w512_mul(a, b, q);
+  w512_sub(p, q, a);
+  return w512_div_u64_to_f64(a, n);
+}
+// m2 = Σ(x − x̄)²: never negative (a window too narrow for every addend truncates low bits, which could push an exact zero below it)
+CDEV double fix_m2(const u64* sxx, int sxx_s, u64 sxx_cls, const u64* sx, int sx_s, u64 sx_cls, u64 n) {
+  const double m2 = fix_comoment(sxx, sxx_s, sxx_cls, sx, sx_s, sx_cls, sx, sx_s, sx_cls, n);
+  return m2 < 0.0 ? 0.0 : m2;
+}
+// finalize_moments (welford.rs): NULL for no rows, NULL or NaN (null_on_divide_by_zero) for a SAMPLE of one row, else moment / (n or n − 1)
+CDEV double stat_finalize(double moment, u64 n, bool sample, bool null_on_div0, bool& valid) {
+  valid = n != 0;
+  if (!valid) return 0.0;
+  if (sample && n == 1) {
+    valid = !null_on_div0;
+    return __longlong_as_double(0x7ff8000000000000ll);
+  }
+  return moment / (double)(sample ? n - 1 : n);
+}
+// corr (correlation.rs): the grouped accumulator's c / sqrt(m2x · m2y) (NULL when either is 0), the ungrouped one's
+// covar_pop / (stddev_pop(x) · stddev_pop(y)) (NULL when either is 0); count 0 → NULL, count 1 → NULL or NaN
+CDEV double corr_finalize(double c, double m2x, double m2y, u64 n, bool grouped, bool null_on_div0, bool& valid) {
+  valid = n != 0;
+  if (!valid) return 0.0;
+  if (n == 1) {
+    valid = !null_on_div0;
+    return __longlong_as_double(0x7ff8000000000000ll);
+  }
+  if (grouped) {
+    valid = m2x != 0.0 && m2y != 0.0;
+    return valid ? c / __dsqrt_rn(fp_mul(m2x, m2y)) : 0.0;
+  }
+  const double dn = (double)n, s1 = __dsqrt_rn(m2x / dn), s2 = __dsqrt_rn(m2y / dn);
+  valid = s1 != 0.0 && s2 != 0.0;
+  return valid ? (c / dn) / fp_mul(s1, s2) : 0.0;
+}
+// (end of the statistical aggregates' helpers)
+
 // LDS slot (level 1): limb-form accumulators; padded to an ODD number of 8-byte words so consecutive slots
 // start on different banks.
 template <int NK, int NPW>

@@ -494,6 +494,7 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
         // SUM / COUNT / AVG of exact types over a frame that starts at the partition start (whole partition, or up to the current row /
         // peer group) — the frames the reference runs with its own Spark-exact accumulators (planner.rs:2953-2972)
         const AggExpr& a = fn.agg;
+        if (const char* sn = stat_agg_name(a)) throw CometError(std::string("Window: ") + sn + " over a window frame is not supported yet");
         // frames: every combination of UNBOUNDED / CURRENT ROW bounds, ROWS frames with literal offsets (n PRECEDING / n FOLLOWING), and
         // RANGE frames with value offsets over ONE integer ORDER BY key (x PRECEDING below, y FOLLOWING above — all the JVM side sends,
         // CometWindowExec.scala:588-632; it keeps DATE / DECIMAL keys in Spark): two binary searches per row over the key

@@ -115,21 +115,36 @@ struct Expr {
 };
 
 // AggExpr.expr_struct oneof tags (expr.proto:143-176)
-enum class AggKind : int { Count = 2, Sum = 3, Min = 4, Max = 5, Avg = 6, First = 7, Last = 8, Unsupported = -1 };
+enum class AggKind : int { Count = 2, Sum = 3, Min = 4, Max = 5, Avg = 6, First = 7, Last = 8, Covariance = 12, Variance = 13, Stddev = 14, Correlation = 15,
+                           Unsupported = -1 };
 
 struct AggExpr {
   AggKind kind = AggKind::Unsupported;
   int proto_tag = 0;
-  std::vector<ExprP> children;    // Count.children or the single child
-  DType dtype;                    // Sum/Min/Max/Avg.datatype (result type)
+  std::vector<ExprP> children;    // Count.children, the single child, or Covariance / Correlation (child1, child2)
+  DType dtype;                    // Sum/Min/Max/Avg/Variance/Stddev/Covariance/Correlation.datatype (result type)
   DType sum_dtype;                // Avg.sum_datatype
   EvalMode eval_mode = EvalMode::Legacy;
   ExprP filter;                   // AggExpr.filter = 89
   bool ignore_nulls = false;      // First / Last
+  int stats_type = 0;             // Variance / Stddev / Covariance: StatisticsType (expr.proto:178-181) 0 SAMPLE, 1 POPULATION
+  bool null_on_divide_by_zero = false;   // Variance / Stddev / Covariance / Correlation
   uint64_t expr_id = 0;
   bool has_expr_id = false;
   std::shared_ptr<QueryContext> qctx;      // AggExpr.query_context = 90: goes with the aggregate's DecimalSumOverflow (sum_decimal.rs wrap_error_with_context)
 };
+
+// Spark's SQL name of a statistical aggregate (var_samp, stddev_pop, covar_samp, corr); nullptr for the other kinds
+inline const char* stat_agg_name(const AggExpr& a) {
+  const bool pop = a.stats_type == 1;
+  switch (a.kind) {
+    case AggKind::Variance: return pop ? "var_pop" : "var_samp";
+    case AggKind::Stddev: return pop ? "stddev_pop" : "stddev_samp";
+    case AggKind::Covariance: return pop ? "covar_pop" : "covar_samp";
+    case AggKind::Correlation: return "corr";
+    default: return nullptr;
+  }
+}
 
 // Operator.op_struct oneof tags (operator.proto:32-79)
 enum class OpKind : int {

@@ -355,8 +355,25 @@ AggExpr decode_agg_expr(Reader r) {
     if (f == 90 || wt != 2) { r.skip(wt); continue; }
     a.proto_tag = f;
     Reader b = r.sub();
-    if (f >= 2 && f <= 8) a.kind = (AggKind)f;
+    if ((f >= 2 && f <= 8) || (f >= 12 && f <= 15)) a.kind = (AggKind)f;
     else { a.kind = AggKind::Unsupported; continue; }
+    if (f >= 12 && f <= 15) {
+      // Covariance{child1 = 1, child2 = 2, null_on_divide_by_zero = 3, datatype = 4, stats_type = 5}, Variance / Stddev{child = 1,
+      // null_on_divide_by_zero = 2, datatype = 3, stats_type = 4}, Correlation{child1 = 1, child2 = 2, null_on_divide_by_zero = 3, datatype = 4}
+      // (expr.proto:237-264)
+      const bool two = f == 12 || f == 15;
+      ExprP kids[2];
+      while (!b.done()) {
+        int wt2, f2 = b.tag(wt2);
+        if ((f2 == 1 || (two && f2 == 2)) && wt2 == 2) kids[f2 - 1] = decode_expr(b.sub());
+        else if (f2 == (two ? 3 : 2) && wt2 == 0) a.null_on_divide_by_zero = b.varint() != 0;
+        else if (f2 == (two ? 4 : 3) && wt2 == 2) a.dtype = decode_datatype(b.sub());
+        else if (f != 15 && f2 == (two ? 5 : 4) && wt2 == 0) a.stats_type = (int)b.varint();
+        else b.skip(wt2);
+      }
+      for (int k = 0; k < (two ? 2 : 1); k++) a.children.push_back(kids[k]);
+      continue;
+    }
     while (!b.done()) {
       int wt2, f2 = b.tag(wt2);
       if (f2 == 1 && wt2 == 2) a.children.push_back(decode_expr(b.sub()));

@@ -441,8 +441,10 @@ class AggExpr:
     eval_mode: int = LEGACY
     filter: Optional[Expr] = None
     ignore_nulls: bool = False      # first | last
+    stats_type: int = 0             # variance | stddev | covariance: SAMPLE (0) or POPULATION (1)
+    null_on_divide_by_zero: bool = True      # variance | stddev | covariance | corr
 
-    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8)
+    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, covariance=12, variance=13, stddev=14, corr=15)
 
     def encode(self) -> bytes:
         if self.kind == "count":
@@ -459,6 +461,15 @@ class AggExpr:
             body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.dtype.encode()) + _f_msg(3, self.sum_dtype.encode())
             if self.eval_mode:
                 body += _f_varint(4, self.eval_mode)
+        elif self.kind in ("variance", "stddev"):      # Variance / Stddev{child=1, null_on_divide_by_zero=2, datatype=3, stats_type=4} (expr.proto:245-257)
+            body = _f_msg(1, self.children[0].encode()) + (_f_varint(2, 1) if self.null_on_divide_by_zero else b"") + _f_msg(3, self.dtype.encode())
+            if self.stats_type:
+                body += _f_varint(4, self.stats_type)
+        elif self.kind in ("covariance", "corr"):      # Covariance{child1=1, child2=2, null_on_divide_by_zero=3, datatype=4, stats_type=5}, Correlation{… datatype=4}
+            body = (_f_msg(1, self.children[0].encode()) + _f_msg(2, self.children[1].encode()) + (_f_varint(3, 1) if self.null_on_divide_by_zero else b"") +
+                    _f_msg(4, self.dtype.encode()))
+            if self.kind == "covariance" and self.stats_type:
+                body += _f_varint(5, self.stats_type)
         else:
             raise ValueError(self.kind)
         out = _f_msg(self.TAGS[self.kind], body)
@@ -493,6 +504,28 @@ def first_(child: Expr, dtype: DataType, ignore_nulls: bool = False) -> AggExpr:
 
 def last_(child: Expr, dtype: DataType, ignore_nulls: bool = False) -> AggExpr:
     return AggExpr("last", [child], dtype=dtype, ignore_nulls=ignore_nulls)
+
+
+SAMPLE, POPULATION = 0, 1      # StatisticsType (expr.proto:178-181)
+
+
+def variance(child: Expr, stats_type: int = SAMPLE, null_on_divide_by_zero: bool = True, filter: Optional[Expr] = None) -> AggExpr:
+    """var_samp / var_pop; null_on_divide_by_zero is what the JVM sends for !spark.sql.legacy.statisticalAggregate"""
+    return AggExpr("variance", [child], dtype=T_DOUBLE, stats_type=stats_type, null_on_divide_by_zero=null_on_divide_by_zero, filter=filter)
+
+
+def stddev(child: Expr, stats_type: int = SAMPLE, null_on_divide_by_zero: bool = True, filter: Optional[Expr] = None) -> AggExpr:
+    """stddev_samp / stddev_pop"""
+    return AggExpr("stddev", [child], dtype=T_DOUBLE, stats_type=stats_type, null_on_divide_by_zero=null_on_divide_by_zero, filter=filter)
+
+
+def covariance(child1: Expr, child2: Expr, stats_type: int = SAMPLE, null_on_divide_by_zero: bool = True, filter: Optional[Expr] = None) -> AggExpr:
+    """covar_samp / covar_pop"""
+    return AggExpr("covariance", [child1, child2], dtype=T_DOUBLE, stats_type=stats_type, null_on_divide_by_zero=null_on_divide_by_zero, filter=filter)
+
+
+def corr(child1: Expr, child2: Expr, null_on_divide_by_zero: bool = True, filter: Optional[Expr] = None) -> AggExpr:
+    return AggExpr("corr", [child1, child2], dtype=T_DOUBLE, null_on_divide_by_zero=null_on_divide_by_zero, filter=filter)
 
 
 # --------------------------------------------------------------------------- operators (operator.proto)

@@ -178,7 +178,11 @@ def probes():
 
 
 ACCEPTED_AGGREGATES = {"Sum": "integers, decimals, Float64 (exact, order independent)", "Average": "decimals and Float64", "Count": "", "Min": "not decimal(>18) in grouped aggregates",
-                       "Max": "not decimal(>18) in grouped aggregates", "First": "window frames only", "Last": "window frames only"}
+                       "Max": "not decimal(>18) in grouped aggregates", "First": "window frames only", "Last": "window frames only",
+                       "VarianceSamp": "Float64, not over window frames (exact moments, order independent)", "VariancePop": "Float64, not over window frames (exact moments, order independent)",
+                       "StddevSamp": "Float64, not over window frames (exact moments, order independent)", "StddevPop": "Float64, not over window frames (exact moments, order independent)",
+                       "CovSample": "Float64, not over window frames (exact moments, order independent)", "CovPopulation": "Float64, not over window frames (exact moments, order independent)",
+                       "Corr": "Float64, not over window frames (exact moments, order independent)"}
 
 
 def probe_plan(expr):
@@ -250,7 +254,8 @@ def render() -> str:
     w("")
     w("* `Cast`: timestamp -> float / decimal / boolean, binary, casts of a COMPUTED string; a cast to string is an output column (not an operand); on a")
     w("  device-resident input ANY type mismatch with the declared Scan fields.  Time zones come from the system's database ($TZDIR, /usr/share/zoneinfo).")
-    w("* `Min` / `Max` of decimal(> 18) in grouped aggregates; more than eight Float64 sums / averages in one aggregate.")
+    w("* `Min` / `Max` of decimal(> 18) in grouped aggregates; more than eight Float64 sums / averages in one aggregate (a variance or stddev takes two,")
+    w("  a covariance three, a corr five; in a Partial aggregate functions over the same columns share theirs); statistical aggregates over window frames.")
     w("* `RLike`: patterns outside the byte-exact subset (`\\\\p{..}`, scoped flags, look-around, `\\\\b` under `(?m)`) are refused by name.")
     w("* `Concat`: of Utf8 columns and literals (at most eight), as an output column.")
     w("* Computed Utf8 values used as operands of further expressions must fit 15 bytes (literals, substring, CASE over those).")
@@ -272,6 +277,13 @@ def render() -> str:
     w("* Float64 / Float32 `sum` and `avg`: the reference adds in row order (its result moves with batch and partition boundaries); here the sum is the EXACT real sum")
     w("  rounded once — the same bits for every order, chunking and grid, at most half an ulp from the truth, within the reference's own a-priori error bound of its")
     w("  sequential sum and bit-equal to it wherever that one is exact (`tests/test_float_agg_gpu.py`).  Up to eight such sums per aggregate.")
+    w("* `var_samp` / `var_pop`, `stddev_samp` / `stddev_pop`, `covar_samp` / `covar_pop`, `corr`: the reference runs Welford's recurrence in row order and")
+    w("  merges states pairwise, so its states move with batch boundaries and its m2 loses about log2(mean² / variance) bits.  Here the moments come from exact")
+    w("  Float64 sums of x, y, x², y², x·y (products split exactly with fma): the results are deterministic (the same bits for every order, chunking and grid); a")
+    w("  Partial state's mean, m2 and co-moments are within 1 ulp of the exact moments of its rows; a Final / PartialMerge merge is exact over the states as")
+    w("  they were rounded; variance, stddev and covariance results are within 2 ulp of exact, corr within 4 (`tests/test_stat_agg_gpu.py`).  A group with a")
+    w("  NaN or ±inf input has NaN results on both sides, but its state's `mean` differs: here it is the IEEE outcome of the exact sum divided by the count,")
+    w("  in the reference it depends on the row order (inf or NaN).")
     w("* Join and hash-aggregate OUTPUT ORDER is unspecified in the reference (hash-table order per batch); tests compare multisets.  A sort-merge join's output is")
     w("  ordered by its keys only where that order is observable (plan output, Limit, shuffle file).")
     w("* Everything else on the path — integers, decimals (HALF_UP, overflow → NULL / ANSI error), dates, timestamps, strings, hashes (murmur3 / xxhash64), partition")
