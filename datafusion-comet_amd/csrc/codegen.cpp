@@ -2841,7 +2841,7 @@ struct Gen {
 // use one sum and one count).  The same lowering feeds the ungrouped template (registers) and the
 // grouped template (per-group slots, atomics).
 // ---------------------------------------------------------------------------------------------
-enum class Prim { Cnt, RowCnt, Sum128, Sum192, SumI64, SumF64, AMaxHi, SignFlags, MinI64, MaxI64, MinI128, MaxI128, MinF64, MaxF64 };
+enum class Prim { Cnt, RowCnt, Sum128, Sum192, SumI64, SumF64, AMaxHi, SignFlags, MinI64, MaxI64, MinI128, MaxI128, MinF64, MaxF64, BitAnd, BitOr, BitXor };
 
 struct PrimSlot {
   Prim prim;
@@ -3027,6 +3027,80 @@ struct AggLowering {
     return npw++;
   }
 
+  // ---- first / last: the ordinal of the winning row (min / max of a unique key) and value words that no accumulation touches (comet_device.hpp
+  // "first / last").  Ungrouped: ordinal and value travel together through the private accumulators.  Grouped: only the ordinal is accumulated,
+  // P::pick fills the value words afterwards ----
+  struct Pick { int ord = 0, val = 0, ok = 0; bool first = true; };
+  struct PickReq { Pick p; ExprP child; };
+  std::map<std::string, Pick> pick_slots;
+  std::vector<PickReq> pick_reqs;      // grouped: what P::pick has to evaluate
+  static const char* ord_identity(bool first) { return first ? "0x7fffffffffffffffull" : "0x8000000000000000ull"; }
+  // the value as one or two 64-bit words, bit for bit
+  static void value_words(const Val& v, const std::string& x, std::string& lo, std::string& hi) {
+    hi.clear();
+    switch (v.rep) {
+      case Rep::B: lo = "(u64)((" + x + ") ? 1 : 0)"; break;
+      case Rep::I32: case Rep::I64: lo = "(u64)(i64)(" + x + ")"; break;
+      case Rep::I128: lo = "comet::lo64(" + x + ")"; hi = "comet::hi64(" + x + ")"; break;
+      case Rep::F64: lo = "(u64)__double_as_longlong(" + x + ")"; break;
+      case Rep::F32: lo = "(u64)(u32)__float_as_int(" + x + ")"; break;
+      default: throw CometError("internal: first / last over a value that is not fixed-width");
+    }
+  }
+  static std::string value_read(const Val& v, int w) {
+    const std::string A = "acc[" + std::to_string(w) + "]";
+    switch (v.rep) {
+      case Rep::B: return "(u8)" + A;
+      case Rep::I32: case Rep::I64: return v.t.id == TypeId::Decimal ? "(i128)(i64)" + A : std::string("(") + store_ctype(v.t) + ")(i64)" + A;
+      case Rep::I128: return "comet::mk128(acc[" + std::to_string(w + 1) + "], " + A + ")";
+      case Rep::F64: return "__longlong_as_double((i64)" + A + ")";
+      case Rep::F32: return "__int_as_float((int)(u32)" + A + ")";
+      default: throw CometError("internal: first / last over a value that is not fixed-width");
+    }
+  }
+  // cond: the row may win iff cond (empty = always); v: the child's value at the row; key: what makes two requests the same
+  Pick get_pick(bool first, const std::string& key, const std::string& cond, const Val& v, const ExprP& child) {
+    const std::string k = std::string(first ? "first|" : "last|") + key;
+    auto it = pick_slots.find(k);
+    if (it != pick_slots.end()) return it->second;
+    const int nval = v.rep == Rep::I128 ? 2 : 1;
+    Pick p;
+    p.first = first;
+    p.ord = nw;
+    p.val = nw + 1;
+    p.ok = nw + 1 + nval;
+    nw += 2 + nval;
+    const char* id = ord_identity(first);
+    const std::string W = std::to_string(p.ord), cmp = first ? " < " : " > ";
+    init_code += "    a[" + W + "] = " + id + ";";
+    for (int t = p.val; t <= p.ok; t++) init_code += " a[" + std::to_string(t) + "] = 0;";
+    init_code += "\n";
+    combine_code += "    if ((i64)b[" + W + "]" + cmp + "(i64)a[" + W + "]) {";
+    for (int t = p.ord; t <= p.ok; t++) combine_code += " a[" + std::to_string(t) + "] = b[" + std::to_string(t) + "];";
+    combine_code += " }\n";
+    gops.push_back(first ? "G_IMIN64" : "G_IMAX64");
+    gident.push_back(id);
+    for (int t = p.val; t <= p.ok; t++) { gops.push_back("G_CONT"); gident.push_back("0ull"); }
+    const std::string ordinal = "(prm.iarg[" + std::to_string(kRowBaseArg) + "] + idx[r])";
+    if (grouped) {
+      const int j = pword(first ? "G_IMIN64" : "G_IMAX64", id);
+      pv_code += "        pv[" + std::to_string(j) + "] = (" + (cond.empty() ? std::string("true") : cond) + ") ? (u64)" + ordinal + " : " + id + ";\n";
+      fold_code += "    val[" + W + "] = pw[" + std::to_string(j) + "];";
+      for (int t = p.val; t <= p.ok; t++) fold_code += " val[" + std::to_string(t) + "] = 0;";
+      fold_code += "\n";
+      pick_reqs.push_back({p, child});
+    } else {
+      std::string lo, hi;
+      value_words(v, v.v, lo, hi);
+      std::string body = "{ const i64 o_ = " + ordinal + "; if (o_" + cmp + "(i64)acc[" + W + "]) { acc[" + W + "] = (u64)o_; acc[" + std::to_string(p.val) + "] = " + lo + ";";
+      if (nval == 2) body += " acc[" + std::to_string(p.val + 1) + "] = " + hi + ";";
+      body += " acc[" + std::to_string(p.ok) + "] = " + (v.ok.empty() ? std::string("1ull") : "(" + v.ok + ") ? 1ull : 0ull") + "; } }";
+      g.stmt(cond.empty() ? body : "if (" + cond + ") " + body);
+    }
+    pick_slots[k] = p;
+    return p;
+  }
+
   // cond: row contributes iff cond (empty = always); x: value expression typed for the primitive;
   // maxabs: static bound on |x| (integer sums), used to size the limb split
   PrimSlot get(Prim p, const std::string& vkey, const std::string& fkey, const std::string& cond, const std::string& x,
@@ -3158,6 +3232,21 @@ struct AggLowering {
         } else feed(std::string("{ u64 t_ = (u64)__double_as_longlong((double)(") + x + ")); comet::acc_" + (mn ? "fmin64" : "fmax64") + "(acc + " + w + ", &t_); }");
         break;
       }
+      case Prim::BitAnd: case Prim::BitOr: case Prim::BitXor: {
+        // the integer sign-extended into the word; and / or / xor commute with that, the result is truncated on the way out
+        const char* gop = p == Prim::BitAnd ? "G_AND64" : p == Prim::BitOr ? "G_OR64" : "G_XOR64";
+        const char* cop = p == Prim::BitAnd ? "&=" : p == Prim::BitOr ? "|=" : "^=";
+        const char* id = p == Prim::BitAnd ? "0xffffffffffffffffull" : "0ull";
+        init_code += "    a[" + w + "] = " + id + ";\n";
+        combine_code += "    a[" + w + "] " + cop + " b[" + w + "];\n";
+        ops({gop}, {id});
+        if (grouped) {
+          int j = pword(gop, id);
+          pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? (u64)(i64)(" + x + ") : " + id + ";\n";
+          fold_code += "    val[" + w + "] = pw[" + std::to_string(j) + "];\n";
+        } else feed("acc[" + w + "] " + cop + " (u64)(i64)(" + x + ");");
+        break;
+      }
       case Prim::MinI128: case Prim::MaxI128: {
         const bool mn = p == Prim::MinI128;
         if (grouped) throw CometError("min/max of a decimal wider than 18 digits is not supported in a grouped GPU aggregate yet");
@@ -3276,6 +3365,7 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
           if (a.kind == AggKind::Variance || a.kind == AggKind::Stddev) arity = 3;     // (count, mean, m2)
           if (a.kind == AggKind::Covariance) arity = 4;                                // (count, mean1, mean2, algo_const)
           if (a.kind == AggKind::Correlation) arity = 6;                               // … + (m2_1, m2_2)
+          if (a.kind == AggKind::First || a.kind == AggKind::Last) arity = 2;          // (value, is_set); the bitwise aggregates: one column
           for (int k = 0; k < arity; k++) {
             size_t idx = state_base + final_state_pos++;
             if (idx >= cols.size()) throw CometError("Final aggregate: state column " + std::to_string(idx) + " is out of bound");
@@ -3663,6 +3753,60 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
       throw CometError(std::string(stat_agg_name(a)) + " over " + v.t.str() + " is not supported: its " + what + " must be Float64 (Spark casts the input to double)");
   };
 
+  // ---- first / last (planner.rs:2679-2702 → DataFusion's FirstValue / LastValue without ORDER BY) and bit_and / bit_or / bit_xor (:2703-2735) ----
+  // first / last keep a fixed-width state: Boolean, the integers, the floats (bit for bit), Date, Timestamp / TimestampNTZ, Decimal of any precision
+  auto pick_check = [&](const AggExpr& a, const ExprP& child) {
+    const char* name = order_bit_agg_name(a.kind);
+    DType t = child->dtype;
+    if (child->kind == ExprKind::Bound && child->bound_index >= 0 && (size_t)child->bound_index < d.in_types.size()) t = d.in_types[(size_t)child->bound_index];
+    if (t.id == TypeId::String || t.id == TypeId::Bytes || t.is_nested())
+      throw CometError(std::string(name) + " over " + t.str() + " is not supported in a HashAggregate by the MI355X native engine yet (its state is fixed-width: Boolean, integers, floats, Date, Timestamp, Decimal)");
+  };
+  auto pick_check_val = [&](const AggExpr& a, const Val& v) {
+    if (v.rep == Rep::STR)
+      throw CometError(std::string(order_bit_agg_name(a.kind)) + " over " + v.t.str() + " is not supported in a HashAggregate by the MI355X native engine yet (its state is fixed-width: Boolean, integers, floats, Date, Timestamp, Decimal)");
+    store_ctype(v.t);
+  };
+  // Partial state = (value: child type, nullable; is_set: Boolean) — Spark's own buffer (First.aggBufferAttributes = first :: valueSet) and, from memory (its
+  // source is not in the reference tree), DataFusion's FirstValue::state_fields without orderings; Final evaluates to the value
+  auto pick_emit = [&](const AggExpr& a, const Val& v, const AggLowering::Pick& p, bool as_state, const char* label) {
+    const char* st = store_ctype(v.t);
+    const std::string set = "(acc[" + std::to_string(p.ord) + "] != " + AggLowering::ord_identity(p.first) + ")";
+    fin += "    { const bool set_ = " + set + ", ok_ = set_ && acc[" + std::to_string(p.ok) + "] != 0;\n";
+    fin += "      ((" + std::string(st) + "*)" + out_val(out_j) + ")" + ROW + " = ok_ ? " + AggLowering::value_read(v, p.val) + " : (" + st + ")0;\n";
+    fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = ok_ ? 1 : 0;\n";
+    OutCol s0; s0.type = v.t; s0.nullable = true;
+    d.out_cols.push_back(s0);
+    out_j++;
+    const std::string name = std::string(order_bit_agg_name(a.kind)) + (a.ignore_nulls ? "(ignore_nulls)" : "");
+    if (as_state) {
+      fin += "      ((u8*)" + out_val(out_j) + ")" + ROW + " = set_ ? 1 : 0;\n";
+      OutCol s1; s1.type = DType::of(TypeId::Bool); s1.nullable = false;
+      d.out_cols.push_back(s1);
+      out_j++;
+      ex << "  agg" << label << ": " << name << " -> (" << v.t.str() << ", is_set)\n";
+    } else {
+      ex << "  agg" << label << ": " << name << " -> " << v.t.str() << "\n";
+    }
+    fin += "    }\n";
+  };
+  // state = result = one nullable column of the input's integer type, in every mode; merging states is the same operation
+  auto bit_agg = [&](const AggExpr& a, const Val& v, const std::string& vkey, const std::string& fkey, const std::string& cond, const char* label) {
+    const char* name = order_bit_agg_name(a.kind);
+    if (!v.t.is_integer())
+      throw CometError(std::string(name) + " over " + v.t.str() + " is not supported: the bitwise aggregates take Int8, Int16, Int32 or Int64 (AggSerde.bitwiseAggTypeSupported)");
+    PrimSlot cnt = al.get(Prim::Cnt, vkey, fkey, cond, "");
+    PrimSlot s = al.get(a.kind == AggKind::BitAnd ? Prim::BitAnd : a.kind == AggKind::BitOr ? Prim::BitOr : Prim::BitXor, vkey, fkey, cond, v.v);
+    const char* st = store_ctype(v.t);
+    const std::string C = "acc[" + std::to_string(cnt.word) + "]";
+    fin += "    ((" + std::string(st) + "*)" + out_val(out_j) + ")" + ROW + " = " + C + " ? (" + st + ")(i64)acc[" + std::to_string(s.word) + "] : (" + st + ")0;\n";
+    fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = " + C + " ? 1 : 0;\n";
+    OutCol oc; oc.type = v.t; oc.nullable = true;
+    d.out_cols.push_back(oc);
+    out_j++;
+    ex << "  agg" << label << ": " << name << " -> " << v.t.str() << "\n";
+  };
+
   // rows that reach the aggregate
   PrimSlot rowcnt = al.get(Prim::RowCnt, "*", "", "", "");
   const std::string rowcnt_word = std::to_string(rowcnt.word);
@@ -3927,6 +4071,25 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
           stat_emit(a, ss, emit_state, emit_state ? "(partial-merge)" : "(final)");
           break;
         }
+        case AggKind::First: case AggKind::Last: {
+          // merge_batch: the first (last) STATE ROW of the group whose is_set is true, in state-row order; its value may be NULL
+          if (in.children.size() != 2) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects (value, is_set) state columns");
+          pick_check(a, in.children[0]);
+          Val v = g.named(g.gen(in.children[0]));
+          Val s2 = g.named(g.gen(in.children[1]));
+          pick_check_val(a, v);
+          if (s2.rep != Rep::B) throw CometError(std::string("Final ") + order_bit_agg_name(a.kind) + " expects (value, is_set) state columns, got is_set : " + s2.t.str());
+          const std::string key = "fin:" + g.key_of(in.children[0]) + "|" + g.key_of(in.children[1]);
+          AggLowering::Pick p = al.get_pick(a.kind == AggKind::First, key, Gen::and_ok(s2.ok, s2.v), v, in.children[0]);
+          pick_emit(a, v, p, emit_state, emit_state ? "(partial-merge)" : "(final)");
+          break;
+        }
+        case AggKind::BitAnd: case AggKind::BitOr: case AggKind::BitXor: {
+          if (in.children.size() != 1) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects one state column");
+          Val v = g.named(g.gen(in.children[0]));
+          bit_agg(a, v, "fin:" + g.key_of(in.children[0]), "", v.ok, emit_state ? "(partial-merge)" : "(final)");
+          break;
+        }
         default:
           throw CometError("Final mode of aggregate (tag " + std::to_string(a.proto_tag) + ") is not supported by the MI355X native engine");
       }
@@ -4133,6 +4296,23 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
         stat_emit(a, ss, true, "");
         break;
       }
+      case AggKind::First: case AggKind::Last: {
+        // update_batch: the first (last) row that passes the FILTER — with ignore_nulls, the first (last) such row whose value is not NULL
+        if (in.children.size() != 1) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects one child");
+        pick_check(a, in.children[0]);
+        Val v = g.named(g.gen(in.children[0]));
+        pick_check_val(a, v);
+        const std::string key = g.key_of(in.children[0]) + "|" + fkey + (a.ignore_nulls ? "|nn" : "");
+        AggLowering::Pick p = al.get_pick(a.kind == AggKind::First, key, guarded(a.ignore_nulls ? v.ok : std::string()), v, in.children[0]);
+        pick_emit(a, v, p, true, "");
+        break;
+      }
+      case AggKind::BitAnd: case AggKind::BitOr: case AggKind::BitXor: {
+        if (in.children.size() != 1) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects one child");
+        Val v = g.named(g.gen(in.children[0]));
+        bit_agg(a, v, g.key_of(in.children[0]), fkey, guarded(v.ok), "");
+        break;
+      }
       default:
         throw CometError("Aggregate function (tag " + std::to_string(a.proto_tag) + ") is not supported by the MI355X native engine");
     }
@@ -4205,8 +4385,31 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
       src << "  static __device__ __forceinline__ void tile_grouped(const CometKParams& prm, i64 base, i64 n, const comet::GroupCtx<P>& grp, u64* kacc) {\n"
           << rowinit << g.decls << g.body() << update;
     }
+    if (!al.pick_reqs.empty()) {
+      // P::pick: per first / last, the child expression at the row whose ordinal won — if that row is one of this launch's (comet_device.hpp "first / last")
+      std::string calls;
+      for (size_t i = 0; i < al.pick_reqs.size(); i++) {
+        const auto& rq = al.pick_reqs[i];
+        Gen gp(d.in_types, in_has_validity_all);
+        if (str_fixed_len) gp.str_fixed_len = *str_fixed_len;
+        Val pv = gp.named(gp.gen(rq.child));
+        std::string lo, hi, ok = pv.ok.empty() ? std::string("1ull") : "(" + pv.ok + ") ? 1ull : 0ull";
+        AggLowering::value_words(pv, pv.v, lo, hi);
+        for (std::string* e : {&lo, &hi, &ok})
+          for (size_t p0 = e->find("[r]"); p0 != std::string::npos; p0 = e->find("[r]")) e->replace(p0, 3, "[0]");
+        src << "  static __device__ __forceinline__ void pick" << i << "(const CometKParams& prm, i64 prow, u64* acc) {\n    bool k[R] = {true}; i64 idx[R] = {prow};\n"
+            << gp.decls << gp.body() << "    acc[" << rq.p.val << "] = " << lo << ";";
+        if (!hi.empty()) src << " acc[" << rq.p.val + 1 << "] = " << hi << ";";
+        src << " acc[" << rq.p.ok << "] = " << ok << ";\n  }\n";
+        calls += "    { const i64 o_ = (i64)acc[" + std::to_string(rq.p.ord) + "]; if (o_ >= b_ && o_ - b_ < prm.n) pick" + std::to_string(i) + "(prm, o_ - b_, acc); }\n";
+        for (size_t c = 0; c < d.in_used.size() && c < gp.in_used.size(); c++) d.in_used[c] = d.in_used[c] || gp.in_used[c];
+      }
+      src << "  static __device__ __forceinline__ void pick(const CometKParams& prm, u64* acc) {\n    const i64 b_ = prm.iarg[" << kRowBaseArg << "];\n" << calls << "  }\n";
+    }
     src << "  static __device__ __forceinline__ void emit_group(const CometKParams& prm, const u64* key, const u64* acc, i64 pos) {\n"
         << key_emit << fin << "  }\n};\n";
+    if (!al.pick_reqs.empty())
+      src << "extern \"C\" __global__ __launch_bounds__(256) void k_gpick(const CometKParams prm) { comet::agg_grouped_pick_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256, COMET_WAVES_GAGG) void k_gagg(const CometKParams prm) { comet::agg_grouped_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_gemit(const CometKParams prm) { comet::agg_grouped_emit_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_grehash(const CometKParams prm) { comet::agg_grouped_rehash_body<P>(prm); }\n";
@@ -4222,6 +4425,7 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
       src << "extern \"C\" __global__ __launch_bounds__(256) void k_gpmerge(const CometKParams prm) { comet::agg_part_merge_body<P>(prm); }\n";
     }
     d.kernels = {"k_gagg", "k_gemit", "k_grehash", "k_pack"};
+    if (!al.pick_reqs.empty()) d.kernels.push_back("k_gpick");
     if (part_kernels) {
       d.kernels.push_back("k_gphist");
       d.kernels.push_back("k_gpscat");

@@ -102,6 +102,7 @@ struct PipelineDesc {
 };
 constexpr int kFixScaleArg = 6;      // scales of sums 0-3, 16 bits each
 constexpr int kFixScaleArg2 = 4;     // … of sums 4-7 (round 6: eight exact Float64 sums / averages per aggregate)
+constexpr int kRowBaseArg = 3;       // aggregate sinks: rows the task's aggregate consumed before this chunk (the ordinals of first / last count from it)
 constexpr int kFixMaxSums = 8;
 constexpr int kFixW = 158;            // must equal comet::kFixW
 constexpr int kFixDefaultScale = -94; // window [2^-94, 2^64): doubles from 2^-42 to 2^64 with every mantissa bit, without a re-run

@@ -1865,8 +1865,17 @@ CDEV void atomic_cas_combine_f64(WordPtr dst, u64 v, int op) {
   }
 }
 
+template <int SCOPE, class WordPtr>
+CDEV void atomic_xor64(WordPtr dst, u64 v) {
+#if defined(__has_builtin) && __has_builtin(__hip_atomic_fetch_xor)
+  __hip_atomic_fetch_xor(dst, v, __ATOMIC_RELAXED, SCOPE);
+#else      // a host build of this header (the tests compile the helpers and the kernel bodies with g++ and run them on one thread)
+  *dst ^= v;
+#endif
+}
+
 // accumulator word kinds of the grouped path (P::op(k))
-enum GOp : int { G_ADD64 = 0, G_ADD128 = 1, G_ADD192 = 2, G_UMAX64 = 3, G_OR64 = 4, G_FADD64 = 5, G_IMIN64 = 6, G_IMAX64 = 7, G_FMIN64 = 8, G_FMAX64 = 9, G_CONT = 10 };
+enum GOp : int { G_ADD64 = 0, G_ADD128 = 1, G_ADD192 = 2, G_UMAX64 = 3, G_OR64 = 4, G_FADD64 = 5, G_IMIN64 = 6, G_IMAX64 = 7, G_FMIN64 = 8, G_FMAX64 = 9, G_CONT = 10, G_AND64 = 11, G_XOR64 = 12 };
 
 template <class T> struct as_i64;
 template <> struct as_i64<u64*> { typedef i64* type; };
@@ -1883,6 +1892,8 @@ CDEV void slot_apply(WordPtr acc, const u64* val) {
       case G_ADD192: atomic_add_limbs<SCOPE>(acc + k, val + k, 3); break;
       case G_UMAX64: if (val[k]) __hip_atomic_fetch_max(acc + k, val[k], __ATOMIC_RELAXED, SCOPE); break;
       case G_OR64: if (val[k]) __hip_atomic_fetch_or(acc + k, val[k], __ATOMIC_RELAXED, SCOPE); break;
+      case G_AND64: if (~val[k]) __hip_atomic_fetch_and(acc + k, val[k], __ATOMIC_RELAXED, SCOPE); break;
+      case G_XOR64: if (val[k]) atomic_xor64<SCOPE>(acc + k, val[k]); break;
       case G_IMIN64: __hip_atomic_fetch_min((typename as_i64<WordPtr>::type)(acc + k), (i64)val[k], __ATOMIC_RELAXED, SCOPE); break;
       case G_IMAX64: __hip_atomic_fetch_max((typename as_i64<WordPtr>::type)(acc + k), (i64)val[k], __ATOMIC_RELAXED, SCOPE); break;
       case G_FADD64: atomic_cas_combine_f64<SCOPE>(acc + k, val[k], OP_FADD); break;
@@ -1913,6 +1924,8 @@ CDEV void slot_apply_private(u64* acc, const u64* val) {
       }
       case G_UMAX64: if (val[k] > acc[k]) acc[k] = val[k]; break;
       case G_OR64: acc[k] |= val[k]; break;
+      case G_AND64: acc[k] &= val[k]; break;
+      case G_XOR64: acc[k] ^= val[k]; break;
       case G_IMIN64: if ((i64)val[k] < (i64)acc[k]) acc[k] = val[k]; break;
       case G_IMAX64: if ((i64)val[k] > (i64)acc[k]) acc[k] = val[k]; break;
       case G_FADD64: acc[k] = (u64)__double_as_longlong(fp_add(__longlong_as_double((i64)acc[k]), __longlong_as_double((i64)val[k]))); break;
@@ -2227,6 +2240,8 @@ CDEV void lds_word_apply(COMET_LDS u64* w, int k, u64 v) {
     case G_ADD64: if (v) __hip_atomic_fetch_add(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break;
     case G_UMAX64: if (v) __hip_atomic_fetch_max(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break;
     case G_OR64: if (v) __hip_atomic_fetch_or(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break;
+    case G_AND64: if (~v) __hip_atomic_fetch_and(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break;
+    case G_XOR64: if (v) atomic_xor64<__HIP_MEMORY_SCOPE_WORKGROUP>(w, v); break;
     case G_IMIN64: __hip_atomic_fetch_min((COMET_LDS i64*)w, (i64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break;
     case G_IMAX64: __hip_atomic_fetch_max((COMET_LDS i64*)w, (i64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break;
     case G_FADD64: __hip_atomic_fetch_add((COMET_LDS double*)w, __longlong_as_double((i64)v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break;
@@ -2240,6 +2255,8 @@ CDEV u64 pword_combine(int k, u64 a, u64 b) {
     case G_ADD64: return a + b;
     case G_UMAX64: return a > b ? a : b;
     case G_OR64: return a | b;
+    case G_AND64: return a & b;
+    case G_XOR64: return a ^ b;
     case G_IMIN64: return (i64)b < (i64)a ? b : a;
     case G_IMAX64: return (i64)b > (i64)a ? b : a;
     case G_FADD64: return (u64)__double_as_longlong(fp_add(__longlong_as_double((i64)a), __longlong_as_double((i64)b)));
@@ -2554,6 +2571,28 @@ CDEV void agg_part_pass_body(const CometKParams& prm) {
   }
 }
 
+// first / last (the ordinal + pick scheme).  A group's state is the pair (ordinal of the winning row, that row's value); no memory has an atomic that wide.
+// Only the ORDINAL — rows the task consumed before this launch (iarg[3]) + the row's index in it — is accumulated, by the G_IMIN64 (first) / G_IMAX64 (last)
+// word every table of the grouped path already knows how to merge: ordinals are unique, so their minimum / maximum does not depend on which lane, block or
+// partition comes first.  The value words behind it are G_CONT — no accumulation touches them.  Once the launch's contributions are in, ONE lane per group reads
+// the winning ordinal and, if that row belongs to this launch's rows, evaluates the aggregate's child there (P::pick, generated) and writes value and validity
+// with plain stores.  One writer per group: no lock, nobody waits for anybody.  An ordinal from an earlier launch is smaller than every ordinal of this one, so
+// first keeps its older value and last replaces it.  A plan without first / last has no P::pick: no word, no launch, nothing compiled.
+template <class P, class = void> struct has_pick { static constexpr bool value = false; };
+template <class P> struct has_pick<P, decltype((void)&P::pick)> { static constexpr bool value = true; };
+
+// k_gpick, behind the k_gagg pass that survived: one lane per slot of the global table (out[0], iarg[0] slots); in[] / n / iarg[3] are the chunk's
+template <class P>
+CDEV void agg_grouped_pick_body(const CometKParams& prm) {
+  typedef Slot<P::NK, P::NW> S;
+  S* tbl = (S*)prm.out[0];
+  const i64 cap = prm.iarg[0];
+  for (i64 i = (i64)blockIdx.x * kBlock + threadIdx.x; i < cap; i += (i64)gridDim.x * kBlock) {
+    S* sl = tbl + i;
+    if (sl->state == kSlotReady) P::pick(prm, sl->acc);
+  }
+}
+
 template <class P>
 CDEV void agg_part_merge_body(const CometKParams& prm) {
   typedef Slot<P::NK, P::NW> S;
@@ -2616,6 +2655,7 @@ CDEV void agg_part_merge_body(const CometKParams& prm) {
           for (int k = 0; k < P::NK; k++) key[k] = sl->key[k];
 #pragma unroll
           for (int k = 0; k < P::NW; k++) acc[k] = sl->acc[k];
+          if constexpr (has_pick<P>::value) P::pick(prm, acc);      // (the whole input is this one chunk: every winning row is here)
           P::emit_group(prm, key, acc, (i64)s_base + woff + before[r]);
         }
     }

@@ -372,6 +372,7 @@ class ExecutionContext {
   // aggregate state
   DevBuf partials_;
   int64_t n_partials_ = 0;
+  int64_t agg_rows_seen_ = 0;         // aggregate sinks: rows of the chunks consumed so far, in pull order (kRowBaseArg: first / last order their rows by it)
   // exact Float64 sums: the fixed-point scale of every sum of the aggregate (codegen.hpp kFixDefaultScale until the data say otherwise)
   std::vector<int> fix_scales_;
   bool fix_has_state_ = false;        // an earlier chunk already contributed to the accumulators at these scales

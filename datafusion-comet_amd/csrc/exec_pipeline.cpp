@@ -23,6 +23,10 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
   err_flags_.ensure(kErrBytes);
   prm.out[kOutErr] = err_flags_.p;
   if (!has_join_) input_rows += n;
+  if (d.sink == SinkKind::AggNoGroup || d.sink == SinkKind::AggGrouped) {
+    prm.iarg[kRowBaseArg] = agg_rows_seen_;
+    agg_rows_seen_ += n;
+  }
 
   if (d.sink == SinkKind::AggNoGroup) {
     if (agg_variant_ && agg_variant_->desc.NW != d.NW) throw CometError("internal: accumulator layout differs between variants");
@@ -163,6 +167,16 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
     }
     fix_attempts_ = 0;
     fix_has_state_ = fix_has_state_ || !d.fix_sums.empty();
+    if (std::find(d.kernels.begin(), d.kernels.end(), std::string("k_gpick")) != d.kernels.end()) {
+      // first / last: the groups whose winning ordinal lies in this chunk take their value from that row (comet_device.hpp "first / last").  Behind the pass
+      // that survived — a voided pass went back to the checkpoint, and the table may have been swapped for a larger one — and on the chunk's own stream: the
+      // chunk's buffers are not reused before the work queued here is done
+      prm.out[0] = group_table_.p;
+      prm.iarg[0] = group_cap_;
+      timed_begin();
+      launch(v, "k_gpick", (int)std::min<int64_t>((group_cap_ + 255) / 256, 256 * 8), prm);
+      timed_end();
+    }
     return;
   }
 

@@ -115,7 +115,7 @@ struct Expr {
 };
 
 // AggExpr.expr_struct oneof tags (expr.proto:143-176)
-enum class AggKind : int { Count = 2, Sum = 3, Min = 4, Max = 5, Avg = 6, First = 7, Last = 8, Covariance = 12, Variance = 13, Stddev = 14, Correlation = 15,
+enum class AggKind : int { Count = 2, Sum = 3, Min = 4, Max = 5, Avg = 6, First = 7, Last = 8, BitAnd = 9, BitOr = 10, BitXor = 11, Covariance = 12, Variance = 13, Stddev = 14, Correlation = 15,
                            Unsupported = -1 };
 
 struct AggExpr {
@@ -142,6 +142,18 @@ inline const char* stat_agg_name(const AggExpr& a) {
     case AggKind::Stddev: return pop ? "stddev_pop" : "stddev_samp";
     case AggKind::Covariance: return pop ? "covar_pop" : "covar_samp";
     case AggKind::Correlation: return "corr";
+    default: return nullptr;
+  }
+}
+
+// Spark's SQL name of first / last and the bitwise aggregates; nullptr for the other kinds
+inline const char* order_bit_agg_name(AggKind k) {
+  switch (k) {
+    case AggKind::First: return "first";
+    case AggKind::Last: return "last";
+    case AggKind::BitAnd: return "bit_and";
+    case AggKind::BitOr: return "bit_or";
+    case AggKind::BitXor: return "bit_xor";
     default: return nullptr;
   }
 }

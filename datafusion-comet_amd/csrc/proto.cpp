@@ -355,7 +355,7 @@ AggExpr decode_agg_expr(Reader r) {
     if (f == 90 || wt != 2) { r.skip(wt); continue; }
     a.proto_tag = f;
     Reader b = r.sub();
-    if ((f >= 2 && f <= 8) || (f >= 12 && f <= 15)) a.kind = (AggKind)f;
+    if (f >= 2 && f <= 15) a.kind = (AggKind)f;      // (9-11: BitAndAgg / BitOrAgg / BitXorAgg{child = 1, datatype = 2}, expr.proto:222-235)
     else { a.kind = AggKind::Unsupported; continue; }
     if (f >= 12 && f <= 15) {
       // Covariance{child1 = 1, child2 = 2, null_on_divide_by_zero = 3, datatype = 4, stats_type = 5}, Variance / Stddev{child = 1,

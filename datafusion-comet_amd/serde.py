@@ -444,7 +444,7 @@ class AggExpr:
     stats_type: int = 0             # variance | stddev | covariance: SAMPLE (0) or POPULATION (1)
     null_on_divide_by_zero: bool = True      # variance | stddev | covariance | corr
 
-    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, covariance=12, variance=13, stddev=14, corr=15)
+    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, bit_and=9, bit_or=10, bit_xor=11, covariance=12, variance=13, stddev=14, corr=15)
 
     def encode(self) -> bytes:
         if self.kind == "count":
@@ -453,7 +453,7 @@ class AggExpr:
             body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.dtype.encode())
             if self.eval_mode:
                 body += _f_varint(3, self.eval_mode)
-        elif self.kind in ("min", "max"):
+        elif self.kind in ("min", "max", "bit_and", "bit_or", "bit_xor"):      # BitAndAgg / BitOrAgg / BitXorAgg{child=1, datatype=2} (expr.proto:222-235)
             body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.dtype.encode())
         elif self.kind in ("first", "last"):      # First / Last{child=1, datatype=2, ignore_nulls=3} (expr.proto:210-220)
             body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.dtype.encode()) + (_f_varint(3, 1) if self.ignore_nulls else b"")
@@ -498,12 +498,25 @@ def max_(child: Expr, dtype: DataType) -> AggExpr:
     return AggExpr("max", [child], dtype=dtype)
 
 
-def first_(child: Expr, dtype: DataType, ignore_nulls: bool = False) -> AggExpr:
-    return AggExpr("first", [child], dtype=dtype, ignore_nulls=ignore_nulls)
+def first_(child: Expr, dtype: DataType, ignore_nulls: bool = False, filter: Optional[Expr] = None) -> AggExpr:
+    return AggExpr("first", [child], dtype=dtype, ignore_nulls=ignore_nulls, filter=filter)
 
 
-def last_(child: Expr, dtype: DataType, ignore_nulls: bool = False) -> AggExpr:
-    return AggExpr("last", [child], dtype=dtype, ignore_nulls=ignore_nulls)
+def last_(child: Expr, dtype: DataType, ignore_nulls: bool = False, filter: Optional[Expr] = None) -> AggExpr:
+    return AggExpr("last", [child], dtype=dtype, ignore_nulls=ignore_nulls, filter=filter)
+
+
+def bit_and_agg(child: Expr, dtype: DataType, filter: Optional[Expr] = None) -> AggExpr:
+    """bit_and over Byte / Short / Int / Long (AggSerde.bitwiseAggTypeSupported)"""
+    return AggExpr("bit_and", [child], dtype=dtype, filter=filter)
+
+
+def bit_or_agg(child: Expr, dtype: DataType, filter: Optional[Expr] = None) -> AggExpr:
+    return AggExpr("bit_or", [child], dtype=dtype, filter=filter)
+
+
+def bit_xor_agg(child: Expr, dtype: DataType, filter: Optional[Expr] = None) -> AggExpr:
+    return AggExpr("bit_xor", [child], dtype=dtype, filter=filter)
 
 
 SAMPLE, POPULATION = 0, 1      # StatisticsType (expr.proto:178-181)

@@ -178,7 +178,10 @@ def probes():
 
 
 ACCEPTED_AGGREGATES = {"Sum": "integers, decimals, Float64 (exact, order independent)", "Average": "decimals and Float64", "Count": "", "Min": "not decimal(>18) in grouped aggregates",
-                       "Max": "not decimal(>18) in grouped aggregates", "First": "window frames only", "Last": "window frames only",
+                       "Max": "not decimal(>18) in grouped aggregates", "First": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
+                       "Last": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
+                       "BitAndAgg": "Byte / Short / Int / Long, not over window frames", "BitOrAgg": "Byte / Short / Int / Long, not over window frames",
+                       "BitXorAgg": "Byte / Short / Int / Long, not over window frames",
                        "VarianceSamp": "Float64, not over window frames (exact moments, order independent)", "VariancePop": "Float64, not over window frames (exact moments, order independent)",
                        "StddevSamp": "Float64, not over window frames (exact moments, order independent)", "StddevPop": "Float64, not over window frames (exact moments, order independent)",
                        "CovSample": "Float64, not over window frames (exact moments, order independent)", "CovPopulation": "Float64, not over window frames (exact moments, order independent)",
@@ -256,6 +259,8 @@ def render() -> str:
     w("  device-resident input ANY type mismatch with the declared Scan fields.  Time zones come from the system's database ($TZDIR, /usr/share/zoneinfo).")
     w("* `Min` / `Max` of decimal(> 18) in grouped aggregates; more than eight Float64 sums / averages in one aggregate (a variance or stddev takes two,")
     w("  a covariance three, a corr five; in a Partial aggregate functions over the same columns share theirs); statistical aggregates over window frames.")
+    w("* `First` / `Last` of Utf8, Binary and nested values in a HashAggregate (their state is fixed-width; over window frames any flat type runs); `BitAndAgg` /")
+    w("  `BitOrAgg` / `BitXorAgg` over anything but Byte / Short / Int / Long, and over window frames.")
     w("* `RLike`: patterns outside the byte-exact subset (`\\\\p{..}`, scoped flags, look-around, `\\\\b` under `(?m)`) are refused by name.")
     w("* `Concat`: of Utf8 columns and literals (at most eight), as an output column.")
     w("* Computed Utf8 values used as operands of further expressions must fit 15 bytes (literals, substring, CASE over those).")
@@ -284,6 +289,10 @@ def render() -> str:
     w("  they were rounded; variance, stddev and covariance results are within 2 ulp of exact, corr within 4 (`tests/test_stat_agg_gpu.py`).  A group with a")
     w("  NaN or ±inf input has NaN results on both sides, but its state's `mean` differs: here it is the IEEE outcome of the exact sum divided by the count,")
     w("  in the reference it depends on the row order (inf or NaN).")
+    w("* `first` / `last` in a HashAggregate: the reference marks both not deterministic (`aggregates.scala:240,275`) because its answer moves with partitioning.")
+    w("  Within one native plan the input order is defined — batches in the order `executePlan` pulls them, rows in batch order, behind the chain's Filters and the")
+    w("  aggregate's own FILTER — and this implementation is a pure function of that order: the same bits for every batch size, chunking, grid size and table path")
+    w("  (`tests/test_first_last_bit_agg_gpu.py`).  Above a join the order is the join's output order, which is unspecified on both sides.")
     w("* Join and hash-aggregate OUTPUT ORDER is unspecified in the reference (hash-table order per batch); tests compare multisets.  A sort-merge join's output is")
     w("  ordered by its keys only where that order is observable (plan output, Limit, shuffle file).")
     w("* Everything else on the path — integers, decimals (HALF_UP, overflow → NULL / ANSI error), dates, timestamps, strings, hashes (murmur3 / xxhash64), partition")
