@@ -2896,18 +2896,19 @@ struct AggLowering {
   }
   // the sum's scale and class word, for the statistical finishers
   std::string fargs(const FSum& f) const { return "acc + " + std::to_string(f.word) + ", " + fscale(f.fidx) + ", acc[" + std::to_string(f.cls) + "]"; }
-  // a sum that takes k > 1 addends per row (x² as the two doubles of two_prod, a merged state's n·mean·mean as five): the ungrouped path feeds
-  // each addend; the grouped path adds the row's addends exactly first and splits that into the four limbs, so a limb word still takes less
-  // than 2^43 per row.  Every addend feeds the exponent words, so the window covers each of them.
+  // xs: the row's addends.  One addend is the plain sum.  A sum that takes k > 1 addends per row (x² as the two doubles of two_prod, a merged state's
+  // n·mean·mean as five): the ungrouped path feeds each addend; the grouped path adds the row's addends exactly first and splits that into the four
+  // limbs, so a limb word still takes less than 2^43 per row.  Every addend feeds the exponent words, so the window covers each of them.
   FSum get_fsum(const std::string& vkey, const std::string& fkey, const std::string& cond, const std::vector<std::string>& xs) {
-    if (xs.size() == 1) return get_fsum(vkey, fkey, cond, xs[0]);
     const std::string key = "fsum|" + vkey + "|" + fkey;
     auto it = fsums.find(key);
     if (it != fsums.end()) return it->second;
     if ((int)fix_sums.size() >= kFixMaxSums) throw CometError("more than " + std::to_string(kFixMaxSums) + " distinct Float64 sums / averages in one aggregate are not supported by the GPU pipeline yet");
     const int fidx = (int)fix_sums.size();
     const int k = (int)xs.size();
+    const bool one = k == 1;
     const std::string c = cond.empty() ? "true" : cond, S = fscale(fidx), K = std::to_string(k);
+    const std::string xd = "(double)(" + xs[0] + ")";
     std::string decl = "const double ad_[" + K + "] = {";
     for (int i = 0; i < k; i++) decl += (i ? ", (double)(" : "(double)(") + xs[(size_t)i] + ")";
     decl += "};";
@@ -2928,10 +2929,16 @@ struct AggLowering {
       int j[4];
       for (int t = 0; t < 4; t++) j[t] = pword("G_ADD64", "0ull");
       const int jc = pword("G_OR64", "0ull");
-      pv_code += "        { u64 l_[4] = {0ull, 0ull, 0ull, 0ull}; u64 c_ = 0ull; if (" + c + ") { " + decl + " comet::fix_addends_limbs(ad_, " + K + ", " + S +
-                 ", l_); for (int i_ = 0; i_ < " + K + "; i_++) c_ |= comet::f64_class(ad_[i_]); }\n";
-      for (int t = 0; t < 4; t++) pv_code += "          pv[" + std::to_string(j[t]) + "] = l_[" + std::to_string(t) + "];\n";
-      pv_code += "          pv[" + std::to_string(jc) + "] = c_; }\n";
+      if (one) {
+        for (int t = 0; t < 4; t++)
+          pv_code += "        pv[" + std::to_string(j[t]) + "] = (" + c + ") ? comet::f64_fix_limb(" + xd + ", " + S + ", " + std::to_string(t) + ") : 0ull;\n";
+        pv_code += "        pv[" + std::to_string(jc) + "] = (" + c + ") ? comet::f64_class(" + xd + ") : 0ull;\n";
+      } else {
+        pv_code += "        { u64 l_[4] = {0ull, 0ull, 0ull, 0ull}; u64 c_ = 0ull; if (" + c + ") { " + decl + " comet::fix_addends_limbs(ad_, " + K + ", " + S +
+                   ", l_); for (int i_ = 0; i_ < " + K + "; i_++) c_ |= comet::f64_class(ad_[i_]); }\n";
+        for (int t = 0; t < 4; t++) pv_code += "          pv[" + std::to_string(j[t]) + "] = l_[" + std::to_string(t) + "];\n";
+        pv_code += "          pv[" + std::to_string(jc) + "] = c_; }\n";
+      }
       fold_code += "    { u64 t3_[3]; comet::limbs_to_i192(pw + " + std::to_string(j[0]) + ", 4, t3_); val[" + w + "] = t3_[0]; val[" + w1 + "] = t3_[1]; val[" + w2 +
                    "] = t3_[2]; val[" + cw + "] = pw[" + std::to_string(jc) + "]; }\n";
       fs.aux_hi = nkw++;
@@ -2939,8 +2946,9 @@ struct AggLowering {
       kops.push_back("G_UMAX64");
       kops.push_back("G_UMAX64");
       const std::string H = std::to_string(fs.aux_hi), L = std::to_string(fs.aux_lo);
-      kfeed_code += "        if (" + c + ") { " + decl + " for (int i_ = 0; i_ < " + K + "; i_++) { u64 h_ = comet::f64_exp_hi(ad_[i_]), l_ = comet::f64_exp_lo(ad_[i_]); if (h_ > kacc[" + H +
-                    "]) kacc[" + H + "] = h_; if (l_ > kacc[" + L + "]) kacc[" + L + "] = l_; } }\n";
+      const std::string track = "if (h_ > kacc[" + H + "]) kacc[" + H + "] = h_; if (l_ > kacc[" + L + "]) kacc[" + L + "] = l_;";
+      if (one) kfeed_code += "        if (" + c + ") { u64 h_ = comet::f64_exp_hi(" + xd + "), l_ = comet::f64_exp_lo(" + xd + "); " + track + " }\n";
+      else kfeed_code += "        if (" + c + ") { " + decl + " for (int i_ = 0; i_ < " + K + "; i_++) { u64 h_ = comet::f64_exp_hi(ad_[i_]), l_ = comet::f64_exp_lo(ad_[i_]); " + track + " } }\n";
     } else {
       const int hw = nw, lw = nw + 1;
       nw += 2;
@@ -2949,67 +2957,11 @@ struct AggLowering {
       combine_code += "    if (b[" + H + "] > a[" + H + "]) a[" + H + "] = b[" + H + "]; if (b[" + L + "] > a[" + L + "]) a[" + L + "] = b[" + L + "];\n";
       gops.push_back("G_UMAX64"); gops.push_back("G_UMAX64");
       gident.push_back("0ull"); gident.push_back("0ull");
-      const std::string body = "{ " + decl + " _Pragma(\"unroll\") for (int i_ = 0; i_ < " + K + "; i_++) { const double xd_ = ad_[i_]; comet::acc_feed_fix192(acc + " + w + ", xd_, " + S +
-                               "); acc[" + cw + "] |= comet::f64_class(xd_); const u64 h_ = comet::f64_exp_hi(xd_), l_ = comet::f64_exp_lo(xd_); if (h_ > acc[" + H + "]) acc[" + H +
-                               "] = h_; if (l_ > acc[" + L + "]) acc[" + L + "] = l_; } }";
-      g.stmt(cond.empty() ? body : "if (" + cond + ") " + body);
-      fs.aux_hi = 2 * fidx;
-      fs.aux_lo = 2 * fidx + 1;
-      kexport_code += "    atomicMax(aux + " + std::to_string(fs.aux_hi) + ", (unsigned long long)acc[" + H + "]); atomicMax(aux + " + std::to_string(fs.aux_lo) +
-                      ", (unsigned long long)acc[" + L + "]);\n";
-    }
-    fix_sums.push_back(fs);
-    fsums[key] = f;
-    return f;
-  }
-  FSum get_fsum(const std::string& vkey, const std::string& fkey, const std::string& cond, const std::string& x) {
-    const std::string key = "fsum|" + vkey + "|" + fkey;
-    auto it = fsums.find(key);
-    if (it != fsums.end()) return it->second;
-    if ((int)fix_sums.size() >= kFixMaxSums) throw CometError("more than " + std::to_string(kFixMaxSums) + " distinct Float64 sums / averages in one aggregate are not supported by the GPU pipeline yet");
-    const int fidx = (int)fix_sums.size();
-    const std::string c = cond.empty() ? "true" : cond;
-    const std::string xd = "(double)(" + x + ")", S = fscale(fidx);
-    FSum f;
-    f.fidx = fidx;
-    f.word = nw;
-    nw += 3;
-    f.cls = nw;
-    nw += 1;
-    const std::string w = std::to_string(f.word), w1 = std::to_string(f.word + 1), w2 = std::to_string(f.word + 2), cw = std::to_string(f.cls);
-    init_code += "    a[" + w + "] = 0; a[" + w1 + "] = 0; a[" + w2 + "] = 0; a[" + cw + "] = 0;\n";
-    combine_code += "    comet::acc_add192(a + " + w + ", b + " + w + "); comet::acc_or64(a + " + cw + ", b + " + cw + ");\n";
-    for (auto* q : {"G_ADD192", "G_CONT", "G_CONT", "G_OR64"}) gops.push_back(q);
-    for (int k = 0; k < 4; k++) gident.push_back("0ull");
-    PipelineDesc::FixSum fs;
-    fs.word = f.word;
-    if (grouped) {
-      int j0 = -1;
-      for (int t = 0; t < 4; t++) {
-        int j = pword("G_ADD64", "0ull");
-        if (t == 0) j0 = j;
-        pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? comet::f64_fix_limb(" + xd + ", " + S + ", " + std::to_string(t) + ") : 0ull;\n";
-      }
-      int jc = pword("G_OR64", "0ull");
-      pv_code += "        pv[" + std::to_string(jc) + "] = (" + c + ") ? comet::f64_class(" + xd + ") : 0ull;\n";
-      fold_code += "    { u64 t3_[3]; comet::limbs_to_i192(pw + " + std::to_string(j0) + ", 4, t3_); val[" + w + "] = t3_[0]; val[" + w1 + "] = t3_[1]; val[" + w2 +
-                   "] = t3_[2]; val[" + cw + "] = pw[" + std::to_string(jc) + "]; }\n";
-      fs.aux_hi = nkw++;
-      fs.aux_lo = nkw++;
-      kops.push_back("G_UMAX64");
-      kops.push_back("G_UMAX64");
-      kfeed_code += "        if (" + c + ") { u64 h_ = comet::f64_exp_hi(" + xd + "), l_ = comet::f64_exp_lo(" + xd + "); if (h_ > kacc[" + std::to_string(fs.aux_hi) +
-                    "]) kacc[" + std::to_string(fs.aux_hi) + "] = h_; if (l_ > kacc[" + std::to_string(fs.aux_lo) + "]) kacc[" + std::to_string(fs.aux_lo) + "] = l_; }\n";
-    } else {
-      const int hw = nw, lw = nw + 1;
-      nw += 2;
-      const std::string H = std::to_string(hw), L = std::to_string(lw);
-      init_code += "    a[" + H + "] = 0; a[" + L + "] = 0;\n";
-      combine_code += "    if (b[" + H + "] > a[" + H + "]) a[" + H + "] = b[" + H + "]; if (b[" + L + "] > a[" + L + "]) a[" + L + "] = b[" + L + "];\n";
-      gops.push_back("G_UMAX64"); gops.push_back("G_UMAX64");
-      gident.push_back("0ull"); gident.push_back("0ull");
-      const std::string body = "{ const double xd_ = " + xd + "; comet::acc_feed_fix192(acc + " + w + ", xd_, " + S + "); acc[" + cw + "] |= comet::f64_class(xd_); " +
-                               "const u64 h_ = comet::f64_exp_hi(xd_), l_ = comet::f64_exp_lo(xd_); if (h_ > acc[" + H + "]) acc[" + H + "] = h_; if (l_ > acc[" + L + "]) acc[" + L + "] = l_; }";
+      // one addend xd_: into the 192-bit sum, the class word and the exponent words
+      const std::string feed1 = "comet::acc_feed_fix192(acc + " + w + ", xd_, " + S + "); acc[" + cw + "] |= comet::f64_class(xd_); const u64 h_ = comet::f64_exp_hi(xd_), l_ = comet::f64_exp_lo(xd_); if (h_ > acc[" +
+                                H + "]) acc[" + H + "] = h_; if (l_ > acc[" + L + "]) acc[" + L + "] = l_;";
+      const std::string body = one ? "{ const double xd_ = " + xd + "; " + feed1 + " }"
+                                   : "{ " + decl + " _Pragma(\"unroll\") for (int i_ = 0; i_ < " + K + "; i_++) { const double xd_ = ad_[i_]; " + feed1 + " } }";
       g.stmt(cond.empty() ? body : "if (" + cond + ") " + body);
       fs.aux_hi = 2 * fidx;
       fs.aux_lo = 2 * fidx + 1;
@@ -3129,15 +3081,32 @@ struct AggLowering {
     PrimSlot s{p, nw, prim_words(p)};
     nw += s.nwords;
     slots[key] = s;
-    const std::string w = std::to_string(s.word), w1 = std::to_string(s.word + 1), w2 = std::to_string(s.word + 2);
-    auto ops = [&](std::initializer_list<const char*> o, std::initializer_list<const char*> id) {
-      for (auto* q : o) gops.push_back(q);
-      for (auto* q : id) gident.push_back(q);
+    const std::string w = std::to_string(s.word), w1 = std::to_string(s.word + 1), ACC = "acc[" + w + "]";
+    auto acc_call = [&](const std::string& fn) { return "comet::acc_" + fn + "(a + " + w + ", b + " + w + ");"; };
+    // a one-word primitive: `init` and `id` spell its identity in P::init and in P::identity, `combine` merges two accumulators, `gop` is its op in the
+    // global table.  Ungrouped, a row runs `row`.  Grouped, a row's contribution `pv` (`pid` where it has none) goes into a private word under `pop`
+    // and is folded back as `pre pw[j] post`.
+    auto word1 = [&](const char* init, const char* id, const std::string& combine, const char* gop, const std::string& row, const char* pop = nullptr, const char* pid = nullptr,
+                     const std::string& pv = "", const char* pre = "", const char* post = "") {
+      init_code += "    a[" + w + "] = " + init + ";\n";
+      combine_code += "    " + combine + "\n";
+      gops.push_back(gop);
+      gident.push_back(id);
+      if (!grouped) return feed(row);
+      const std::string j = std::to_string(pword(pop, pid));
+      pv_code += "        pv[" + j + "] = (" + c + ") ? " + pv + " : " + pid + ";\n";
+      fold_code += "    val[" + w + "] = " + pre + "pw[" + j + "]" + post + ";\n";
     };
-    // grouped integer sum: split into limbs, fold back into `nlimb_words` canonical words
-    auto grouped_int_sum = [&](const std::string& x128, u128 bound, int canon_words) {
-      int bits = (bound == kUnbounded ? 127 : bit_length_u128(bound)) + 1;
-      int nl = (bits + kLimbBitsHost - 1) / kLimbBitsHost;
+    // an integer sum of s.nwords words.  Grouped: split into limbs, folded back into the canonical words
+    auto int_sum = [&](const std::string& x128, u128 bound, const std::string& row) {
+      const std::string bits = std::to_string(64 * s.nwords);
+      init_code += "   ";
+      for (int k = 0; k < s.nwords; k++) init_code += " a[" + std::to_string(s.word + k) + "] = 0;";
+      init_code += "\n";
+      combine_code += "    " + acc_call("add" + bits) + "\n";
+      for (int k = 0; k < s.nwords; k++) { gops.push_back(k ? "G_CONT" : "G_ADD" + bits); gident.push_back("0ull"); }
+      if (!grouped) return feed(row);
+      int nl = ((bound == kUnbounded ? 127 : bit_length_u128(bound)) + 1 + kLimbBitsHost - 1) / kLimbBitsHost;
       if (nl < 1) nl = 1;
       int j0 = -1;
       for (int t = 0; t < nl; t++) {
@@ -3146,114 +3115,66 @@ struct AggLowering {
         pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? comet::limb_of(" + x128 + ", " + std::to_string(t) + ", " + std::to_string(nl) + ") : 0ull;\n";
       }
       fold_code += "    { u64 t3_[3]; comet::limbs_to_i192(pw + " + std::to_string(j0) + ", " + std::to_string(nl) + ", t3_);";
-      for (int k = 0; k < canon_words; k++) fold_code += " val[" + std::to_string(s.word + k) + "] = t3_[" + std::to_string(k) + "];";
+      for (int k = 0; k < s.nwords; k++) fold_code += " val[" + std::to_string(s.word + k) + "] = t3_[" + std::to_string(k) + "];";
       fold_code += " }\n";
     };
+    const bool mn = p == Prim::MinI64 || p == Prim::MinF64 || p == Prim::MinI128;
+    const char* imin = "0x7fffffffffffffffull";
+    const char* imax = "0x8000000000000000ull";
     switch (p) {
       case Prim::Cnt: case Prim::RowCnt:
-        init_code += "    a[" + w + "] = 0;\n";
-        combine_code += "    comet::acc_add64(a + " + w + ", b + " + w + ");\n";
-        ops({"G_ADD64"}, {"0ull"});
-        if (grouped) {
-          int j = pword("G_ADD64", "0ull");
-          pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? 1ull : 0ull;\n";
-          fold_code += "    val[" + w + "] = pw[" + std::to_string(j) + "];\n";
-        } else feed("acc[" + w + "] += 1;");
+        word1("0", "0ull", acc_call("add64"), "G_ADD64", ACC + " += 1;", "G_ADD64", "0ull", "1ull");
         break;
-      case Prim::SumI64:
-        init_code += "    a[" + w + "] = 0;\n";
-        combine_code += "    comet::acc_add64(a + " + w + ", b + " + w + ");\n";
-        ops({"G_ADD64"}, {"0ull"});
-        if (grouped) grouped_int_sum("(i128)(i64)(" + x + ")", maxabs == kUnbounded ? ((u128)1 << 63) : maxabs, 1);  // wraps mod 2^64 like add_wrapping
-        else feed("acc[" + w + "] += (u64)(i64)(" + x + ");");
+      case Prim::SumI64:  // wraps mod 2^64 like add_wrapping
+        int_sum("(i128)(i64)(" + x + ")", maxabs == kUnbounded ? ((u128)1 << 63) : maxabs, ACC + " += (u64)(i64)(" + x + ");");
         break;
       case Prim::SumF64:
-        init_code += "    a[" + w + "] = 0;\n";
-        combine_code += "    comet::acc_fadd64(a + " + w + ", b + " + w + ");\n";
-        ops({"G_FADD64"}, {"0ull"});
-        if (grouped) {
-          int j = pword("G_FADD64", "0ull");
-          pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? (u64)__double_as_longlong((double)(" + x + ")) : 0ull;\n";
-          fold_code += "    val[" + w + "] = pw[" + std::to_string(j) + "];\n";
-        } else feed("acc[" + w + "] = (u64)__double_as_longlong(comet::fp_add(__longlong_as_double((i64)acc[" + w + "]), (double)(" + x + ")));");
+        word1("0", "0ull", acc_call("fadd64"), "G_FADD64", ACC + " = (u64)__double_as_longlong(comet::fp_add(__longlong_as_double((i64)" + ACC + "), (double)(" + x + ")));",
+              "G_FADD64", "0ull", "(u64)__double_as_longlong((double)(" + x + "))");
         break;
       case Prim::Sum128:
-        init_code += "    a[" + w + "] = 0; a[" + w1 + "] = 0;\n";
-        combine_code += "    comet::acc_add128(a + " + w + ", b + " + w + ");\n";
-        ops({"G_ADD128", "G_CONT"}, {"0ull", "0ull"});
-        if (grouped) grouped_int_sum(x, maxabs, 2);
-        else feed("comet::acc_feed_i128(acc + " + w + ", " + x + ");");
+        int_sum(x, maxabs, "comet::acc_feed_i128(acc + " + w + ", " + x + ");");
         break;
       case Prim::Sum192:
-        init_code += "    a[" + w + "] = 0; a[" + w1 + "] = 0; a[" + w2 + "] = 0;\n";
-        combine_code += "    comet::acc_add192(a + " + w + ", b + " + w + ");\n";
-        ops({"G_ADD192", "G_CONT", "G_CONT"}, {"0ull", "0ull", "0ull"});
-        if (grouped) grouped_int_sum(x, maxabs, 3);
-        else feed("comet::acc_feed_i192(acc + " + w + ", " + x + ");");
+        int_sum(x, maxabs, "comet::acc_feed_i192(acc + " + w + ", " + x + ");");
         break;
       case Prim::AMaxHi:
         // amax_enc(|v|) (0 = no value yet): a monotone one-word upper bound of max|v|
-        init_code += "    a[" + w + "] = 0;\n";
-        combine_code += "    if (b[" + w + "] > a[" + w + "]) a[" + w + "] = b[" + w + "];\n";
-        ops({"G_UMAX64"}, {"0ull"});
-        feed("{ u64 t_ = comet::amax_enc(comet::uabs128(" + x + ")); if (t_ > acc[" + w + "]) acc[" + w + "] = t_; }");
+        word1("0", "0ull", "if (b[" + w + "] > a[" + w + "]) a[" + w + "] = b[" + w + "];", "G_UMAX64",
+              "{ u64 t_ = comet::amax_enc(comet::uabs128(" + x + ")); if (t_ > " + ACC + ") " + ACC + " = t_; }");
         break;
       case Prim::SignFlags:
-        init_code += "    a[" + w + "] = 0;\n";
-        combine_code += "    comet::acc_or64(a + " + w + ", b + " + w + ");\n";
-        ops({"G_OR64"}, {"0ull"});
-        feed("acc[" + w + "] |= ((" + x + ") < 0) ? 2ull : (((" + x + ") > 0) ? 1ull : 0ull);");
+        word1("0", "0ull", acc_call("or64"), "G_OR64", ACC + " |= ((" + x + ") < 0) ? 2ull : (((" + x + ") > 0) ? 1ull : 0ull);");
         break;
       case Prim::MinI64: case Prim::MaxI64: {
-        const bool mn = p == Prim::MinI64;
-        const char* id = mn ? "0x7fffffffffffffffull" : "0x8000000000000000ull";
-        init_code += "    a[" + w + "] = " + id + ";\n";
-        combine_code += std::string("    comet::acc_") + (mn ? "imin64" : "imax64") + "(a + " + w + ", b + " + w + ");\n";
-        ops({mn ? "G_IMIN64" : "G_IMAX64"}, {id});
-        if (grouped) {
-          int j = pword(mn ? "G_IMIN64" : "G_IMAX64", id);
-          pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? (u64)(i64)(" + x + ") : " + id + ";\n";
-          fold_code += "    val[" + w + "] = pw[" + std::to_string(j) + "];\n";
-        } else feed(std::string("{ u64 t_ = (u64)(i64)(") + x + "); comet::acc_" + (mn ? "imin64" : "imax64") + "(acc + " + w + ", &t_); }");
+        const std::string fn = mn ? "imin64" : "imax64";
+        const char* gop = mn ? "G_IMIN64" : "G_IMAX64";
+        word1(mn ? imin : imax, mn ? imin : imax, acc_call(fn), gop, "{ u64 t_ = (u64)(i64)(" + x + "); comet::acc_" + fn + "(acc + " + w + ", &t_); }", gop, mn ? imin : imax, "(u64)(i64)(" + x + ")");
         break;
       }
       case Prim::MinF64: case Prim::MaxF64: {
-        const bool mn = p == Prim::MinF64;
-        const char* id = mn ? "0x7fffffffffffffffull" : "0xffffffffffffffffull";  // extremes of the IEEE total order (as bits)
-        init_code += "    a[" + w + "] = " + id + ";\n";
-        combine_code += std::string("    comet::acc_") + (mn ? "fmin64" : "fmax64") + "(a + " + w + ", b + " + w + ");\n";
-        ops({mn ? "G_FMIN64" : "G_FMAX64"}, {id});
-        if (grouped) {
-          // in LDS: integer min/max on the total-order key (an involution of the bit pattern)
-          const char* kid = mn ? "0x7fffffffffffffffull" : "0x8000000000000000ull";
-          int j = pword(mn ? "G_IMIN64" : "G_IMAX64", kid);
-          pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? (u64)comet::f64_total_key((double)(" + x + ")) : " + kid + ";\n";
-          fold_code += "    val[" + w + "] = (u64)comet::f64_total_key(__longlong_as_double((i64)pw[" + std::to_string(j) + "]));\n";
-        } else feed(std::string("{ u64 t_ = (u64)__double_as_longlong((double)(") + x + ")); comet::acc_" + (mn ? "fmin64" : "fmax64") + "(acc + " + w + ", &t_); }");
+        // the identities are the extremes of the IEEE total order (as bits); in LDS: integer min/max on the total-order key (an involution of the bit pattern)
+        const std::string fn = mn ? "fmin64" : "fmax64";
+        word1(mn ? imin : "0xffffffffffffffffull", mn ? imin : "0xffffffffffffffffull", acc_call(fn), mn ? "G_FMIN64" : "G_FMAX64",
+              "{ u64 t_ = (u64)__double_as_longlong((double)(" + x + ")); comet::acc_" + fn + "(acc + " + w + ", &t_); }", mn ? "G_IMIN64" : "G_IMAX64", mn ? imin : imax,
+              "(u64)comet::f64_total_key((double)(" + x + "))", "(u64)comet::f64_total_key(__longlong_as_double((i64)", "))");
         break;
       }
       case Prim::BitAnd: case Prim::BitOr: case Prim::BitXor: {
         // the integer sign-extended into the word; and / or / xor commute with that, the result is truncated on the way out
         const char* gop = p == Prim::BitAnd ? "G_AND64" : p == Prim::BitOr ? "G_OR64" : "G_XOR64";
-        const char* cop = p == Prim::BitAnd ? "&=" : p == Prim::BitOr ? "|=" : "^=";
+        const std::string cop = p == Prim::BitAnd ? "&=" : p == Prim::BitOr ? "|=" : "^=";
         const char* id = p == Prim::BitAnd ? "0xffffffffffffffffull" : "0ull";
-        init_code += "    a[" + w + "] = " + id + ";\n";
-        combine_code += "    a[" + w + "] " + cop + " b[" + w + "];\n";
-        ops({gop}, {id});
-        if (grouped) {
-          int j = pword(gop, id);
-          pv_code += "        pv[" + std::to_string(j) + "] = (" + c + ") ? (u64)(i64)(" + x + ") : " + id + ";\n";
-          fold_code += "    val[" + w + "] = pw[" + std::to_string(j) + "];\n";
-        } else feed("acc[" + w + "] " + cop + " (u64)(i64)(" + x + ");");
+        word1(id, id, "a[" + w + "] " + cop + " b[" + w + "];", gop, ACC + " " + cop + " (u64)(i64)(" + x + ");", gop, id, "(u64)(i64)(" + x + ")");
         break;
       }
       case Prim::MinI128: case Prim::MaxI128: {
-        const bool mn = p == Prim::MinI128;
         if (grouped) throw CometError("min/max of a decimal wider than 18 digits is not supported in a grouped GPU aggregate yet");
+        const std::string fn = mn ? "imin128" : "imax128";
         init_code += mn ? "    a[" + w + "] = ~0ull; a[" + w1 + "] = 0x7fffffffffffffffull;\n" : "    a[" + w + "] = 0; a[" + w1 + "] = 0x8000000000000000ull;\n";
-        combine_code += std::string("    comet::acc_") + (mn ? "imin128" : "imax128") + "(a + " + w + ", b + " + w + ");\n";
-        ops({"G_CONT", "G_CONT"}, {"0ull", "0ull"});
-        feed("{ u64 t_[2] = {comet::lo64(" + x + "), comet::hi64(" + x + ")}; comet::acc_" + std::string(mn ? "imin128" : "imax128") + "(acc + " + w + ", t_); }");
+        combine_code += "    " + acc_call(fn) + "\n";
+        for (int k = 0; k < 2; k++) { gops.push_back("G_CONT"); gident.push_back("0ull"); }
+        feed("{ u64 t_[2] = {comet::lo64(" + x + "), comet::hi64(" + x + ")}; comet::acc_" + fn + "(acc + " + w + ", t_); }");
         break;
       }
     }
@@ -3270,14 +3191,26 @@ std::string explain_expr(const ExprP& e) {
   return s + ")";
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------
+// generate_pipeline's steps: collect the chain, fold it leaf → root, append the derived columns, then the Output sink or the aggregate sink
+// ---------------------------------------------------------------------------------------------
+struct SourceColsScope { SourceColsScope(const std::vector<ExprP>* c) { g_source_cols = c; } ~SourceColsScope() { g_source_cols = nullptr; } };
+struct DerivedScope { DerivedScope(std::vector<DerivedCol>* c) { g_derived = c; } ~DerivedScope() { g_derived = nullptr; } };
 
-// ---------------------------------------------------------------------------------------------
-// generate_pipeline
-// ---------------------------------------------------------------------------------------------
-PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in_has_validity, const std::vector<DType>* source_types,
-                               const std::vector<int>* str_fixed_len, const std::vector<int>* dict_id_col) {
-  // 1. walk root → leaf collecting the chain; the chain ends at a Scan or at a materialised source (a join's output)
+// a generator over the pipeline's columns
+struct GenMaker {
+  const std::vector<DType>& types;
+  const std::vector<bool>& valid;
+  const std::vector<int>* str_fixed_len;
+  Gen operator()() const {
+    Gen x(types, valid);
+    if (str_fixed_len) x.str_fixed_len = *str_fixed_len;
+    return x;
+  }
+};
+
+// walk root → leaf collecting the chain; the chain ends at a Scan or at a materialised source (a join's output)
+std::vector<const Operator*> collect_chain(const Operator& root, bool has_source_types) {
   std::vector<const Operator*> chain;
   const Operator* cur = &root;
   while (true) {
@@ -3287,7 +3220,7 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
     // across a pipeline breaker: its result is materialised in HBM and read like a scan)
     if (cur->kind == OpKind::Explode || cur->kind == OpKind::HashJoin || cur->kind == OpKind::NativeScan || cur->kind == OpKind::Sort || cur->kind == OpKind::Limit || cur->kind == OpKind::Expand || cur->kind == OpKind::Window ||
         (cur->kind == OpKind::HashAgg && cur != &root)) {
-      if (!source_types) throw CometError("internal: materialised source without a schema");
+      if (!has_source_types) throw CometError("internal: materialised source without a schema");
       break;
     }
     if (cur->kind == OpKind::Unsupported)
@@ -3297,89 +3230,106 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
     if (cur->children.size() != 1) throw CometError(std::string(op_name(cur->proto_tag)) + " expects exactly one child");
     cur = cur->children[0].get();
   }
-  const Operator& scan = *chain.back();
-  PipelineDesc d;
-  SiteScope site_scope(d);
-  d.in_types = source_types ? *source_types : scan.scan_fields;
-  for (auto* op : chain) d.op_names.push_back(op_name(op->proto_tag));
-  if (in_has_validity.size() != d.in_types.size()) throw CometError("internal: validity mask arity mismatch");
-  if (d.in_types.size() > COMET_MAX_IN) throw CometError("too many scan columns for one GPU pipeline");
+  return chain;
+}
 
-  // 2. fold leaf → root
+std::vector<ExprP> bound_columns(const std::vector<DType>& types) {
   std::vector<ExprP> cols;
-  for (size_t i = 0; i < d.in_types.size(); i++) {
+  for (size_t i = 0; i < types.size(); i++) {
     auto b = std::make_shared<Expr>();
     b->kind = ExprKind::Bound;
     b->proto_tag = 3;
     b->bound_index = (int)i;
-    b->dtype = d.in_types[i];
+    b->dtype = types[i];
     b->has_dtype = true;
     cols.push_back(b);
   }
-  const std::vector<ExprP> source_cols = cols;
-  struct SourceColsScope { SourceColsScope(const std::vector<ExprP>* c) { g_source_cols = c; } ~SourceColsScope() { g_source_cols = nullptr; } } source_cols_scope(&source_cols);
-  struct DerivedScope { DerivedScope(std::vector<DerivedCol>* c) { g_derived = c; } ~DerivedScope() { g_derived = nullptr; } } derived_scope(&d.derived);
-  std::vector<ExprP> preds;
+  return cols;
+}
+
+// the number of Partial state columns of an aggregate: what Final / PartialMerge read, in order
+int state_arity(const AggExpr& a) {
+  switch (a.kind) {
+    case AggKind::Avg: return 2;
+    case AggKind::Sum: return a.dtype.id == TypeId::Decimal ? 2 : 1;
+    case AggKind::Variance: case AggKind::Stddev: return 3;     // (count, mean, m2)
+    case AggKind::Covariance: return 4;                         // (count, mean1, mean2, algo_const)
+    case AggKind::Correlation: return 6;                        // … + (m2_1, m2_2)
+    case AggKind::First: case AggKind::Last: return 2;          // (value, is_set)
+    default: return 1;                                          // the bitwise aggregates: one column
+  }
+}
+
+struct AggIn { const AggExpr* a; std::vector<ExprP> children; ExprP filter; AggMode mode = AggMode::Partial; };
+
+// what the chain folds to: the columns that leave it, the Filters' conjuncts and, under a HashAggregate, its keys and its aggregates' inputs
+struct FoldedChain {
+  std::vector<ExprP> cols, preds, group_exprs;
   const Operator* agg = nullptr;
-  std::vector<ExprP> group_exprs;
-  struct AggIn { const AggExpr* a; std::vector<ExprP> children; ExprP filter; AggMode mode = AggMode::Partial; };
   std::vector<AggIn> agg_ins;
+};
+
+// a HashAggregate's keys and the inputs of its aggregates over the columns below it
+void fold_aggregate(const Operator& op, FoldedChain& f, std::map<const Expr*, ExprP>& memo, PipelineDesc& d) {
+  f.agg = &op;
+  for (auto& e : op.grouping_exprs) f.group_exprs.push_back(substitute(e, f.cols, memo));
+  // per-expression modes (HashAggregate.expr_modes, planner.rs:1274-1345): a Partial-mode operator may carry PartialMerge
+  // expressions — the count(DISTINCT) rewrite merges the other aggregates' states while it starts counting — whose state
+  // columns sit in the child's output from initial_input_buffer_offset on
+  if (!op.expr_modes.empty() && op.expr_modes.size() != op.agg_exprs.size())
+    throw CometError("HashAggregate: expr_modes has " + std::to_string(op.expr_modes.size()) + " entries for " + std::to_string(op.agg_exprs.size()) + " aggregates");
+  const size_t state_base = op.expr_modes.empty() ? op.grouping_exprs.size() : (size_t)std::max(0, op.initial_input_buffer_offset);
   size_t final_state_pos = 0;
+  for (size_t ai = 0; ai < op.agg_exprs.size(); ai++) {
+    const AggExpr& a = op.agg_exprs[ai];
+    AggIn in;
+    in.a = &a;
+    in.mode = op.expr_modes.empty() ? op.agg_mode : (AggMode)op.expr_modes[ai];
+    if (ai == 0) d.merges_states = in.mode != AggMode::Partial;
+    else d.merges_states = d.merges_states && in.mode != AggMode::Partial;
+    if (in.mode == AggMode::Partial) {
+      for (auto& c : a.children) in.children.push_back(substitute(c, f.cols, memo));
+      if (a.filter) in.filter = substitute(a.filter, f.cols, memo);
+    } else if (in.mode == AggMode::Final || in.mode == AggMode::PartialMerge) {
+      // Final / PartialMerge: the aggregate's inputs are the Partial state columns that follow the group columns, in order
+      // (AggregateExec Final mode; the serialized children are unbound, operators.scala:1786-1792)
+      for (int k = 0; k < state_arity(a); k++) {
+        size_t idx = state_base + final_state_pos++;
+        if (idx >= f.cols.size()) throw CometError("Final aggregate: state column " + std::to_string(idx) + " is out of bound");
+        in.children.push_back(f.cols[idx]);
+      }
+    } else {
+      throw CometError("Unsupported aggregate mode: " + std::to_string((int)in.mode));
+    }
+    f.agg_ins.push_back(in);
+  }
+}
+
+// fold leaf → root: Projections substitute into the columns, Filters add conjuncts, a HashAggregate ends the chain
+FoldedChain fold_pipeline(const std::vector<const Operator*>& chain, const std::vector<ExprP>& source_cols, PipelineDesc& d) {
+  FoldedChain f;
+  f.cols = source_cols;
   for (int i = (int)chain.size() - 2; i >= 0; i--) {
     const Operator& op = *chain[i];
     std::map<const Expr*, ExprP> memo;
-    if (agg) throw CometError("Operators above a HashAggregate in the same native plan are not supported yet");
+    if (f.agg) throw CometError("Operators above a HashAggregate in the same native plan are not supported yet");
     if (op.kind == OpKind::Filter) {
       if (!op.predicate) throw CometError("Filter without predicate");
-      split_conjuncts(substitute(op.predicate, cols, memo), preds);
+      split_conjuncts(substitute(op.predicate, f.cols, memo), f.preds);
       d.has_filter = true;
     } else if (op.kind == OpKind::Projection) {
       std::vector<ExprP> nc;
-      for (auto& e : op.project_list) nc.push_back(substitute(e, cols, memo));
-      cols = nc;
+      for (auto& e : op.project_list) nc.push_back(substitute(e, f.cols, memo));
+      f.cols = nc;
     } else if (op.kind == OpKind::HashAgg) {
-      agg = &op;
-      for (auto& e : op.grouping_exprs) group_exprs.push_back(substitute(e, cols, memo));
-      // per-expression modes (HashAggregate.expr_modes, planner.rs:1274-1345): a Partial-mode operator may carry PartialMerge
-      // expressions — the count(DISTINCT) rewrite merges the other aggregates' states while it starts counting — whose state
-      // columns sit in the child's output from initial_input_buffer_offset on
-      if (!op.expr_modes.empty() && op.expr_modes.size() != op.agg_exprs.size())
-        throw CometError("HashAggregate: expr_modes has " + std::to_string(op.expr_modes.size()) + " entries for " + std::to_string(op.agg_exprs.size()) + " aggregates");
-      const size_t state_base = op.expr_modes.empty() ? op.grouping_exprs.size() : (size_t)std::max(0, op.initial_input_buffer_offset);
-      for (size_t ai = 0; ai < op.agg_exprs.size(); ai++) {
-        const AggExpr& a = op.agg_exprs[ai];
-        AggIn in;
-        in.a = &a;
-        in.mode = op.expr_modes.empty() ? op.agg_mode : (AggMode)op.expr_modes[ai];
-        if (ai == 0) d.merges_states = in.mode != AggMode::Partial;
-        else d.merges_states = d.merges_states && in.mode != AggMode::Partial;
-        if (in.mode == AggMode::Partial) {
-          for (auto& c : a.children) in.children.push_back(substitute(c, cols, memo));
-          if (a.filter) in.filter = substitute(a.filter, cols, memo);
-        } else if (in.mode == AggMode::Final || in.mode == AggMode::PartialMerge) {
-          // Final / PartialMerge: the aggregate's inputs are the Partial state columns that follow the group columns, in order
-          // (AggregateExec Final mode; the serialized children are unbound, operators.scala:1786-1792)
-          int arity = 1;
-          if (a.kind == AggKind::Avg) arity = 2;
-          if (a.kind == AggKind::Sum && a.dtype.id == TypeId::Decimal) arity = 2;
-          if (a.kind == AggKind::Variance || a.kind == AggKind::Stddev) arity = 3;     // (count, mean, m2)
-          if (a.kind == AggKind::Covariance) arity = 4;                                // (count, mean1, mean2, algo_const)
-          if (a.kind == AggKind::Correlation) arity = 6;                               // … + (m2_1, m2_2)
-          if (a.kind == AggKind::First || a.kind == AggKind::Last) arity = 2;          // (value, is_set); the bitwise aggregates: one column
-          for (int k = 0; k < arity; k++) {
-            size_t idx = state_base + final_state_pos++;
-            if (idx >= cols.size()) throw CometError("Final aggregate: state column " + std::to_string(idx) + " is out of bound");
-            in.children.push_back(cols[idx]);
-          }
-        } else {
-          throw CometError("Unsupported aggregate mode: " + std::to_string((int)in.mode));
-        }
-        agg_ins.push_back(in);
-      }
+      fold_aggregate(op, f, memo, d);
     }
   }
+  return f;
+}
 
-  // the derived columns follow the source's: a split is NULL where its subject is
+// the derived columns follow the source's: a split is NULL where its subject is.  Returns the validity of every column
+std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool>& in_has_validity, bool under_agg) {
   std::vector<bool> valid_all = in_has_validity;
   for (auto& dc : d.derived) {
     d.in_types.push_back(dc.type);
@@ -3391,179 +3341,151 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
     d.in_types.push_back(et);
     valid_all.push_back(false);
   }
-  if (!d.derived.empty() && agg) throw CometError("split inside an aggregate's chain is not supported by the MI355X native engine yet");
+  if (!d.derived.empty() && under_agg) throw CometError("split inside an aggregate's chain is not supported by the MI355X native engine yet");
   if (d.in_types.size() > COMET_MAX_IN) throw CometError("too many scan columns for one GPU pipeline");
-  const std::vector<bool>& in_has_validity_all = valid_all;
-  Gen g(d.in_types, in_has_validity_all);
-  if (str_fixed_len) g.str_fixed_len = *str_fixed_len;
-  if (const char* e = getenv("COMET_GEN_EAGER")) g.eager_loads = atoi(e) != 0;
-  g.pipelined = agg != nullptr;   // aggregate sinks prefetch tile t+1's first-stage columns while computing tile t
-  if (const char* e = getenv("COMET_GEN_PIPELINE")) g.pipelined = g.pipelined && atoi(e) != 0;
-  for (auto& p : preds) g.add_predicate(p);
+  return valid_all;
+}
 
-  std::ostringstream src;
-  src << "// generated by datafusion-comet_amd codegen — fused pipeline: ";
-  for (auto& n : d.op_names) src << n << " <- ";
-  src << "input\n";
-  if (const char* e = getenv("COMET_EXPERIMENT")) src << "#define COMET_EXPERIMENT " << atoi(e) << "\n";
-  // An aggregate sink reads every column byte once and keeps nothing but its accumulators: its column loads are non-temporal (streaming)
-  // loads — SF100 Q1's k_gagg 7.24-7.58 -> 7.01-7.13 ms in three alternating pairs on one box.  Join probes keep ordinary loads (their
-  // bitmap and build rows want the L2; both of SF100 Q3's got ~3 % slower with streaming loads).
-  if (agg) src << "#ifndef COMET_LD_NT\n#define COMET_LD_NT 1\n#endif\n";
-  src << "#include \"comet_device.hpp\"\nusing namespace comet;\n";
+const char* const kRowInit = "    bool k[R]; i64 idx[R];\n    _Pragma(\"unroll\") for (int r = 0; r < R; r++) { idx[r] = base + (i64)r * comet::kBlock + threadIdx.x; k[r] = idx[r] < n; }\n";
+const char* const kPackKernel = "extern \"C\" __global__ __launch_bounds__(256) void k_pack(const CometKParams prm) { comet::pack_validity_body((const u8*)prm.out[0], (u8*)prm.out[1], prm.n); }\n";
 
-  std::ostringstream ex;
-  for (auto& p : preds) ex << "  filter: " << explain_expr(p) << "\n";
+std::string out_val(size_t j) { return "prm.out[" + std::to_string(kOutFirstCol + 2 * j) + "]"; }
+std::string out_ok(size_t j) { return "prm.out[" + std::to_string(kOutFirstCol + 2 * j + 1) + "]"; }
 
-  if (!agg) {
-    // ---------------- Output sink ----------------
-    d.sink = SinkKind::Output;
-    std::vector<Val> outs;
-    // outputs are evaluated in the emit kernel (per surviving row); predicates in the mask kernel.
-    Gen ge(d.in_types, in_has_validity_all);
-    if (str_fixed_len) ge.str_fixed_len = *str_fixed_len;
-    for (auto& c : cols) {
-      // (… and so is a nested column: its rows are gathered by the executor, children and all — exec.cpp take_nested)
-      const bool is_str_type = c->kind == ExprKind::Bound && c->bound_index >= 0 && (size_t)c->bound_index < d.in_types.size() &&
-                               (d.in_types[(size_t)c->bound_index].id == TypeId::String || d.in_types[(size_t)c->bound_index].id == TypeId::Bytes ||
-                                d.in_types[(size_t)c->bound_index].is_nested());
-      if (c->kind == ExprKind::ListExtract && !c->children.empty() && c->children[0]->kind == ExprKind::Bound && c->children[0]->bound_index >= 0 &&
-          (size_t)c->children[0]->bound_index < d.in_types.size() && d.in_types[(size_t)c->children[0]->bound_index].id == TypeId::List &&
-          !d.in_types[(size_t)c->children[0]->bound_index].kids.empty() && d.in_types[(size_t)c->children[0]->bound_index].kids[0].id == TypeId::String) {
-        // an element of a list of strings (split(s, ',')[0], element_at(arr, -1)): the ELEMENT column's row travels, the executor gathers the string
-        Gen::ListRef l;
-        std::string row, hit;
-        ge.list_extract_pos(*c, l, row, hit);
-        Val v;
-        v.t = DType::of(TypeId::String);
-        v.rep = Rep::I64;
-        v.v = row;
-        v.ok = in_has_validity_all[(size_t)l.elem] ? "(" + hit + " && comet::ld_valid(" + l.ecol + ", " + row + "))" : hit;
-        v = ge.named(v);
-        outs.push_back(v);
-        OutCol oc;
-        oc.type = v.t;
-        oc.nullable = true;
-        oc.gather_src = l.elem;
-        d.out_cols.push_back(oc);
-        ex << "  output: " << explain_expr(c) << " : Utf8 (an element gathered from column " << l.elem << ")\n";
-        continue;
-      }
-      if (is_str_type) {
-        // a Utf8 column passed through: emit the source row index, the executor gathers the string afterwards
-        const int src = c->bound_index;
-        ge.in_used[(size_t)src] = true;
-        Val v;
-        v.t = d.in_types[(size_t)src];
-        v.rep = Rep::I64;
-        v.v = "idx[r]";
-        if (in_has_validity_all[(size_t)src]) v.ok = "comet::ld_valid(prm.in[" + std::to_string(ge.locate(src).first) + "], idx[r])";
-        v = ge.named(v);
-        outs.push_back(v);
-        OutCol oc;
-        oc.type = v.t;
-        oc.type.virt_parent = oc.type.virt_kid = -1;
-        oc.nullable = !v.ok.empty();
-        oc.gather_src = src;
-        d.out_cols.push_back(oc);
-        ex << "  output: " << explain_expr(c) << " : " << v.t.str() << " (gathered)\n";
-        continue;
-      }
-      {
-        // a string function of a Utf8 COLUMN with literal arguments whose result is a slice of the value plus padding: any length
-        OutCol voc;
-        Val vv;
-        if (ge.string_view(*c, vv, voc)) {
-          outs.push_back(vv);
-          voc.type = vv.t;
-          voc.nullable = !vv.ok.empty();
-          d.out_cols.push_back(voc);
-          ex << "  output: " << explain_expr(c) << " : " << vv.t.str() << " (string view of column " << voc.view_src << ")\n";
-          continue;
-        }
-      }
-      {
-        // concat of Utf8 columns and literals: the source row travels, the executor assembles the column
-        OutCol coc;
-        Val cvl;
-        if (ge.string_concat(*c, cvl, coc)) {
-          outs.push_back(cvl);
-          coc.type = DType::of(TypeId::String);
-          coc.nullable = !cvl.ok.empty();
-          d.out_cols.push_back(coc);
-          ex << "  output: " << explain_expr(c) << " : string (concatenation of " << coc.concat_cols.size() << " parts)\n";
-          continue;
-        }
-      }
-      {
-        // Cast(<integer | boolean | decimal | date | timestamp> AS STRING): the value travels, the executor writes the digits
-        OutCol foc;
-        Val fv;
-        if (ge.string_format(*c, fv, foc)) {
-          outs.push_back(fv);
-          foc.type = DType::of(TypeId::String);
-          foc.nullable = !fv.ok.empty();
-          d.out_cols.push_back(foc);
-          ex << "  output: " << explain_expr(c) << " : string (formatted value)\n";
-          continue;
-        }
-      }
-      Val v = ge.named(ge.gen(c));
-      outs.push_back(v);
+// ---------------- Output sink ----------------
+// outputs are evaluated in the emit kernel (per surviving row); predicates in the mask kernel.
+struct OutputSink {
+  PipelineDesc& d;
+  Gen& ge;
+  const std::vector<bool>& valid;
+  std::ostringstream& ex;
+  std::vector<Val> outs;
+
+  void add(const ExprP& c, const Val& v, const OutCol& oc, const std::string& what) {
+    outs.push_back(v);
+    d.out_cols.push_back(oc);
+    ex << "  output: " << explain_expr(c) << " : " << what << "\n";
+  }
+
+  bool is_source(const ExprP& c, size_t& idx) const {
+    idx = (size_t)c->bound_index;
+    return c->kind == ExprKind::Bound && c->bound_index >= 0 && idx < d.in_types.size();
+  }
+
+  void column(const ExprP& c) {
+    size_t src = 0, lsrc = 0;
+    if (c->kind == ExprKind::ListExtract && !c->children.empty() && is_source(c->children[0], lsrc) && d.in_types[lsrc].id == TypeId::List &&
+        !d.in_types[lsrc].kids.empty() && d.in_types[lsrc].kids[0].id == TypeId::String) {
+      // an element of a list of strings (split(s, ',')[0], element_at(arr, -1)): the ELEMENT column's row travels, the executor gathers the string
+      Gen::ListRef l;
+      std::string row, hit;
+      ge.list_extract_pos(*c, l, row, hit);
+      Val v;
+      v.t = DType::of(TypeId::String);
+      v.rep = Rep::I64;
+      v.v = row;
+      v.ok = valid[(size_t)l.elem] ? "(" + hit + " && comet::ld_valid(" + l.ecol + ", " + row + "))" : hit;
+      v = ge.named(v);
       OutCol oc;
       oc.type = v.t;
-      oc.nullable = !v.ok.empty();
-      // a computed string (literal, substring, CASE over those — at most 15 bytes): stored packed, expanded to offsets + bytes by the executor
-      oc.packed_string = v.rep == Rep::STR;
-      d.out_cols.push_back(oc);
-      ex << "  output: " << explain_expr(c) << " : " << v.t.str() << "\n";
+      oc.nullable = true;
+      oc.gather_src = l.elem;
+      return add(c, v, oc, "Utf8 (an element gathered from column " + std::to_string(l.elem) + ")");
     }
-    if (d.out_cols.size() * 2 + kOutFirstCol > COMET_MAX_OUT) throw CometError("too many output columns for one GPU pipeline");
-    for (size_t j = 0; j < outs.size(); j++) {
-      const Val& v = outs[j];
-      std::string vb = "prm.out[" + std::to_string(kOutFirstCol + 2 * j) + "]";
-      std::string ob = "prm.out[" + std::to_string(kOutFirstCol + 2 * j + 1) + "]";
-      if (d.out_cols[j].fmt_kind) {
-        ge.stmt("((i128*)" + vb + ")[pos[r]] = (i128)" + v.v + ";");
-        if (!v.ok.empty()) ge.stmt("((u8*)" + ob + ")[pos[r]] = " + v.ok + " ? 1 : 0;");
-        continue;
+    // (… and so is a nested column: its rows are gathered by the executor, children and all — exec.cpp take_nested)
+    if (is_source(c, src) && (d.in_types[src].id == TypeId::String || d.in_types[src].id == TypeId::Bytes || d.in_types[src].is_nested())) {
+      // a Utf8 column passed through: emit the source row index, the executor gathers the string afterwards
+      ge.in_used[src] = true;
+      Val v;
+      v.t = d.in_types[src];
+      v.rep = Rep::I64;
+      v.v = "idx[r]";
+      if (valid[src]) v.ok = "comet::ld_valid(prm.in[" + std::to_string(ge.locate((int)src).first) + "], idx[r])";
+      v = ge.named(v);
+      OutCol oc;
+      oc.type = v.t;
+      oc.type.virt_parent = oc.type.virt_kid = -1;
+      oc.nullable = !v.ok.empty();
+      oc.gather_src = (int)src;
+      return add(c, v, oc, v.t.str() + " (gathered)");
+    }
+    {
+      // a string function of a Utf8 COLUMN with literal arguments whose result is a slice of the value plus padding: any length
+      OutCol voc;
+      Val vv;
+      if (ge.string_view(*c, vv, voc)) {
+        voc.type = vv.t;
+        voc.nullable = !vv.ok.empty();
+        return add(c, vv, voc, vv.t.str() + " (string view of column " + std::to_string(voc.view_src) + ")");
       }
-      if (d.out_cols[j].view_src >= 0) {
-        ge.stmt("((comet::strview*)" + vb + ")[pos[r]] = " + v.v + ";");
-        if (!v.ok.empty()) ge.stmt("((u8*)" + ob + ")[pos[r]] = " + v.ok + " ? 1 : 0;");
-        continue;
+    }
+    {
+      // concat of Utf8 columns and literals: the source row travels, the executor assembles the column
+      OutCol coc;
+      Val cvl;
+      if (ge.string_concat(*c, cvl, coc)) {
+        coc.type = DType::of(TypeId::String);
+        coc.nullable = !cvl.ok.empty();
+        return add(c, cvl, coc, "string (concatenation of " + std::to_string(coc.concat_cols.size()) + " parts)");
       }
-      if (d.out_cols[j].gather_src >= 0 || !d.out_cols[j].concat_cols.empty()) {
-        ge.stmt("((u32*)" + vb + ")[pos[r]] = (u32)" + v.v + ";");
-        if (!v.ok.empty()) ge.stmt("((u8*)" + ob + ")[pos[r]] = " + v.ok + " ? 1 : 0;");
-        continue;
+    }
+    {
+      // Cast(<integer | boolean | decimal | date | timestamp> AS STRING): the value travels, the executor writes the digits
+      OutCol foc;
+      Val fv;
+      if (ge.string_format(*c, fv, foc)) {
+        foc.type = DType::of(TypeId::String);
+        foc.nullable = !fv.ok.empty();
+        return add(c, fv, foc, "string (formatted value)");
       }
-      if (d.out_cols[j].packed_string) {
-        ge.stmt("((comet::str16*)" + vb + ")[pos[r]] = " + (v.ok.empty() ? v.v : "(" + v.ok + " ? " + v.v + " : comet::str16{0ull, 0ull})") + ";");
-        if (!v.ok.empty()) ge.stmt("((u8*)" + ob + ")[pos[r]] = " + v.ok + " ? 1 : 0;");
-        continue;
-      }
+    }
+    Val v = ge.named(ge.gen(c));
+    OutCol oc;
+    oc.type = v.t;
+    oc.nullable = !v.ok.empty();
+    // a computed string (literal, substring, CASE over those — at most 15 bytes): stored packed, expanded to offsets + bytes by the executor
+    oc.packed_string = v.rep == Rep::STR;
+    add(c, v, oc, v.t.str());
+  }
+
+  // column j's value into its slot at pos[r], then its validity byte
+  void store(size_t j) {
+    const Val& v = outs[j];
+    const OutCol& oc = d.out_cols[j];
+    const std::string vb = out_val(j);
+    auto at = [&](const std::string& ctype) { return "((" + ctype + "*)" + vb + ")[pos[r]] = "; };
+    if (oc.fmt_kind) {
+      ge.stmt(at("i128") + "(i128)" + v.v + ";");
+    } else if (oc.view_src >= 0) {
+      ge.stmt(at("comet::strview") + v.v + ";");
+    } else if (oc.gather_src >= 0 || !oc.concat_cols.empty()) {
+      ge.stmt(at("u32") + "(u32)" + v.v + ";");
+    } else if (oc.packed_string) {
+      ge.stmt(at("comet::str16") + (v.ok.empty() ? v.v : "(" + v.ok + " ? " + v.v + " : comet::str16{0ull, 0ull})") + ";");
+    } else {
       const char* st = store_ctype(v.t);
       std::string val = v.v;
       if (v.t.id == TypeId::Decimal) val = v.rep == Rep::I128 ? v.v : "(i128)" + v.v;
       else if (v.t.id == TypeId::Bool) val = "(u8)(" + v.v + " ? 1 : 0)";
       else val = std::string("(") + st + ")" + v.v;
       // NULL slots are written as zero like arrow builders do (deterministic bytes)
-      if (!v.ok.empty()) {
-        ge.stmt("((" + std::string(st) + "*)" + vb + ")[pos[r]] = " + v.ok + " ? " + val + " : (" + st + ")0;");
-        ge.stmt("((u8*)" + ob + ")[pos[r]] = " + v.ok + " ? 1 : 0;");
-      } else {
-        ge.stmt("((" + std::string(st) + "*)" + vb + ")[pos[r]] = " + val + ";");
-      }
+      ge.stmt(at(st) + (v.ok.empty() ? val : v.ok + " ? " + val + " : (" + st + ")0") + ";");
     }
+    if (!v.ok.empty()) ge.stmt("((u8*)" + out_ok(j) + ")[pos[r]] = " + v.ok + " ? 1 : 0;");
+  }
+
+  // g: the predicates' generator
+  void finish(std::ostringstream& src, const Gen& g, const std::vector<ExprP>& cols) {
+    d.sink = SinkKind::Output;
+    for (auto& c : cols) column(c);
+    if (d.out_cols.size() * 2 + kOutFirstCol > COMET_MAX_OUT) throw CometError("too many output columns for one GPU pipeline");
+    for (size_t j = 0; j < outs.size(); j++) store(j);
     for (size_t i = 0; i < d.in_types.size(); i++) d.in_used.push_back(g.in_used[i] || ge.in_used[i]);
     if (d.has_filter) {
       // tile-wise functors for the single-pass filter kernel: R row slots per thread; every stage first issues the loads of all R
       // rows, then computes / stores, so a thread keeps R × (columns) loads in flight instead of one row's
-      int fr = 8;
-      if (const char* e = getenv("COMET_EXPERIMENT")) fr = std::max(1, std::min(16, atoi(e)));
-      d.R = fr;
-      src << "struct P {\n  static constexpr int R = " << fr << ";\n";
+      d.R = 8;
+      src << "struct P {\n  static constexpr int R = " << d.R << ";\n";
       src << "  static __device__ __forceinline__ void keep_tile(const CometKParams& prm, i64 base, i64 n, bool* k) {\n"
           << "    i64 idx[R];\n    _Pragma(\"unroll\") for (int r = 0; r < R; r++) { idx[r] = base + (i64)r * comet::kBlock + threadIdx.x; k[r] = idx[r] < n; }\n"
           << g.decls << g.body() << "  }\n";
@@ -3580,46 +3502,78 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
       src << "extern \"C\" __global__ __launch_bounds__(256) void k_emit(const CometKParams prm) { comet::project_body<P>(prm); }\n";
       d.kernels = {"k_emit"};
     }
-    src << "extern \"C\" __global__ __launch_bounds__(256) void k_pack(const CometKParams prm) { comet::pack_validity_body((const u8*)prm.out[0], (u8*)prm.out[1], prm.n); }\n";
+    src << kPackKernel;
     d.kernels.push_back("k_pack");
-    d.source = with_optional_headers(src.str());
-    d.explain = ex.str();
-    return d;
   }
+};
 
-  // ---------------- Aggregate sinks ----------------
-  // Final and PartialMerge both MERGE Partial states (merge_batch); Final then evaluates, PartialMerge re-emits the state
-  const bool grouped = !group_exprs.empty();
-  d.sink = grouped ? SinkKind::AggGrouped : SinkKind::AggNoGroup;
-  // the context an ANSI decimal sum (0) / average (1) raises its DecimalSumOverflow with (PipelineDesc::agg_ctx)
-  auto note_agg_ctx = [&](int kind, const AggExpr& a) {
-    std::shared_ptr<QueryContext> c = (a.qctx && a.has_expr_id) ? a.qctx : nullptr;
-    static const std::shared_ptr<QueryContext> none;
-    if (d.agg_ctx_mixed[kind]) return;
-    if (!d.agg_ctx[kind] && !d.agg_ctx_seen[kind]) { d.agg_ctx[kind] = c; d.agg_ctx_seen[kind] = true; return; }
-    const QueryContext* x = d.agg_ctx[kind].get();
-    const bool same = (!x && !c) || (x && c && x->sql_text == c->sql_text && x->start_index == c->start_index && x->stop_index == c->stop_index);
-    if (!same) { d.agg_ctx_mixed[kind] = true; d.agg_ctx[kind] = nullptr; }
-  };
-  AggLowering al(g, grouped);
-  std::string fin;  // finalize body; ROW is "[0]" (ungrouped) or "[pos]" (grouped emit)
-  const std::string ROW = grouped ? "[pos]" : "[0]";
-  int out_j = 0;
-  auto out_val = [&](int j) { return "prm.out[" + std::to_string(kOutFirstCol + 2 * j) + "]"; };
-  auto out_ok = [&](int j) { return "prm.out[" + std::to_string(kOutFirstCol + 2 * j + 1) + "]"; };
-
-  // ---- group keys → packed key words (word 0 = NULL bitmask of the keys)
+// ---------------- Aggregate sinks ----------------
+// Final and PartialMerge both MERGE Partial states (merge_batch); Final then evaluates, PartialMerge re-emits the state
+struct AggSink {
+  PipelineDesc& d;
+  Gen& g;
+  const bool grouped;
+  AggLowering al;
+  std::ostringstream& ex;
+  std::string fin;          // finalize body
+  const std::string ROW;    // the output row: "[0]" (ungrouped) or "[pos]" (grouped emit)
+  int out_j = 0;            // the next output column's slot
+  // group keys → packed key words (word 0 = NULL bitmask of the keys)
   std::string key_code, key_emit;
   std::vector<ExprP> synthetic_exprs;
   int nk = 0;
-  if (grouped) {
+  PrimSlot rowcnt;          // rows that reach the aggregate
+  long long max_rows_exact = 0;
+
+  AggSink(PipelineDesc& desc, Gen& gen, bool grp, std::ostringstream& explain) : d(desc), g(gen), grouped(grp), al(gen, grp), ex(explain), ROW(grp ? "[pos]" : "[0]") {
+    d.sink = grouped ? SinkKind::AggGrouped : SinkKind::AggNoGroup;
+  }
+
+  // one aggregate of the operator: its inputs (children: the values in Partial mode, the Partial state columns in a merging mode) and its FILTER
+  struct Call {
+    const AggExpr& a;
+    const std::vector<ExprP>& children;
+    bool merging;        // Final / PartialMerge: merge Partial states
+    bool as_state;       // Partial / PartialMerge: the output is the state; Final: the result
+    std::string fkey, guard;
+    const char* label() const { return !merging ? "" : as_state ? "(partial-merge)" : "(final)"; }
+    // count, integer sum, float sum and min / max put the same columns out in both merging modes and name both "(final)"
+    const char* merge_label() const { return merging ? "(final)" : ""; }
+    std::string guarded(const std::string& ok) const { return Gen::and_ok(guard, ok); }
+    // what makes two inputs the same primitive's: the child's key, apart for values and for merged states
+    std::string vkey(Gen& g, size_t i = 0) const { return (merging ? "fin:" : "") + g.key_of(children[i]); }
+  };
+
+  // ---- output columns: slot j's value is prm.out[kOutFirstCol + 2j], its validity bytes the slot behind it ----
+  int add_out(const OutCol& oc) {
+    d.out_cols.push_back(oc);
+    return out_j++;
+  }
+  int add_out(const DType& t, bool nullable) {
+    OutCol oc;
+    oc.type = t;
+    oc.nullable = nullable;
+    return add_out(oc);
+  }
+  void put(int j, const std::string& ctype, const std::string& expr, const char* indent = "    ") {
+    fin += indent + ("((" + ctype + "*)" + out_val((size_t)j) + ")" + ROW + " = " + expr + ";\n");
+  }
+  void put_ok(int j, const std::string& expr, const char* indent = "    ", const char* tail = "") {
+    fin += indent + ("((u8*)" + out_ok((size_t)j) + ")" + ROW + " = " + expr + ";" + tail + "\n");
+  }
+  void explain(const char* label, const std::string& what) { ex << "  agg" << label << ": " << what << "\n"; }
+  static std::string acc(const PrimSlot& s) { return "acc[" + std::to_string(s.word) + "]"; }
+  static std::string okx(const Val& v) { return v.ok.empty() ? std::string("true") : v.ok; }
+
+  // ---- group keys ----
+  void lower_group_keys(const std::vector<ExprP>& group_exprs, const std::vector<int>* dict_id_col) {
     nk = 1;
     key_code += "        key[0] = 0;\n";
     int kj = 0;
     for (auto& ge : group_exprs) {
       OutCol oc;
       std::string ok_expr;
-      const std::string vb = out_val(out_j), ob = out_ok(out_j);
+      const std::string vb = out_val((size_t)out_j), ob = out_ok((size_t)out_j);
       const std::string nullbit = std::to_string(1ull << kj) + "ull";
       const bool direct_str = ge->kind == ExprKind::Bound && ge->bound_index >= 0 && (size_t)ge->bound_index < d.in_types.size() &&
                               (d.in_types[(size_t)ge->bound_index].id == TypeId::String || d.in_types[(size_t)ge->bound_index].id == TypeId::Bytes);
@@ -3664,6 +3618,7 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
           const char* st = store_ctype(v.t);
           const std::string k0 = std::to_string(nk);
           std::string enc, dec;
+          // (not AggLowering::value_words / value_read: those parenthesise the value and read acc[], the text here does neither)
           switch (v.rep) {
             case Rep::B: enc = "(u64)(" + v.v + " ? 1 : 0)"; dec = "(u8)key[" + k0 + "]"; break;
             case Rep::I32: case Rep::I64: enc = "(u64)(i64)" + v.v; dec = std::string("(") + st + ")(i64)key[" + k0 + "]"; break;
@@ -3682,25 +3637,330 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
       if (!ok_expr.empty()) key_code += "        if (!(" + ok_expr + ")) key[0] |= " + nullbit + ";\n";
       key_emit += "    ((u8*)" + ob + ")[pos] = (key[0] & " + nullbit + ") ? 0 : 1;\n";
       oc.nullable = true;
-      d.out_cols.push_back(oc);
+      add_out(oc);
       ex << "  group key: " << explain_expr(ge) << " : " << oc.type.str() << "\n";
-      out_j++;
       kj++;
       if (kj > 60) throw CometError("too many group keys");
     }
   }
 
+  // ---- count ----
+  void count(const Call& c) {
+    PrimSlot s;
+    if (c.merging) {
+      // count state: Int64, summed (DataFusion count_udaf merge)
+      Val v = g.named(g.gen(c.children.at(0)));
+      if (!v.t.is_integer()) throw CometError("Final count expects an Int64 state column");
+      s = al.get(Prim::SumI64, c.vkey(g), "", v.ok, v.v, (u128)1 << 63);
+    } else {
+      if (c.children.empty()) throw CometError("count() without children");
+      std::string ok, vkey;
+      for (auto& ch : c.children) {
+        Val v = g.gen(ch);
+        ok = Gen::and_ok(ok, v.ok);
+        vkey += g.key_of(ch) + ",";
+      }
+      s = al.get(Prim::Cnt, vkey, c.fkey, c.guarded(ok), "");
+    }
+    put(add_out(DType::of(TypeId::Int64), false), "i64", "(i64)" + acc(s));
+    explain(c.merge_label(), "count -> Int64");
+  }
+
+  // ---- sum / avg: over Decimal, the integer sum, everything else as Float64 ----
+  void sum_avg(const Call& c) {
+    if (!c.merging && c.children.size() != 1) throw CometError("sum/avg expects one child");
+    if (c.a.dtype.id == TypeId::Decimal) return c.merging ? decimal_merge(c) : decimal_update(c);
+    if (c.a.kind == AggKind::Sum && c.a.dtype.is_integer()) return int_sum(c);
+    float_sum_avg(c);
+  }
+
+  // the context an ANSI decimal sum (0) / average (1) raises its DecimalSumOverflow with (PipelineDesc::agg_ctx)
+  void note_agg_ctx(int kind, const AggExpr& a) {
+    std::shared_ptr<QueryContext> c = (a.qctx && a.has_expr_id) ? a.qctx : nullptr;
+    if (d.agg_ctx_mixed[kind]) return;
+    if (!d.agg_ctx[kind] && !d.agg_ctx_seen[kind]) { d.agg_ctx[kind] = c; d.agg_ctx_seen[kind] = true; return; }
+    const QueryContext* x = d.agg_ctx[kind].get();
+    const bool same = (!x && !c) || (x && c && x->sql_text == c->sql_text && x->start_index == c->start_index && x->stop_index == c->stop_index);
+    if (!same) { d.agg_ctx_mixed[kind] = true; d.agg_ctx[kind] = nullptr; }
+  }
+  // where an overflow-tracking word lives: in the kernel-level words behind the error word (grouped) or among the accumulators
+  static std::string kw(const PrimSlot& ps) {
+    return ps.kernel_level ? "((const u64*)prm.out[" + std::to_string(kOutErr) + "])[2 + " + std::to_string(ps.word) + "]" : acc(ps);
+  }
+  static std::string err_word() { return "(unsigned int*)prm.out[" + std::to_string(kOutErr) + "]"; }
+  // opens the block a decimal sum is finished in: its low 128 bits and — dynamic: where no static bound rules an overflow out — the decision from the 192-bit
+  // sum, the bound words (amax, sflags) and the number of addends n
+  void open_total(const PrimSlot& sum, bool dynamic, const PrimSlot& amax, const PrimSlot& sflags, const PrimSlot& n, u128 bound) {
+    const std::string W = std::to_string(sum.word), W1 = std::to_string(sum.word + 1);
+    fin += "    {\n      i128 total = comet::mk128(acc[" + W1 + "], acc[" + W + "]);\n      bool ovf = false;\n";
+    if (!dynamic) return;
+    fin += "      comet::sum_overflow_decide(acc + " + W + ", " + kw(amax) + ", " + kw(sflags) + ", " + acc(n) + ", " + lit_u128(bound) + ", ovf, " + err_word() + ");\n";
+    g.uses_err = true;
+  }
+  // the two state columns of a decimal sum / average: (sum: the sum type, nullable; is_empty: Boolean | count: Int64, nullable)
+  void decimal_state_cols(const DType& st, bool is_avg, int& j0, int& j1) {
+    j0 = add_out(st, true);
+    j1 = is_avg ? add_out(DType::of(TypeId::Int64), true) : add_out(DType::of(TypeId::Bool), false);
+  }
+  static constexpr const char* IN2 = "      ";
+
+  void decimal_update(const Call& c) {
+    const AggExpr& a = c.a;
+    const bool is_avg = a.kind == AggKind::Avg;
+    Val v = g.named(g.gen(c.children[0]));
+    const std::string vkey = c.vkey(g), cond = c.guarded(v.ok);
+    if (v.t.id != TypeId::Decimal) throw CometError("decimal sum/avg over non-decimal input " + v.t.str());
+    const DType st = is_avg ? a.sum_dtype : a.dtype;   // accumulation type
+    if (st.id != TypeId::Decimal) throw CometError("Invalid data type for SumDecimal");
+    if (st.scale != v.t.scale) throw CometError("decimal sum/avg: input scale differs from sum scale");
+    const u128 bound = pow10_u128(st.precision) - 1;
+    // Appendix C.1: no prefix can overflow while rows × max|v| ≤ 10^p − 1
+    u128 vmax = v.maxabs == 0 ? 1 : v.maxabs;
+    u128 safe_rows = vmax == kUnbounded ? 0 : bound / vmax;
+    const bool dynamic = safe_rows < ((u128)1 << 33);  // Spark sizes sum types for 10^10 rows (p+10)
+    if (!dynamic) {
+      long long sr = safe_rows > (u128)0x7fffffffffffffffll ? 0x7fffffffffffffffll : (long long)safe_rows;
+      if (max_rows_exact == 0 || sr < max_rows_exact) max_rows_exact = sr;
+    }
+    std::string val128 = v.rep == Rep::I128 ? v.v : "(i128)" + v.v;
+    PrimSlot cnt = al.get(Prim::Cnt, vkey, c.fkey, cond, "");
+    PrimSlot sum, amax{}, sflags{};
+    if (!dynamic) {
+      sum = al.get(Prim::Sum128, vkey, c.fkey, cond, val128, v.maxabs);
+    } else {
+      sum = al.get(Prim::Sum192, vkey, c.fkey, cond, val128, v.maxabs);
+      amax = al.get(Prim::AMaxHi, vkey, c.fkey, cond, val128);
+      sflags = al.get(Prim::SignFlags, vkey, c.fkey, cond, val128);
+    }
+    const std::string C = acc(cnt);
+    open_total(sum, dynamic, amax, sflags, cnt, bound);
+    // ANSI: an overflowing decimal SUM fails the query instead of turning NULL (sum_decimal.rs:211-215, 427-431).  An average only notes the
+    // overflow in its state here (avg_decimal.rs:268-300, 483-503) and raises when the states are merged or evaluated (:366-380, 576-580, 610-616)
+    if (dynamic && a.eval_mode == EvalMode::Ansi && !is_avg) {
+      note_agg_ctx(0, a);
+      fin += "      if (ovf) atomicOr(" + err_word() + ", 65536u);\n";
+    }
+    int j0, j1;
+    decimal_state_cols(st, is_avg, j0, j1);
+    if (!is_avg) {
+      // SumDecimal state (sum_decimal.rs:281-295, :526-538): (sum | NULL if overflowed, is_empty)
+      fin += "      bool empty = " + C + " == 0;\n";
+      put(j0, "i128", "ovf ? (i128)0 : total", IN2);
+      put_ok(j0, "ovf ? 0 : 1", IN2);
+      put(j1, "u8", "empty ? 1 : 0", IN2);
+      explain("", "sum_decimal -> (" + st.str() + ", is_empty)");
+    } else {
+      if (grouped) {
+        // AvgDecimalGroupsAccumulator::state (avg_decimal.rs:638-653): sum and count share the is_not_null mask
+        put(j0, "i128", "ovf ? (i128)0 : total", IN2);
+        put_ok(j0, "ovf ? 0 : 1", IN2);
+        put(j1, "i64", "ovf ? 0 : (i64)" + C, IN2);
+        put_ok(j1, "ovf ? 0 : 1", IN2);
+      } else {
+        // AvgDecimalAccumulator::state (avg_decimal.rs:283-288): sum = None until the first value
+        fin += "      bool none = " + C + " == 0 || ovf;\n";
+        put(j0, "i128", "none ? (i128)0 : total", IN2);
+        put_ok(j0, "none ? 0 : 1", IN2);
+        put(j1, "i64", "(i64)" + C, IN2);
+        put_ok(j1, "1", IN2);
+      }
+      explain("", "avg_decimal -> (" + st.str() + ", count)");
+    }
+    fin += "    }\n";
+  }
+
+  void decimal_merge(const Call& c) {
+    const AggExpr& a = c.a;
+    const bool is_avg = a.kind == AggKind::Avg;
+    Val sv = g.named(g.gen(c.children.at(0)));
+    Val s2 = g.named(g.gen(c.children.at(1)));
+    const DType st = is_avg ? a.sum_dtype : a.dtype;
+    if (!(sv.t == st)) throw CometError("Final decimal aggregate: state type " + sv.t.str() + " differs from " + st.str());
+    const u128 bound = pow10_u128(st.precision) - 1;
+    const std::string vk = c.vkey(g), fits = "comet::dec_fits(total, " + lit_u128(bound) + ")";
+    std::string val128 = sv.rep == Rep::I128 ? sv.v : "(i128)" + sv.v;
+    int j0, j1;
+    if (!is_avg) {
+      // SumDecimal merge_batch (sum_decimal.rs:309-368 / :540-609): state = (sum nullable, is_empty)
+      if (s2.rep != Rep::B) throw CometError("Final SumDecimal expects (sum, is_empty) state columns");
+      const std::string empty = "(" + s2.v + ")";                       // is_empty is non-null
+      const std::string that_ovf = "(!" + empty + " && !" + okx(sv) + ")";  // overflowed partial: sticky
+      const std::string contrib = "(!" + empty + " && " + okx(sv) + ")";
+      PrimSlot cnt = al.get(Prim::Cnt, vk, "ne", contrib, "");
+      PrimSlot any_ovf = al.get(Prim::Cnt, vk, "ovf", that_ovf, "");
+      PrimSlot sum = al.get(Prim::Sum192, vk, "", contrib, val128, bound);
+      PrimSlot amax = al.get(Prim::AMaxHi, vk, "", contrib, val128);
+      PrimSlot sflags = al.get(Prim::SignFlags, vk, "", contrib, val128);
+      const std::string C = acc(cnt), OVF = acc(any_ovf);
+      open_total(sum, true, amax, sflags, cnt, bound);
+      // ANSI: merging into an overflow fails the query (sum_decimal.rs:352-358, 594-600)
+      if (a.eval_mode == EvalMode::Ansi) {
+        note_agg_ctx(0, a);
+        fin += "      if (" + OVF + " != 0 || ovf || (" + C + " != 0 && !" + fits + ")) atomicOr(" + err_word() + ", 65536u);\n";
+      }
+      if (c.as_state) {
+        // merged state (sum_decimal.rs:281-295 after :309-368): sum is NULL once any side overflowed, is_empty only
+        // if every merged state was empty
+        fin += "      bool sovf = " + OVF + " != 0 || ovf || !" + fits + ";\n";
+        fin += "      bool empty = " + C + " == 0 && " + OVF + " == 0;\n";
+        decimal_state_cols(st, false, j0, j1);
+        put(j0, "i128", "sovf ? (i128)0 : total", IN2);
+        put_ok(j0, "sovf ? 0 : 1", IN2);
+        put(j1, "u8", "empty ? 1 : 0", IN2);
+        explain(c.label(), "sum_decimal -> (" + st.str() + ", is_empty)");
+      } else {
+        // evaluate (sum_decimal.rs:264-279): NULL if empty, overflowed, or out of precision
+        fin += "      bool isnull = " + C + " == 0 || " + OVF + " != 0 || ovf || !" + fits + ";\n";
+        j0 = add_out(st, true);
+        put(j0, "i128", "isnull ? (i128)0 : total", IN2);
+        put_ok(j0, "isnull ? 0 : 1", IN2);
+        explain(c.label(), "sum_decimal -> " + st.str());
+      }
+    } else {
+      // AvgDecimal merge (avg_decimal.rs:542-595) + evaluate (:597-636, avg() :670-689): state = (sum nullable, count)
+      if (!s2.t.is_integer()) throw CometError("Final AvgDecimal expects (sum, count) state columns");
+      PrimSlot cnt = al.get(Prim::SumI64, vk + "#cnt", "", s2.ok, s2.v, (u128)1 << 63);
+      PrimSlot bad = al.get(Prim::Cnt, vk, "nullstate", "(!" + okx(sv) + " || !" + okx(s2) + ")", "");
+      PrimSlot nsum = al.get(Prim::Cnt, vk, "nsum", sv.ok, "");
+      PrimSlot sum = al.get(Prim::Sum192, vk, "", sv.ok, val128, bound);
+      PrimSlot amax = al.get(Prim::AMaxHi, vk, "", sv.ok, val128);
+      PrimSlot sflags = al.get(Prim::SignFlags, vk, "", sv.ok, val128);
+      const u128 tbound = pow10_u128(a.dtype.precision) - 1;
+      const int up = std::max(0, a.dtype.scale - st.scale);
+      open_total(sum, true, amax, sflags, nsum, bound);
+      fin += "      i64 count = (i64)" + acc(cnt) + ";\n";
+      // grouped (AvgDecimalGroupsAccumulator::merge_batch, avg_decimal.rs:542-595): a NULL partial sum / count or an
+      // overflowing merge step clears is_not_null for good.  Ungrouped (AvgDecimalAccumulator::merge_batch, :331-356):
+      // arrow's sum() skips NULL partial sums and only the batch total is checked against the precision.
+      if (grouped) fin += "      bool sum_ok = " + acc(bad) + " == 0 && !ovf;\n";
+      else fin += "      bool sum_ok = " + acc(nsum) + " != 0 && " + fits + ";\n";
+      // ANSI: an overflowed sum under a count fails the query (avg_decimal.rs:366-380, 576-580, 610-616)
+      if (a.eval_mode == EvalMode::Ansi) {
+        note_agg_ctx(1, a);
+        fin += "      if (!sum_ok && count > 0) atomicOr(" + err_word() + ", 131072u);\n";
+      }
+      if (c.as_state) {
+        // state: grouped sums and counts share the is_not_null mask (:638-653); ungrouped (sum Option, count) (:301-306)
+        decimal_state_cols(st, true, j0, j1);
+        put(j0, "i128", "sum_ok ? total : (i128)0", IN2);
+        put_ok(j0, "sum_ok ? 1 : 0", IN2);
+        put(j1, "i64", grouped ? "sum_ok ? count : 0" : "count", IN2);
+        put_ok(j1, grouped ? "sum_ok ? 1 : 0" : "1", IN2);
+        explain(c.label(), "avg_decimal -> (" + st.str() + ", count)");
+      } else {
+        fin += "      i128 avgv = 0;\n";
+        fin += "      bool has = sum_ok && count != 0 && comet::dec_avg(total, count, " +
+               lit_i128((i128)pow10_u128(up)) + ", " + lit_u128(tbound) + ", avgv);\n";
+        j0 = add_out(a.dtype, true);
+        put(j0, "i128", "has ? avgv : (i128)0", IN2);
+        put_ok(j0, "has ? 1 : 0", IN2);
+        explain(c.label(), "avg_decimal -> " + a.dtype.str());
+      }
+    }
+    fin += "    }\n";
+  }
+
+  void int_sum(const Call& c) {
+    Val v = g.named(g.gen(c.children.at(0)));
+    if (!c.merging) {
+      // SumInteger LEGACY (sum_int.rs:117-160, :403-475): wrapping i64, NULL until a non-null value arrives
+      if (!v.t.is_integer()) throw CometError("integer sum over " + v.t.str());
+      if (c.a.eval_mode != EvalMode::Legacy) throw CometError("ANSI/TRY integer sum is not supported in the GPU pipeline yet");
+    }
+    // … and its merge (sum_int.rs:494-530): wrapping sum of the non-null partial sums, NULL if none
+    const std::string vkey = c.vkey(g), cond = c.guarded(v.ok);
+    PrimSlot cnt = al.get(Prim::Cnt, vkey, c.fkey, cond, "");
+    PrimSlot sum = al.get(Prim::SumI64, vkey, c.fkey, cond, v.v, c.merging ? (u128)1 << 63 : v.maxabs);
+    const int j = add_out(DType::of(TypeId::Int64), true);
+    put(j, "i64", acc(cnt) + " ? (i64)" + acc(sum) + " : 0");
+    put_ok(j, acc(cnt) + " ? 1 : 0");
+    explain(c.merge_label(), "sum_int -> Int64");
+  }
+
+  void float_sum_avg(const Call& c) {
+    const bool is_avg = c.a.kind == AggKind::Avg;
+    Val v = g.named(g.gen(c.children.at(0)));
+    if (c.merging) {
+      // float: Avg merge/evaluate (avg.rs:146-176, :283-327) / DataFusion sum merge
+      if (v.rep != Rep::F64) throw CometError("Final float aggregate expects a Float64 state column");
+    } else if (!(v.rep == Rep::F64 || v.rep == Rep::F32 || v.rep == Rep::I32 || v.rep == Rep::I64)) {
+      // float sum (DataFusion sum_udaf over Float64, planner.rs:2628-2634) / Avg (avg.rs): child cast to Float64
+      throw CometError("float sum/avg over " + v.t.str() + " is not supported in the GPU pipeline yet");
+    }
+    const std::string vkey = c.vkey(g), cond = c.guarded(v.ok);
+    // the values summed: rows in Partial mode, non-NULL partial sums in a merge — where an average's count is the sum of the states' counts
+    PrimSlot n = al.get(Prim::Cnt, vkey, c.fkey, cond, "");
+    const AggLowering::FSum fsum = al.get_fsum(c.merging ? vkey : "f64:" + vkey, c.fkey, cond, {v.v});
+    const std::string SUMX = al.fread(fsum);
+    PrimSlot cnt = n;
+    if (is_avg && c.merging) {
+      Val s2 = g.named(g.gen(c.children.at(1)));
+      cnt = al.get(Prim::SumI64, vkey + "#cnt", "", s2.ok, s2.v, (u128)1 << 63);
+    }
+    const int j = add_out(DType::of(TypeId::Double), true);
+    if (is_avg && c.as_state) {
+      // AvgAccumulator::state (avg.rs:139-144; after a merge :139-176): (sum, count).  Ungrouped, the sum is Some once any batch arrived — a merge: any
+      // non-NULL partial sum; grouped never NULL
+      const int j1 = add_out(DType::of(TypeId::Int64), true);
+      put(j, "double", SUMX);
+      put_ok(j, grouped ? "1" : acc(c.merging ? n : rowcnt) + " ? 1 : 0");
+      put(j1, "i64", "(i64)" + acc(cnt));
+      put_ok(j1, "1");
+      explain(c.label(), "avg_f64 -> (Float64, count)");
+    } else if (is_avg) {
+      fin += "    { i64 count = (i64)" + acc(cnt) + ";\n";
+      put(j, "double", "count ? comet::fp_div(" + SUMX + ", (double)count) : 0.0", IN2);
+      put_ok(j, "count ? 1 : 0", IN2, " }");
+      explain(c.label(), "avg_f64 -> Float64");
+    } else {
+      put(j, "double", SUMX);
+      put_ok(j, acc(n) + " ? 1 : 0");
+      explain(c.merge_label(), "sum_f64 -> Float64");
+    }
+  }
+
+  // ---- min / max ----
+  void min_max(const Call& c) {
+    if (!c.merging && c.children.size() != 1) throw CometError("min/max expects one child");
+    Val v = g.named(g.gen(c.children.at(0)));
+    const bool mn = c.a.kind == AggKind::Min;
+    if (!c.merging && !(v.t == c.a.dtype)) throw CometError("min/max with cast is not supported in the GPU pipeline yet");
+    const std::string vkey = c.vkey(g), cond = c.guarded(v.ok);
+    PrimSlot cnt = al.get(Prim::Cnt, vkey, c.fkey, cond, "");
+    PrimSlot s;
+    std::string rd;
+    const char* st = store_ctype(v.t);
+    // (not AggLowering::value_read: a Float32 extreme is kept as a double and cast on the way out, a first / last value bit for bit)
+    if (v.rep == Rep::I32 || v.rep == Rep::I64) {
+      s = al.get(mn ? Prim::MinI64 : Prim::MaxI64, vkey, c.fkey, cond, v.v);
+      rd = v.t.id == TypeId::Decimal ? "(i128)(i64)" + acc(s) : std::string("(") + st + ")(i64)" + acc(s);
+    } else if (v.rep == Rep::I128) {
+      s = al.get(mn ? Prim::MinI128 : Prim::MaxI128, vkey, c.fkey, cond, v.v);
+      rd = "comet::mk128(acc[" + std::to_string(s.word + 1) + "], " + acc(s) + ")";
+    } else if (v.rep == Rep::F64 || v.rep == Rep::F32) {
+      s = al.get(mn ? Prim::MinF64 : Prim::MaxF64, vkey, c.fkey, cond, v.v);
+      rd = std::string("(") + st + ")__longlong_as_double((i64)" + acc(s) + ")";
+    } else {
+      throw CometError("min/max over " + v.t.str() + " is not supported in the GPU pipeline yet");
+    }
+    const int j = add_out(v.t, true);
+    put(j, st, acc(cnt) + " ? " + rd + " : (" + st + ")0");
+    put_ok(j, acc(cnt) + " ? 1 : 0");
+    explain(c.merge_label(), std::string(mn ? "min" : "max") + " -> " + v.t.str());
+  }
+
   // ---- statistical aggregates (var_* / stddev_* / covar_* / corr): exact moment sums (comet_device.hpp "Statistical aggregates") ----
-  struct StatSums { PrimSlot n; AggLowering::FSum sx, sy, sxx, syy, sxy; bool has_sxx = false, has_syy = false, has_sxy = false; };
+  struct StatSums { PrimSlot n; AggLowering::FSum sx, sy, sxx, syy, sxy; };
   // state columns and the explain text's shape of each function (variance.rs / stddev.rs / covariance.rs / correlation.rs state_fields)
-  auto stat_state_names = [](AggKind k) -> std::string {
+  static std::string stat_state_names(AggKind k) {
     if (k == AggKind::Covariance) return "count, mean1, mean2, algo_const";
     if (k == AggKind::Correlation) return "count, mean1, mean2, algo_const, m2_1, m2_2";
     return "count, mean, m2";
-  };
+  }
   // the finished moments of one group (n, mean1, mean2, c, m2_1, m2_2 as expressions), then either the state columns or the result
-  auto stat_emit = [&](const AggExpr& a, const StatSums& ss, bool as_state, const char* label) {
-    const std::string N = "acc[" + std::to_string(ss.n.word) + "]";
+  void stat_emit(const Call& c, const StatSums& ss) {
+    const AggExpr& a = c.a;
+    const std::string N = acc(ss.n);
     const std::string MEAN1 = "comet::fix_mean(" + al.fargs(ss.sx) + ", " + N + ")";
     std::vector<std::string> cols = {"(double)" + N, MEAN1};
     if (a.kind == AggKind::Variance || a.kind == AggKind::Stddev) {
@@ -3713,19 +3973,13 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
         cols.push_back("comet::fix_m2(" + al.fargs(ss.syy) + ", " + al.fargs(ss.sy) + ", " + N + ")");
       }
     }
-    const char* name = stat_agg_name(a);
-    if (as_state) {
+    const std::string name = stat_agg_name(a);
+    if (c.as_state) {
       // Partial / PartialMerge: the state columns, all Float64 and never NULL (an empty group is (0, 0, 0 …))
       fin += "    {\n";
-      for (size_t c = 0; c < cols.size(); c++) {
-        fin += "      ((double*)" + out_val(out_j) + ")" + ROW + " = " + cols[c] + ";\n";
-        OutCol oc; oc.type = DType::of(TypeId::Double); oc.nullable = false;
-        d.out_cols.push_back(oc);
-        out_j++;
-      }
+      for (auto& col : cols) put(add_out(DType::of(TypeId::Double), false), "double", col, IN2);
       fin += "    }\n";
-      ex << "  agg" << label << ": " << name << "_f64 -> (" << stat_state_names(a.kind) << ")\n";
-      return;
+      return explain(c.label(), name + "_f64 -> (" + stat_state_names(a.kind) + ")");
     }
     const std::string sample = a.stats_type == 0 ? "true" : "false", nodz = a.null_on_divide_by_zero ? "true" : "false";
     fin += "    { bool v_ = false; double r_ = 0.0;\n";
@@ -3734,624 +3988,221 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
     else
       fin += "      r_ = comet::stat_finalize(" + cols[a.kind == AggKind::Covariance ? 3 : 2] + ", " + N + ", " + sample + ", " + nodz + ", v_);\n";
     if (a.kind == AggKind::Stddev) fin += "      r_ = __dsqrt_rn(r_);\n";
-    fin += "      ((double*)" + out_val(out_j) + ")" + ROW + " = r_;\n";
-    fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = v_ ? 1 : 0; }\n";
-    OutCol oc; oc.type = DType::of(TypeId::Double); oc.nullable = true;
-    d.out_cols.push_back(oc);
-    out_j++;
-    ex << "  agg" << label << ": " << name << "_f64 -> Float64\n";
-  };
-  auto stat_check = [&](const AggExpr& a, size_t nchildren, bool final_mode) {
+    const int j = add_out(DType::of(TypeId::Double), true);
+    put(j, "double", "r_", IN2);
+    put_ok(j, "v_ ? 1 : 0", IN2, " }");
+    explain(c.label(), name + "_f64 -> Float64");
+  }
+  void stat_f64(const AggExpr& a, const Val& v, const char* what) {
+    if (v.rep != Rep::F64 || v.t.id != TypeId::Double)
+      throw CometError(std::string(stat_agg_name(a)) + " over " + v.t.str() + " is not supported: its " + what + " must be Float64 (Spark casts the input to double)");
+  }
+  void stat(const Call& c) {
+    const AggExpr& a = c.a;
     if (a.stats_type != 0 && a.stats_type != 1)
       throw CometError("Unknown StatisticsType " + std::to_string(a.stats_type) + " for " + (a.kind == AggKind::Covariance ? "Covariance" : a.kind == AggKind::Stddev ? "Stddev" : "Variance"));
     const bool two = a.kind == AggKind::Covariance || a.kind == AggKind::Correlation;
-    const size_t want = final_mode ? (a.kind == AggKind::Correlation ? 6 : two ? 4 : 3) : (two ? 2 : 1);
-    if (nchildren != want) throw CometError(std::string(stat_agg_name(a)) + " expects " + std::to_string(want) + (final_mode ? " state columns" : " children"));
-  };
-  auto stat_f64 = [&](const AggExpr& a, const Val& v, const char* what) {
-    if (v.rep != Rep::F64 || v.t.id != TypeId::Double)
-      throw CometError(std::string(stat_agg_name(a)) + " over " + v.t.str() + " is not supported: its " + what + " must be Float64 (Spark casts the input to double)");
-  };
+    const size_t want = c.merging ? (size_t)state_arity(a) : (two ? 2 : 1);
+    if (c.children.size() != want) throw CometError(std::string(stat_agg_name(a)) + " expects " + std::to_string(want) + (c.merging ? " state columns" : " children"));
+    StatSums ss;
+    if (c.merging) {
+      // merge_batch of the Welford states as an EXACT merge of the states as they were rounded: N = Σ n_i (integers), S1 = Σ n_i·mean_i,
+      // S2 = Σ (m2_i + n_i·mean_i²) (co-moments: c_i + n_i·mean1_i·mean2_i), every product split into doubles that add up to it exactly
+      // (two_prod of two_prod: five addends); states with n_i = 0 are skipped (variance.rs merge_batch).  Then the Partial finisher.
+      std::vector<Val> sv;
+      for (auto& ch : c.children) {
+        sv.push_back(g.named(g.gen(ch)));
+        stat_f64(a, sv.back(), "state column");
+      }
+      std::string cond;
+      for (auto& v : sv) cond = Gen::and_ok(cond, v.ok);
+      cond = Gen::and_ok(cond, "(" + sv[0].v + " != 0.0)");
+      const std::string vk = c.vkey(g), n = sv[0].v;
+      // m + n·mean·other exactly: m, then the hi and lo of (hi of n·mean)·other and of (lo of n·mean)·other
+      auto merged = [&](const std::string& m, const std::string& mean, const std::string& other) {
+        const std::string ph = "comet::fp_mul(" + n + ", " + mean + ")", pl = "comet::two_prod_lo(" + n + ", " + mean + ")";
+        return std::vector<std::string>{m, "comet::fp_mul(" + ph + ", " + other + ")", "comet::two_prod_lo(" + ph + ", " + other + ")",
+                                        "comet::fp_mul(" + pl + ", " + other + ")", "comet::two_prod_lo(" + pl + ", " + other + ")"};
+      };
+      auto first_moment = [&](const std::string& mean) {
+        return std::vector<std::string>{"comet::fp_mul(" + n + ", " + mean + ")", "comet::two_prod_lo(" + n + ", " + mean + ")"};
+      };
+      ss.n = al.get(Prim::SumI64, vk + "#n", "", cond, "(i64)(" + n + ")", (u128)1 << 63);
+      ss.sx = al.get_fsum(vk + "#s1", "", cond, first_moment(sv[1].v));
+      if (!two) {
+        ss.sxx = al.get_fsum(vk + "#s2", "", cond, merged(sv[2].v, sv[1].v, sv[1].v));
+      } else {
+        ss.sy = al.get_fsum(vk + "#s1y", "", cond, first_moment(sv[2].v));
+        ss.sxy = al.get_fsum(vk + "#sxy", "", cond, merged(sv[3].v, sv[1].v, sv[2].v));
+        if (a.kind == AggKind::Correlation) {
+          ss.sxx = al.get_fsum(vk + "#s2", "", cond, merged(sv[4].v, sv[1].v, sv[1].v));
+          ss.syy = al.get_fsum(vk + "#s2y", "", cond, merged(sv[5].v, sv[2].v, sv[2].v));
+        }
+      }
+    } else {
+      // update_batch (variance.rs / covariance.rs / correlation.rs): rows where every child is non-NULL (and the FILTER holds) count.  The
+      // sums are keyed like avg's — "f64:" + the value's key — so avg(x), var_samp(x) and stddev_samp(x) over one x and filter share Σx and
+      // the count; a pair's sums also carry the other child's validity in their key
+      Val x = g.named(g.gen(c.children[0]));
+      stat_f64(a, x, two ? "first child" : "child");
+      Val y = x;
+      if (two) {
+        y = g.named(g.gen(c.children[1]));
+        stat_f64(a, y, "second child");
+      }
+      const std::string kx = g.key_of(c.children[0]), ky = two ? g.key_of(c.children[1]) : kx;
+      const std::string cond = c.guarded(two ? Gen::and_ok(x.ok, y.ok) : x.ok);
+      const std::string vx = two && !y.ok.empty() ? kx + "|valid:" + ky : kx, vy = two && !x.ok.empty() ? ky + "|valid:" + kx : ky;
+      auto sq = [](const std::string& u, const std::string& v) {
+        return std::vector<std::string>{"comet::fp_mul(" + u + ", " + v + ")", "comet::two_prod_lo(" + u + ", " + v + ")"};
+      };
+      ss.n = al.get(Prim::Cnt, vx, c.fkey, cond, "");
+      ss.sx = al.get_fsum("f64:" + vx, c.fkey, cond, {x.v});
+      if (two) ss.sy = al.get_fsum("f64:" + vy, c.fkey, cond, {y.v});
+      if (a.kind != AggKind::Covariance) ss.sxx = al.get_fsum("f64sq:" + vx, c.fkey, cond, sq(x.v, x.v));
+      if (a.kind == AggKind::Correlation) ss.syy = al.get_fsum("f64sq:" + vy, c.fkey, cond, sq(y.v, y.v));
+      if (two) ss.sxy = al.get_fsum("f64xy:" + kx + "," + ky, c.fkey, cond, sq(x.v, y.v));
+    }
+    stat_emit(c, ss);
+  }
 
-  // ---- first / last (planner.rs:2679-2702 → DataFusion's FirstValue / LastValue without ORDER BY) and bit_and / bit_or / bit_xor (:2703-2735) ----
-  // first / last keep a fixed-width state: Boolean, the integers, the floats (bit for bit), Date, Timestamp / TimestampNTZ, Decimal of any precision
-  auto pick_check = [&](const AggExpr& a, const ExprP& child) {
-    const char* name = order_bit_agg_name(a.kind);
-    DType t = child->dtype;
-    if (child->kind == ExprKind::Bound && child->bound_index >= 0 && (size_t)child->bound_index < d.in_types.size()) t = d.in_types[(size_t)child->bound_index];
-    if (t.id == TypeId::String || t.id == TypeId::Bytes || t.is_nested())
-      throw CometError(std::string(name) + " over " + t.str() + " is not supported in a HashAggregate by the MI355X native engine yet (its state is fixed-width: Boolean, integers, floats, Date, Timestamp, Decimal)");
-  };
-  auto pick_check_val = [&](const AggExpr& a, const Val& v) {
-    if (v.rep == Rep::STR)
-      throw CometError(std::string(order_bit_agg_name(a.kind)) + " over " + v.t.str() + " is not supported in a HashAggregate by the MI355X native engine yet (its state is fixed-width: Boolean, integers, floats, Date, Timestamp, Decimal)");
-    store_ctype(v.t);
-  };
+  // ---- first / last (planner.rs:2679-2702 → DataFusion's FirstValue / LastValue without ORDER BY) ----
+  // they keep a fixed-width state: Boolean, the integers, the floats (bit for bit), Date, Timestamp / TimestampNTZ, Decimal of any precision.
   // Partial state = (value: child type, nullable; is_set: Boolean) — Spark's own buffer (First.aggBufferAttributes = first :: valueSet) and, from memory (its
   // source is not in the reference tree), DataFusion's FirstValue::state_fields without orderings; Final evaluates to the value
-  auto pick_emit = [&](const AggExpr& a, const Val& v, const AggLowering::Pick& p, bool as_state, const char* label) {
+  void first_last(const Call& c) {
+    const AggExpr& a = c.a;
+    const char* fn = order_bit_agg_name(a.kind);
+    const char* fixed_width = " is not supported in a HashAggregate by the MI355X native engine yet (its state is fixed-width: Boolean, integers, floats, Date, Timestamp, Decimal)";
+    if (c.merging && c.children.size() != 2) throw CometError(std::string(fn) + " expects (value, is_set) state columns");
+    if (!c.merging && c.children.size() != 1) throw CometError(std::string(fn) + " expects one child");
+    const ExprP& child = c.children[0];
+    DType t = child->dtype;
+    if (child->kind == ExprKind::Bound && child->bound_index >= 0 && (size_t)child->bound_index < d.in_types.size()) t = d.in_types[(size_t)child->bound_index];
+    if (t.id == TypeId::String || t.id == TypeId::Bytes || t.is_nested()) throw CometError(std::string(fn) + " over " + t.str() + fixed_width);
+    Val v = g.named(g.gen(child));
+    Val s2;
+    if (c.merging) s2 = g.named(g.gen(c.children[1]));
+    if (v.rep == Rep::STR) throw CometError(std::string(fn) + " over " + v.t.str() + fixed_width);
     const char* st = store_ctype(v.t);
+    std::string key, cond;
+    if (c.merging) {
+      // merge_batch: the first (last) STATE ROW of the group whose is_set is true, in state-row order; its value may be NULL
+      if (s2.rep != Rep::B) throw CometError(std::string("Final ") + fn + " expects (value, is_set) state columns, got is_set : " + s2.t.str());
+      key = c.vkey(g) + "|" + g.key_of(c.children[1]);
+      cond = Gen::and_ok(s2.ok, s2.v);
+    } else {
+      // update_batch: the first (last) row that passes the FILTER — with ignore_nulls, the first (last) such row whose value is not NULL
+      key = g.key_of(child) + "|" + c.fkey + (a.ignore_nulls ? "|nn" : "");
+      cond = c.guarded(a.ignore_nulls ? v.ok : std::string());
+    }
+    const AggLowering::Pick p = al.get_pick(a.kind == AggKind::First, key, cond, v, child);
     const std::string set = "(acc[" + std::to_string(p.ord) + "] != " + AggLowering::ord_identity(p.first) + ")";
     fin += "    { const bool set_ = " + set + ", ok_ = set_ && acc[" + std::to_string(p.ok) + "] != 0;\n";
-    fin += "      ((" + std::string(st) + "*)" + out_val(out_j) + ")" + ROW + " = ok_ ? " + AggLowering::value_read(v, p.val) + " : (" + st + ")0;\n";
-    fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = ok_ ? 1 : 0;\n";
-    OutCol s0; s0.type = v.t; s0.nullable = true;
-    d.out_cols.push_back(s0);
-    out_j++;
-    const std::string name = std::string(order_bit_agg_name(a.kind)) + (a.ignore_nulls ? "(ignore_nulls)" : "");
-    if (as_state) {
-      fin += "      ((u8*)" + out_val(out_j) + ")" + ROW + " = set_ ? 1 : 0;\n";
-      OutCol s1; s1.type = DType::of(TypeId::Bool); s1.nullable = false;
-      d.out_cols.push_back(s1);
-      out_j++;
-      ex << "  agg" << label << ": " << name << " -> (" << v.t.str() << ", is_set)\n";
+    const int j = add_out(v.t, true);
+    put(j, st, "ok_ ? " + AggLowering::value_read(v, p.val) + " : (" + st + ")0", IN2);
+    put_ok(j, "ok_ ? 1 : 0", IN2);
+    const std::string name = std::string(fn) + (a.ignore_nulls ? "(ignore_nulls)" : "");
+    if (c.as_state) {
+      put(add_out(DType::of(TypeId::Bool), false), "u8", "set_ ? 1 : 0", IN2);
+      explain(c.label(), name + " -> (" + v.t.str() + ", is_set)");
     } else {
-      ex << "  agg" << label << ": " << name << " -> " << v.t.str() << "\n";
+      explain(c.label(), name + " -> " + v.t.str());
     }
     fin += "    }\n";
-  };
+  }
+
+  // ---- bit_and / bit_or / bit_xor (planner.rs:2703-2735) ----
   // state = result = one nullable column of the input's integer type, in every mode; merging states is the same operation
-  auto bit_agg = [&](const AggExpr& a, const Val& v, const std::string& vkey, const std::string& fkey, const std::string& cond, const char* label) {
+  void bitwise(const Call& c) {
+    const AggExpr& a = c.a;
     const char* name = order_bit_agg_name(a.kind);
+    if (c.children.size() != 1) throw CometError(std::string(name) + (c.merging ? " expects one state column" : " expects one child"));
+    Val v = g.named(g.gen(c.children[0]));
+    const std::string vkey = c.vkey(g), cond = c.guarded(v.ok);
     if (!v.t.is_integer())
       throw CometError(std::string(name) + " over " + v.t.str() + " is not supported: the bitwise aggregates take Int8, Int16, Int32 or Int64 (AggSerde.bitwiseAggTypeSupported)");
-    PrimSlot cnt = al.get(Prim::Cnt, vkey, fkey, cond, "");
-    PrimSlot s = al.get(a.kind == AggKind::BitAnd ? Prim::BitAnd : a.kind == AggKind::BitOr ? Prim::BitOr : Prim::BitXor, vkey, fkey, cond, v.v);
+    PrimSlot cnt = al.get(Prim::Cnt, vkey, c.fkey, cond, "");
+    PrimSlot s = al.get(a.kind == AggKind::BitAnd ? Prim::BitAnd : a.kind == AggKind::BitOr ? Prim::BitOr : Prim::BitXor, vkey, c.fkey, cond, v.v);
     const char* st = store_ctype(v.t);
-    const std::string C = "acc[" + std::to_string(cnt.word) + "]";
-    fin += "    ((" + std::string(st) + "*)" + out_val(out_j) + ")" + ROW + " = " + C + " ? (" + st + ")(i64)acc[" + std::to_string(s.word) + "] : (" + st + ")0;\n";
-    fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = " + C + " ? 1 : 0;\n";
-    OutCol oc; oc.type = v.t; oc.nullable = true;
-    d.out_cols.push_back(oc);
-    out_j++;
-    ex << "  agg" << label << ": " << name << " -> " << v.t.str() << "\n";
-  };
-
-  // rows that reach the aggregate
-  PrimSlot rowcnt = al.get(Prim::RowCnt, "*", "", "", "");
-  const std::string rowcnt_word = std::to_string(rowcnt.word);
-  long long max_rows_exact = 0;
-  for (auto& in : agg_ins) {
-    const AggExpr& a = *in.a;
-    std::string fkey, guard;
-    if (in.filter) {
-      // FILTER (WHERE …): row contributes only if the filter is TRUE and valid (sum_decimal.rs:452-458)
-      Val f = g.named(g.gen(in.filter));
-      fkey = g.key_of(in.filter);
-      guard = Gen::and_ok(f.ok, f.v);
-    }
-    auto guarded = [&](const std::string& ok) { return Gen::and_ok(guard, ok); };
-    const bool final_mode = in.mode == AggMode::Final || in.mode == AggMode::PartialMerge;
-    const bool emit_state = in.mode == AggMode::PartialMerge;
-    if (final_mode) {
-      // ---- Final mode: merge Partial states (merge_batch + evaluate of each accumulator) ----
-      auto okx = [](const Val& v) { return v.ok.empty() ? std::string("true") : v.ok; };
-      switch (a.kind) {
-        case AggKind::Count: {
-          // count state: Int64, summed (DataFusion count_udaf merge)
-          Val c = g.named(g.gen(in.children.at(0)));
-          if (!c.t.is_integer()) throw CometError("Final count expects an Int64 state column");
-          PrimSlot s = al.get(Prim::SumI64, "fin:" + g.key_of(in.children[0]), "", c.ok, c.v, (u128)1 << 63);
-          OutCol oc; oc.type = DType::of(TypeId::Int64); oc.nullable = false;
-          d.out_cols.push_back(oc);
-          fin += "    ((i64*)" + out_val(out_j) + ")" + ROW + " = (i64)acc[" + std::to_string(s.word) + "];\n";
-          out_j++;
-          ex << "  agg(final): count -> Int64\n";
-          break;
-        }
-        case AggKind::Sum: case AggKind::Avg: {
-          const bool is_avg = a.kind == AggKind::Avg;
-          if (a.dtype.id == TypeId::Decimal) {
-            Val sv = g.named(g.gen(in.children.at(0)));
-            Val s2 = g.named(g.gen(in.children.at(1)));
-            const DType st = is_avg ? a.sum_dtype : a.dtype;
-            if (!(sv.t == st)) throw CometError("Final decimal aggregate: state type " + sv.t.str() + " differs from " + st.str());
-            const u128 bound = pow10_u128(st.precision) - 1;
-            const std::string vk = "fin:" + g.key_of(in.children[0]);
-            std::string val128 = sv.rep == Rep::I128 ? sv.v : "(i128)" + sv.v;
-            if (!is_avg) {
-              // SumDecimal merge_batch (sum_decimal.rs:309-368 / :540-609): state = (sum nullable, is_empty)
-              if (s2.rep != Rep::B) throw CometError("Final SumDecimal expects (sum, is_empty) state columns");
-              const std::string empty = "(" + s2.v + ")";                       // is_empty is non-null
-              const std::string that_ovf = "(!" + empty + " && !" + okx(sv) + ")";  // overflowed partial: sticky
-              const std::string contrib = "(!" + empty + " && " + okx(sv) + ")";
-              PrimSlot cnt = al.get(Prim::Cnt, vk, "ne", contrib, "");
-              PrimSlot any_ovf = al.get(Prim::Cnt, vk, "ovf", that_ovf, "");
-              PrimSlot sum = al.get(Prim::Sum192, vk, "", contrib, val128, bound);
-              PrimSlot amax = al.get(Prim::AMaxHi, vk, "", contrib, val128);
-              PrimSlot sflags = al.get(Prim::SignFlags, vk, "", contrib, val128);
-              auto kw = [&](const PrimSlot& ps) {
-                return ps.kernel_level ? "((const u64*)prm.out[" + std::to_string(kOutErr) + "])[2 + " + std::to_string(ps.word) + "]"
-                                       : "acc[" + std::to_string(ps.word) + "]";
-              };
-              const std::string W = std::to_string(sum.word), W1 = std::to_string(sum.word + 1);
-              fin += "    {\n      i128 total = comet::mk128(acc[" + W1 + "], acc[" + W + "]);\n      bool ovf = false;\n";
-              fin += "      comet::sum_overflow_decide(acc + " + W + ", " + kw(amax) + ", " + kw(sflags) + ", acc[" + std::to_string(cnt.word) + "], " +
-                     lit_u128(bound) + ", ovf, (unsigned int*)prm.out[" + std::to_string(kOutErr) + "]);\n";
-              g.uses_err = true;
-              // ANSI: merging into an overflow fails the query (sum_decimal.rs:352-358, 594-600)
-              if (a.eval_mode == EvalMode::Ansi) note_agg_ctx(0, a);
-              if (a.eval_mode == EvalMode::Ansi)
-                fin += "      if (acc[" + std::to_string(any_ovf.word) + "] != 0 || ovf || (acc[" + std::to_string(cnt.word) + "] != 0 && !comet::dec_fits(total, " + lit_u128(bound) +
-                       "))) atomicOr((unsigned int*)prm.out[" + std::to_string(kOutErr) + "], 65536u);\n";
-              if (emit_state) {
-                // merged state (sum_decimal.rs:281-295 after :309-368): sum is NULL once any side overflowed, is_empty only
-                // if every merged state was empty
-                fin += "      bool sovf = acc[" + std::to_string(any_ovf.word) + "] != 0 || ovf || !comet::dec_fits(total, " + lit_u128(bound) + ");\n";
-                fin += "      bool empty = acc[" + std::to_string(cnt.word) + "] == 0 && acc[" + std::to_string(any_ovf.word) + "] == 0;\n";
-                fin += "      ((i128*)" + out_val(out_j) + ")" + ROW + " = sovf ? (i128)0 : total;\n";
-                fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = sovf ? 0 : 1;\n";
-                fin += "      ((u8*)" + out_val(out_j + 1) + ")" + ROW + " = empty ? 1 : 0;\n    }\n";
-                OutCol s0; s0.type = st; s0.nullable = true;
-                OutCol s1; s1.type = DType::of(TypeId::Bool); s1.nullable = false;
-                d.out_cols.push_back(s0);
-                d.out_cols.push_back(s1);
-                out_j += 2;
-                ex << "  agg(partial-merge): sum_decimal -> (" << st.str() << ", is_empty)\n";
-              } else {
-              // evaluate (sum_decimal.rs:264-279): NULL if empty, overflowed, or out of precision
-              fin += "      bool isnull = acc[" + std::to_string(cnt.word) + "] == 0 || acc[" + std::to_string(any_ovf.word) + "] != 0 || ovf || !comet::dec_fits(total, " + lit_u128(bound) + ");\n";
-              fin += "      ((i128*)" + out_val(out_j) + ")" + ROW + " = isnull ? (i128)0 : total;\n";
-              fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = isnull ? 0 : 1;\n    }\n";
-              OutCol oc; oc.type = st; oc.nullable = true;
-              d.out_cols.push_back(oc);
-              out_j++;
-              ex << "  agg(final): sum_decimal -> " << st.str() << "\n";
-              }
-            } else {
-              // AvgDecimal merge (avg_decimal.rs:542-595) + evaluate (:597-636, avg() :670-689): state = (sum nullable, count)
-              if (!s2.t.is_integer()) throw CometError("Final AvgDecimal expects (sum, count) state columns");
-              PrimSlot cnt = al.get(Prim::SumI64, vk + "#cnt", "", s2.ok, s2.v, (u128)1 << 63);
-              PrimSlot bad = al.get(Prim::Cnt, vk, "nullstate", "(!" + okx(sv) + " || !" + okx(s2) + ")", "");
-              PrimSlot nsum = al.get(Prim::Cnt, vk, "nsum", sv.ok, "");
-              PrimSlot sum = al.get(Prim::Sum192, vk, "", sv.ok, val128, bound);
-              PrimSlot amax = al.get(Prim::AMaxHi, vk, "", sv.ok, val128);
-              PrimSlot sflags = al.get(Prim::SignFlags, vk, "", sv.ok, val128);
-              auto kw = [&](const PrimSlot& ps) {
-                return ps.kernel_level ? "((const u64*)prm.out[" + std::to_string(kOutErr) + "])[2 + " + std::to_string(ps.word) + "]"
-                                       : "acc[" + std::to_string(ps.word) + "]";
-              };
-              const std::string W = std::to_string(sum.word), W1 = std::to_string(sum.word + 1);
-              const u128 tbound = pow10_u128(a.dtype.precision) - 1;
-              const int up = std::max(0, a.dtype.scale - st.scale);
-              fin += "    {\n      i128 total = comet::mk128(acc[" + W1 + "], acc[" + W + "]);\n      bool ovf = false;\n";
-              fin += "      comet::sum_overflow_decide(acc + " + W + ", " + kw(amax) + ", " + kw(sflags) + ", acc[" + std::to_string(nsum.word) + "], " +
-                     lit_u128(bound) + ", ovf, (unsigned int*)prm.out[" + std::to_string(kOutErr) + "]);\n";
-              g.uses_err = true;
-              fin += "      i64 count = (i64)acc[" + std::to_string(cnt.word) + "];\n";
-              // grouped (AvgDecimalGroupsAccumulator::merge_batch, avg_decimal.rs:542-595): a NULL partial sum / count or an
-              // overflowing merge step clears is_not_null for good.  Ungrouped (AvgDecimalAccumulator::merge_batch, :331-356):
-              // arrow's sum() skips NULL partial sums and only the batch total is checked against the precision.
-              if (grouped) fin += "      bool sum_ok = acc[" + std::to_string(bad.word) + "] == 0 && !ovf;\n";
-              else fin += "      bool sum_ok = acc[" + std::to_string(nsum.word) + "] != 0 && comet::dec_fits(total, " + lit_u128(bound) + ");\n";
-              // ANSI: an overflowed sum under a count fails the query (avg_decimal.rs:366-380, 576-580, 610-616)
-              if (a.eval_mode == EvalMode::Ansi) note_agg_ctx(1, a);
-              if (a.eval_mode == EvalMode::Ansi)
-                fin += "      if (!sum_ok && count > 0) atomicOr((unsigned int*)prm.out[" + std::to_string(kOutErr) + "], 131072u);\n";
-              if (emit_state) {
-                // state: grouped sums and counts share the is_not_null mask (:638-653); ungrouped (sum Option, count) (:301-306)
-                fin += "      ((i128*)" + out_val(out_j) + ")" + ROW + " = sum_ok ? total : (i128)0;\n";
-                fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = sum_ok ? 1 : 0;\n";
-                fin += std::string("      ((i64*)") + out_val(out_j + 1) + ")" + ROW + " = " + (grouped ? "sum_ok ? count : 0" : "count") + ";\n";
-                fin += std::string("      ((u8*)") + out_ok(out_j + 1) + ")" + ROW + " = " + (grouped ? "sum_ok ? 1 : 0" : "1") + ";\n    }\n";
-                OutCol s0; s0.type = st; s0.nullable = true;
-                OutCol s1; s1.type = DType::of(TypeId::Int64); s1.nullable = true;
-                d.out_cols.push_back(s0);
-                d.out_cols.push_back(s1);
-                out_j += 2;
-                ex << "  agg(partial-merge): avg_decimal -> (" << st.str() << ", count)\n";
-              } else {
-              fin += "      i128 avgv = 0;\n";
-              fin += "      bool has = sum_ok && count != 0 && comet::dec_avg(total, count, " +
-                     lit_i128((i128)pow10_u128(up)) + ", " + lit_u128(tbound) + ", avgv);\n";
-              fin += "      ((i128*)" + out_val(out_j) + ")" + ROW + " = has ? avgv : (i128)0;\n";
-              fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = has ? 1 : 0;\n    }\n";
-              OutCol oc; oc.type = a.dtype; oc.nullable = true;
-              d.out_cols.push_back(oc);
-              out_j++;
-              ex << "  agg(final): avg_decimal -> " << a.dtype.str() << "\n";
-              }
-            }
-          } else if (!is_avg && a.dtype.is_integer()) {
-            // SumInteger merge (sum_int.rs:494-530): wrapping sum of the non-null partial sums, NULL if none
-            Val sv = g.named(g.gen(in.children.at(0)));
-            const std::string vk = "fin:" + g.key_of(in.children[0]);
-            PrimSlot cnt = al.get(Prim::Cnt, vk, "", sv.ok, "");
-            PrimSlot sum = al.get(Prim::SumI64, vk, "", sv.ok, sv.v, (u128)1 << 63);
-            fin += "    ((i64*)" + out_val(out_j) + ")" + ROW + " = acc[" + std::to_string(cnt.word) + "] ? (i64)acc[" + std::to_string(sum.word) + "] : 0;\n";
-            fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = acc[" + std::to_string(cnt.word) + "] ? 1 : 0;\n";
-            OutCol oc; oc.type = DType::of(TypeId::Int64); oc.nullable = true;
-            d.out_cols.push_back(oc);
-            out_j++;
-            ex << "  agg(final): sum_int -> Int64\n";
-          } else {
-            // float: Avg merge/evaluate (avg.rs:146-176, :283-327) / DataFusion sum merge
-            Val sv = g.named(g.gen(in.children.at(0)));
-            if (sv.rep != Rep::F64) throw CometError("Final float aggregate expects a Float64 state column");
-            const std::string vk = "fin:" + g.key_of(in.children[0]);
-            PrimSlot nsum = al.get(Prim::Cnt, vk, "", sv.ok, "");
-            const AggLowering::FSum fsum = al.get_fsum(vk, "", sv.ok, sv.v);
-            const std::string SUMX = al.fread(fsum);
-            if (is_avg && emit_state) {
-              // AvgAccumulator / AvgGroupsAccumulator state after merge (avg.rs:139-176): (sum, count)
-              Val s2 = g.named(g.gen(in.children.at(1)));
-              PrimSlot cnt = al.get(Prim::SumI64, vk + "#cnt", "", s2.ok, s2.v, (u128)1 << 63);
-              fin += "    ((double*)" + out_val(out_j) + ")" + ROW + " = " + SUMX + ";\n";
-              fin += std::string("    ((u8*)") + out_ok(out_j) + ")" + ROW + " = " + (grouped ? "1" : "acc[" + std::to_string(nsum.word) + "] ? 1 : 0") + ";\n";
-              fin += "    ((i64*)" + out_val(out_j + 1) + ")" + ROW + " = (i64)acc[" + std::to_string(cnt.word) + "];\n";
-              fin += "    ((u8*)" + out_ok(out_j + 1) + ")" + ROW + " = 1;\n";
-              OutCol s0; s0.type = DType::of(TypeId::Double); s0.nullable = true;
-              OutCol s1; s1.type = DType::of(TypeId::Int64); s1.nullable = true;
-              d.out_cols.push_back(s0);
-              d.out_cols.push_back(s1);
-              out_j += 2;
-              ex << "  agg(partial-merge): avg_f64 -> (Float64, count)\n";
-              break;
-            }
-            if (is_avg) {
-              Val s2 = g.named(g.gen(in.children.at(1)));
-              PrimSlot cnt = al.get(Prim::SumI64, vk + "#cnt", "", s2.ok, s2.v, (u128)1 << 63);
-              fin += "    { i64 count = (i64)acc[" + std::to_string(cnt.word) + "];\n";
-              fin += "      ((double*)" + out_val(out_j) + ")" + ROW + " = count ? comet::fp_div(" + SUMX + ", (double)count) : 0.0;\n";
-              fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = count ? 1 : 0; }\n";
-            } else {
-              fin += "    ((double*)" + out_val(out_j) + ")" + ROW + " = " + SUMX + ";\n";
-              fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = acc[" + std::to_string(nsum.word) + "] ? 1 : 0;\n";
-            }
-            OutCol oc; oc.type = DType::of(TypeId::Double); oc.nullable = true;
-            d.out_cols.push_back(oc);
-            out_j++;
-            ex << "  agg(final): " << (is_avg ? "avg" : "sum") << "_f64 -> Float64\n";
-          }
-          break;
-        }
-        case AggKind::Min: case AggKind::Max: {
-          Val v = g.named(g.gen(in.children.at(0)));
-          const bool mn = a.kind == AggKind::Min;
-          const std::string vk = "fin:" + g.key_of(in.children[0]);
-          PrimSlot cnt = al.get(Prim::Cnt, vk, "", v.ok, "");
-          PrimSlot s;
-          std::string rd;
-          const char* stc = store_ctype(v.t);
-          if (v.rep == Rep::I32 || v.rep == Rep::I64) {
-            s = al.get(mn ? Prim::MinI64 : Prim::MaxI64, vk, "", v.ok, v.v);
-            rd = v.t.id == TypeId::Decimal ? "(i128)(i64)acc[" + std::to_string(s.word) + "]" : std::string("(") + stc + ")(i64)acc[" + std::to_string(s.word) + "]";
-          } else if (v.rep == Rep::I128) {
-            s = al.get(mn ? Prim::MinI128 : Prim::MaxI128, vk, "", v.ok, v.v);
-            rd = "comet::mk128(acc[" + std::to_string(s.word + 1) + "], acc[" + std::to_string(s.word) + "])";
-          } else if (v.rep == Rep::F64 || v.rep == Rep::F32) {
-            s = al.get(mn ? Prim::MinF64 : Prim::MaxF64, vk, "", v.ok, v.v);
-            rd = std::string("(") + stc + ")__longlong_as_double((i64)acc[" + std::to_string(s.word) + "])";
-          } else throw CometError("min/max over " + v.t.str() + " is not supported in the GPU pipeline yet");
-          const std::string C = std::to_string(cnt.word);
-          fin += "    ((" + std::string(stc) + "*)" + out_val(out_j) + ")" + ROW + " = acc[" + C + "] ? " + rd + " : (" + stc + ")0;\n";
-          fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = acc[" + C + "] ? 1 : 0;\n";
-          OutCol oc; oc.type = v.t; oc.nullable = true;
-          d.out_cols.push_back(oc);
-          out_j++;
-          ex << "  agg(final): " << (mn ? "min" : "max") << " -> " << v.t.str() << "\n";
-          break;
-        }
-        case AggKind::Variance: case AggKind::Stddev: case AggKind::Covariance: case AggKind::Correlation: {
-          // merge_batch of the Welford states as an EXACT merge of the states as they were rounded: N = Σ n_i (integers), S1 = Σ n_i·mean_i,
-          // S2 = Σ (m2_i + n_i·mean_i²) (co-moments: c_i + n_i·mean1_i·mean2_i), every product split into doubles that add up to it exactly
-          // (two_prod of two_prod: five addends); states with n_i = 0 are skipped (variance.rs merge_batch).  Then the Partial finisher.
-          stat_check(a, in.children.size(), true);
-          std::vector<Val> sv;
-          for (auto& c : in.children) {
-            sv.push_back(g.named(g.gen(c)));
-            stat_f64(a, sv.back(), "state column");
-          }
-          std::string cond;
-          for (auto& v : sv) cond = Gen::and_ok(cond, v.ok);
-          cond = Gen::and_ok(cond, "(" + sv[0].v + " != 0.0)");
-          const std::string vk = "fin:" + g.key_of(in.children[0]), n = sv[0].v;
-          // m + n·mean·other exactly: m, then the hi and lo of (hi of n·mean)·other and of (lo of n·mean)·other
-          auto merged = [&](const std::string& m, const std::string& mean, const std::string& other) {
-            const std::string ph = "comet::fp_mul(" + n + ", " + mean + ")", pl = "comet::two_prod_lo(" + n + ", " + mean + ")";
-            return std::vector<std::string>{m, "comet::fp_mul(" + ph + ", " + other + ")", "comet::two_prod_lo(" + ph + ", " + other + ")",
-                                            "comet::fp_mul(" + pl + ", " + other + ")", "comet::two_prod_lo(" + pl + ", " + other + ")"};
-          };
-          auto first_moment = [&](const std::string& mean) {
-            return std::vector<std::string>{"comet::fp_mul(" + n + ", " + mean + ")", "comet::two_prod_lo(" + n + ", " + mean + ")"};
-          };
-          StatSums ss;
-          ss.n = al.get(Prim::SumI64, vk + "#n", "", cond, "(i64)(" + n + ")", (u128)1 << 63);
-          ss.sx = al.get_fsum(vk + "#s1", "", cond, first_moment(sv[1].v));
-          if (a.kind == AggKind::Variance || a.kind == AggKind::Stddev) {
-            ss.sxx = al.get_fsum(vk + "#s2", "", cond, merged(sv[2].v, sv[1].v, sv[1].v));
-          } else {
-            ss.sy = al.get_fsum(vk + "#s1y", "", cond, first_moment(sv[2].v));
-            ss.sxy = al.get_fsum(vk + "#sxy", "", cond, merged(sv[3].v, sv[1].v, sv[2].v));
-            if (a.kind == AggKind::Correlation) {
-              ss.sxx = al.get_fsum(vk + "#s2", "", cond, merged(sv[4].v, sv[1].v, sv[1].v));
-              ss.syy = al.get_fsum(vk + "#s2y", "", cond, merged(sv[5].v, sv[2].v, sv[2].v));
-            }
-          }
-          stat_emit(a, ss, emit_state, emit_state ? "(partial-merge)" : "(final)");
-          break;
-        }
-        case AggKind::First: case AggKind::Last: {
-          // merge_batch: the first (last) STATE ROW of the group whose is_set is true, in state-row order; its value may be NULL
-          if (in.children.size() != 2) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects (value, is_set) state columns");
-          pick_check(a, in.children[0]);
-          Val v = g.named(g.gen(in.children[0]));
-          Val s2 = g.named(g.gen(in.children[1]));
-          pick_check_val(a, v);
-          if (s2.rep != Rep::B) throw CometError(std::string("Final ") + order_bit_agg_name(a.kind) + " expects (value, is_set) state columns, got is_set : " + s2.t.str());
-          const std::string key = "fin:" + g.key_of(in.children[0]) + "|" + g.key_of(in.children[1]);
-          AggLowering::Pick p = al.get_pick(a.kind == AggKind::First, key, Gen::and_ok(s2.ok, s2.v), v, in.children[0]);
-          pick_emit(a, v, p, emit_state, emit_state ? "(partial-merge)" : "(final)");
-          break;
-        }
-        case AggKind::BitAnd: case AggKind::BitOr: case AggKind::BitXor: {
-          if (in.children.size() != 1) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects one state column");
-          Val v = g.named(g.gen(in.children[0]));
-          bit_agg(a, v, "fin:" + g.key_of(in.children[0]), "", v.ok, emit_state ? "(partial-merge)" : "(final)");
-          break;
-        }
-        default:
-          throw CometError("Final mode of aggregate (tag " + std::to_string(a.proto_tag) + ") is not supported by the MI355X native engine");
-      }
-      continue;
-    }
-    switch (a.kind) {
-      case AggKind::Count: {
-        if (in.children.empty()) throw CometError("count() without children");
-        std::string ok, vkey;
-        for (auto& c : in.children) {
-          Val v = g.gen(c);
-          ok = Gen::and_ok(ok, v.ok);
-          vkey += g.key_of(c) + ",";
-        }
-        PrimSlot s = al.get(Prim::Cnt, vkey, fkey, guarded(ok), "");
-        OutCol oc; oc.type = DType::of(TypeId::Int64); oc.nullable = false;
-        d.out_cols.push_back(oc);
-        fin += "    ((i64*)" + out_val(out_j) + ")" + ROW + " = (i64)acc[" + std::to_string(s.word) + "];\n";
-        out_j++;
-        ex << "  agg: count -> Int64\n";
-        break;
-      }
-      case AggKind::Sum: case AggKind::Avg: {
-        if (in.children.size() != 1) throw CometError("sum/avg expects one child");
-        Val v = g.named(g.gen(in.children[0]));
-        std::string vkey = g.key_of(in.children[0]);
-        const bool is_avg = a.kind == AggKind::Avg;
-        const DType& rt = a.dtype;
-        const std::string cond = guarded(v.ok);
-        if (rt.id == TypeId::Decimal) {
-          if (v.t.id != TypeId::Decimal) throw CometError("decimal sum/avg over non-decimal input " + v.t.str());
-          const DType st = is_avg ? a.sum_dtype : rt;   // accumulation type
-          if (st.id != TypeId::Decimal) throw CometError("Invalid data type for SumDecimal");
-          if (st.scale != v.t.scale) throw CometError("decimal sum/avg: input scale differs from sum scale");
-          const u128 bound = pow10_u128(st.precision) - 1;
-          // Appendix C.1: no prefix can overflow while rows × max|v| ≤ 10^p − 1
-          u128 vmax = v.maxabs == 0 ? 1 : v.maxabs;
-          u128 safe_rows = vmax == kUnbounded ? 0 : bound / vmax;
-          const bool dynamic = safe_rows < ((u128)1 << 33);  // Spark sizes sum types for 10^10 rows (p+10)
-          if (!dynamic) {
-            long long sr = safe_rows > (u128)0x7fffffffffffffffll ? 0x7fffffffffffffffll : (long long)safe_rows;
-            if (max_rows_exact == 0 || sr < max_rows_exact) max_rows_exact = sr;
-          }
-          std::string val128 = v.rep == Rep::I128 ? v.v : "(i128)" + v.v;
-          PrimSlot cnt = al.get(Prim::Cnt, vkey, fkey, cond, "");
-          PrimSlot sum, amax{}, sflags{};
-          if (!dynamic) {
-            sum = al.get(Prim::Sum128, vkey, fkey, cond, val128, v.maxabs);
-          } else {
-            sum = al.get(Prim::Sum192, vkey, fkey, cond, val128, v.maxabs);
-            amax = al.get(Prim::AMaxHi, vkey, fkey, cond, val128);
-            sflags = al.get(Prim::SignFlags, vkey, fkey, cond, val128);
-          }
-          std::string W = std::to_string(sum.word), W1 = std::to_string(sum.word + 1), C = std::to_string(cnt.word);
-          fin += "    {\n      i128 total = comet::mk128(acc[" + W1 + "], acc[" + W + "]);\n      bool ovf = false;\n";
-          if (dynamic) {
-            auto kw = [&](const PrimSlot& ps) {
-              return ps.kernel_level ? "((const u64*)prm.out[" + std::to_string(kOutErr) + "])[2 + " + std::to_string(ps.word) + "]"
-                                     : "acc[" + std::to_string(ps.word) + "]";
-            };
-            fin += "      comet::sum_overflow_decide(acc + " + W + ", " + kw(amax) + ", " + kw(sflags) + ", acc[" + C + "], " + lit_u128(bound) +
-                   ", ovf, (unsigned int*)prm.out[" + std::to_string(kOutErr) + "]);\n";
-            g.uses_err = true;
-            // ANSI: an overflowing decimal SUM fails the query instead of turning NULL (sum_decimal.rs:211-215, 427-431).  An average only notes the
-            // overflow in its state here (avg_decimal.rs:268-300, 483-503) and raises when the states are merged or evaluated (:366-380, 576-580, 610-616)
-            if (a.eval_mode == EvalMode::Ansi && !is_avg) note_agg_ctx(0, a);
-            if (a.eval_mode == EvalMode::Ansi && !is_avg)
-              fin += "      if (ovf) atomicOr((unsigned int*)prm.out[" + std::to_string(kOutErr) + "], 65536u);\n";
-          }
-          if (!is_avg) {
-            // SumDecimal state (sum_decimal.rs:281-295, :526-538): (sum | NULL if overflowed, is_empty)
-            fin += "      bool empty = acc[" + C + "] == 0;\n";
-            fin += "      ((i128*)" + out_val(out_j) + ")" + ROW + " = ovf ? (i128)0 : total;\n";
-            fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = ovf ? 0 : 1;\n";
-            fin += "      ((u8*)" + out_val(out_j + 1) + ")" + ROW + " = empty ? 1 : 0;\n    }\n";
-            OutCol s0; s0.type = st; s0.nullable = true;
-            OutCol s1; s1.type = DType::of(TypeId::Bool); s1.nullable = false;
-            d.out_cols.push_back(s0);
-            d.out_cols.push_back(s1);
-            out_j += 2;
-            ex << "  agg: sum_decimal -> (" << st.str() << ", is_empty)\n";
-          } else {
-            if (grouped) {
-              // AvgDecimalGroupsAccumulator::state (avg_decimal.rs:638-653): sum and count share the is_not_null mask
-              fin += "      ((i128*)" + out_val(out_j) + ")" + ROW + " = ovf ? (i128)0 : total;\n";
-              fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = ovf ? 0 : 1;\n";
-              fin += "      ((i64*)" + out_val(out_j + 1) + ")" + ROW + " = ovf ? 0 : (i64)acc[" + C + "];\n";
-              fin += "      ((u8*)" + out_ok(out_j + 1) + ")" + ROW + " = ovf ? 0 : 1;\n    }\n";
-            } else {
-              // AvgDecimalAccumulator::state (avg_decimal.rs:283-288): sum = None until the first value
-              fin += "      bool none = acc[" + C + "] == 0 || ovf;\n";
-              fin += "      ((i128*)" + out_val(out_j) + ")" + ROW + " = none ? (i128)0 : total;\n";
-              fin += "      ((u8*)" + out_ok(out_j) + ")" + ROW + " = none ? 0 : 1;\n";
-              fin += "      ((i64*)" + out_val(out_j + 1) + ")" + ROW + " = (i64)acc[" + C + "];\n";
-              fin += "      ((u8*)" + out_ok(out_j + 1) + ")" + ROW + " = 1;\n    }\n";
-            }
-            OutCol s0; s0.type = st; s0.nullable = true;
-            OutCol s1; s1.type = DType::of(TypeId::Int64); s1.nullable = true;
-            d.out_cols.push_back(s0);
-            d.out_cols.push_back(s1);
-            out_j += 2;
-            ex << "  agg: avg_decimal -> (" << st.str() << ", count)\n";
-          }
-        } else if (!is_avg && rt.is_integer()) {
-          // SumInteger LEGACY (sum_int.rs:117-160, :403-475): wrapping i64, NULL until a non-null value arrives
-          if (!v.t.is_integer()) throw CometError("integer sum over " + v.t.str());
-          if (a.eval_mode != EvalMode::Legacy) throw CometError("ANSI/TRY integer sum is not supported in the GPU pipeline yet");
-          PrimSlot cnt = al.get(Prim::Cnt, vkey, fkey, cond, "");
-          PrimSlot sum = al.get(Prim::SumI64, vkey, fkey, cond, v.v, v.maxabs);
-          fin += "    ((i64*)" + out_val(out_j) + ")" + ROW + " = acc[" + std::to_string(cnt.word) + "] ? (i64)acc[" + std::to_string(sum.word) + "] : 0;\n";
-          fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = acc[" + std::to_string(cnt.word) + "] ? 1 : 0;\n";
-          OutCol s0; s0.type = DType::of(TypeId::Int64); s0.nullable = true;
-          d.out_cols.push_back(s0);
-          out_j++;
-          ex << "  agg: sum_int -> Int64\n";
-        } else {
-          // float sum (DataFusion sum_udaf over Float64, planner.rs:2628-2634) / Avg (avg.rs): child cast to Float64
-          if (!(v.rep == Rep::F64 || v.rep == Rep::F32 || v.rep == Rep::I32 || v.rep == Rep::I64))
-            throw CometError("float sum/avg over " + v.t.str() + " is not supported in the GPU pipeline yet");
-          PrimSlot cnt = al.get(Prim::Cnt, vkey, fkey, cond, "");
-          const AggLowering::FSum fsum = al.get_fsum("f64:" + vkey, fkey, cond, v.v);
-          const std::string SUMX = al.fread(fsum), C = std::to_string(cnt.word);
-          if (is_avg) {
-            // AvgAccumulator::state (avg.rs:139-144): ungrouped sum is Some once any batch arrived; grouped never NULL
-            fin += "    ((double*)" + out_val(out_j) + ")" + ROW + " = " + SUMX + ";\n";
-            fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = " + (grouped ? std::string("1") : "acc[" + rowcnt_word + "] ? 1 : 0") + ";\n";
-            fin += "    ((i64*)" + out_val(out_j + 1) + ")" + ROW + " = (i64)acc[" + C + "];\n";
-            fin += "    ((u8*)" + out_ok(out_j + 1) + ")" + ROW + " = 1;\n";
-            OutCol s0; s0.type = DType::of(TypeId::Double); s0.nullable = true;
-            OutCol s1; s1.type = DType::of(TypeId::Int64); s1.nullable = true;
-            d.out_cols.push_back(s0);
-            d.out_cols.push_back(s1);
-            out_j += 2;
-            ex << "  agg: avg_f64 -> (Float64, count)\n";
-          } else {
-            fin += "    ((double*)" + out_val(out_j) + ")" + ROW + " = " + SUMX + ";\n";
-            fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = acc[" + C + "] ? 1 : 0;\n";
-            OutCol s0; s0.type = DType::of(TypeId::Double); s0.nullable = true;
-            d.out_cols.push_back(s0);
-            out_j++;
-            ex << "  agg: sum_f64 -> Float64\n";
-          }
-        }
-        break;
-      }
-      case AggKind::Min: case AggKind::Max: {
-        if (in.children.size() != 1) throw CometError("min/max expects one child");
-        Val v = g.named(g.gen(in.children[0]));
-        std::string vkey = g.key_of(in.children[0]);
-        const bool mn = a.kind == AggKind::Min;
-        if (!(v.t == a.dtype)) throw CometError("min/max with cast is not supported in the GPU pipeline yet");
-        const std::string cond = guarded(v.ok);
-        PrimSlot cnt = al.get(Prim::Cnt, vkey, fkey, cond, "");
-        PrimSlot s;
-        std::string rd;
-        const char* st = store_ctype(v.t);
-        if (v.rep == Rep::I32 || v.rep == Rep::I64) {
-          s = al.get(mn ? Prim::MinI64 : Prim::MaxI64, vkey, fkey, cond, v.v);
-          rd = v.t.id == TypeId::Decimal ? "(i128)(i64)acc[" + std::to_string(s.word) + "]" : std::string("(") + st + ")(i64)acc[" + std::to_string(s.word) + "]";
-        } else if (v.rep == Rep::I128) {
-          s = al.get(mn ? Prim::MinI128 : Prim::MaxI128, vkey, fkey, cond, v.v);
-          rd = "comet::mk128(acc[" + std::to_string(s.word + 1) + "], acc[" + std::to_string(s.word) + "])";
-        } else if (v.rep == Rep::F64 || v.rep == Rep::F32) {
-          s = al.get(mn ? Prim::MinF64 : Prim::MaxF64, vkey, fkey, cond, v.v);
-          rd = std::string("(") + st + ")__longlong_as_double((i64)acc[" + std::to_string(s.word) + "])";
-        } else {
-          throw CometError("min/max over " + v.t.str() + " is not supported in the GPU pipeline yet");
-        }
-        std::string C = std::to_string(cnt.word);
-        fin += "    ((" + std::string(st) + "*)" + out_val(out_j) + ")" + ROW + " = acc[" + C + "] ? " + rd + " : (" + st + ")0;\n";
-        fin += "    ((u8*)" + out_ok(out_j) + ")" + ROW + " = acc[" + C + "] ? 1 : 0;\n";
-        OutCol s0; s0.type = v.t; s0.nullable = true;
-        d.out_cols.push_back(s0);
-        out_j++;
-        ex << "  agg: " << (mn ? "min" : "max") << " -> " << v.t.str() << "\n";
-        break;
-      }
-      case AggKind::Variance: case AggKind::Stddev: case AggKind::Covariance: case AggKind::Correlation: {
-        // update_batch (variance.rs / covariance.rs / correlation.rs): rows where every child is non-NULL (and the FILTER holds) count.  The
-        // sums are keyed like avg's — "f64:" + the value's key — so avg(x), var_samp(x) and stddev_samp(x) over one x and filter share Σx and
-        // the count; a pair's sums also carry the other child's validity in their key
-        stat_check(a, in.children.size(), false);
-        const bool two = a.kind == AggKind::Covariance || a.kind == AggKind::Correlation;
-        Val x = g.named(g.gen(in.children[0]));
-        stat_f64(a, x, two ? "first child" : "child");
-        Val y = x;
-        if (two) {
-          y = g.named(g.gen(in.children[1]));
-          stat_f64(a, y, "second child");
-        }
-        const std::string kx = g.key_of(in.children[0]), ky = two ? g.key_of(in.children[1]) : kx;
-        const std::string cond = guarded(two ? Gen::and_ok(x.ok, y.ok) : x.ok);
-        const std::string vx = two && !y.ok.empty() ? kx + "|valid:" + ky : kx, vy = two && !x.ok.empty() ? ky + "|valid:" + kx : ky;
-        auto sq = [](const std::string& u, const std::string& v) {
-          return std::vector<std::string>{"comet::fp_mul(" + u + ", " + v + ")", "comet::two_prod_lo(" + u + ", " + v + ")"};
-        };
-        StatSums ss;
-        ss.n = al.get(Prim::Cnt, vx, fkey, cond, "");
-        ss.sx = al.get_fsum("f64:" + vx, fkey, cond, x.v);
-        if (two) ss.sy = al.get_fsum("f64:" + vy, fkey, cond, y.v);
-        if (a.kind != AggKind::Covariance) ss.sxx = al.get_fsum("f64sq:" + vx, fkey, cond, sq(x.v, x.v));
-        if (a.kind == AggKind::Correlation) ss.syy = al.get_fsum("f64sq:" + vy, fkey, cond, sq(y.v, y.v));
-        if (two) ss.sxy = al.get_fsum("f64xy:" + kx + "," + ky, fkey, cond, sq(x.v, y.v));
-        stat_emit(a, ss, true, "");
-        break;
-      }
-      case AggKind::First: case AggKind::Last: {
-        // update_batch: the first (last) row that passes the FILTER — with ignore_nulls, the first (last) such row whose value is not NULL
-        if (in.children.size() != 1) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects one child");
-        pick_check(a, in.children[0]);
-        Val v = g.named(g.gen(in.children[0]));
-        pick_check_val(a, v);
-        const std::string key = g.key_of(in.children[0]) + "|" + fkey + (a.ignore_nulls ? "|nn" : "");
-        AggLowering::Pick p = al.get_pick(a.kind == AggKind::First, key, guarded(a.ignore_nulls ? v.ok : std::string()), v, in.children[0]);
-        pick_emit(a, v, p, true, "");
-        break;
-      }
-      case AggKind::BitAnd: case AggKind::BitOr: case AggKind::BitXor: {
-        if (in.children.size() != 1) throw CometError(std::string(order_bit_agg_name(a.kind)) + " expects one child");
-        Val v = g.named(g.gen(in.children[0]));
-        bit_agg(a, v, g.key_of(in.children[0]), fkey, guarded(v.ok), "");
-        break;
-      }
-      default:
-        throw CometError("Aggregate function (tag " + std::to_string(a.proto_tag) + ") is not supported by the MI355X native engine");
-    }
+    const int j = add_out(v.t, true);
+    put(j, st, acc(cnt) + " ? (" + st + ")(i64)" + acc(s) + " : (" + st + ")0");
+    put_ok(j, acc(cnt) + " ? 1 : 0");
+    explain(c.label(), std::string(name) + " -> " + v.t.str());
   }
-  if (d.out_cols.size() * 2 + kOutFirstCol > COMET_MAX_OUT) throw CometError("too many aggregate state columns for one GPU pipeline");
-  d.NW = al.nw;
-  d.fix_sums = al.fix_sums;
-  d.NK = nk;
-  d.R = grouped ? 2 : 4;
-  if (const char* e = getenv("COMET_GEN_R")) d.R = std::max(1, std::min(8, atoi(e)));
-  d.max_rows_exact = max_rows_exact;
-  d.in_used = g.in_used;
-  src << "struct P {\n  static constexpr int R = " << d.R << ";\n  static constexpr int NW = " << d.NW << ";\n";
-  src << "  static __device__ __forceinline__ void init(u64* a) {\n" << al.init_code << "  }\n";
-  src << "  static __device__ __forceinline__ void combine(u64* a, const u64* b) {\n" << al.combine_code << "  }\n";
-  if (!grouped) {
-    const std::string rowinit = "    bool k[R]; i64 idx[R];\n    _Pragma(\"unroll\") for (int r = 0; r < R; r++) { idx[r] = base + (i64)r * comet::kBlock + threadIdx.x; k[r] = idx[r] < n; }\n";
-    src << "  static constexpr bool PIPELINED = " << (g.pipelined ? "true" : "false") << ";\n";
-    if (g.pipelined) {
-      src << "  struct L {\n" << g.ldecls << "  };\n";
-      src << "  static __device__ __forceinline__ void tile_load(const CometKParams& prm, i64 base, i64 n, L& ld) {\n" << rowinit << g.prefetch_body() << "  }\n";
-      src << "  static __device__ __forceinline__ void tile(const CometKParams& prm, i64 base, i64 n, L& ld, u64* acc) {\n" << rowinit << g.laliases
-          << g.decls << g.body("", true) << "  }\n";
-    } else {
-      src << "  static __device__ __forceinline__ void tile(const CometKParams& prm, i64 base, i64 n, u64* acc) {\n" << rowinit << g.decls << g.body() << "  }\n";
+
+  void lower_aggregates(const std::vector<AggIn>& agg_ins) {
+    rowcnt = al.get(Prim::RowCnt, "*", "", "", "");
+    for (auto& in : agg_ins) {
+      Call c{*in.a, in.children, in.mode == AggMode::Final || in.mode == AggMode::PartialMerge, in.mode != AggMode::Final, "", ""};
+      if (in.filter) {
+        // FILTER (WHERE …): row contributes only if the filter is TRUE and valid (sum_decimal.rs:452-458)
+        Val f = g.named(g.gen(in.filter));
+        c.fkey = g.key_of(in.filter);
+        c.guard = Gen::and_ok(f.ok, f.v);
+      }
+      switch (in.a->kind) {
+        case AggKind::Count: count(c); break;
+        case AggKind::Sum: case AggKind::Avg: sum_avg(c); break;
+        case AggKind::Min: case AggKind::Max: min_max(c); break;
+        case AggKind::Variance: case AggKind::Stddev: case AggKind::Covariance: case AggKind::Correlation: stat(c); break;
+        case AggKind::First: case AggKind::Last: first_last(c); break;
+        case AggKind::BitAnd: case AggKind::BitOr: case AggKind::BitXor: bitwise(c); break;
+        default:
+          throw CometError(std::string(c.merging ? "Final mode of aggregate (tag " : "Aggregate function (tag ") + std::to_string(in.a->proto_tag) + ") is not supported by the MI355X native engine");
+      }
     }
+    if (d.out_cols.size() * 2 + kOutFirstCol > COMET_MAX_OUT) throw CometError("too many aggregate state columns for one GPU pipeline");
+  }
+
+  // ---- struct P and the kernels ----
+  // the two halves of a pipelined tile: tile_load prefetches the first stage's columns of the next tile, `name` computes this one.  `params`: what the
+  // compute half takes behind the loaded columns; `tail`: what follows its row body
+  void emit_tile(std::ostringstream& src, const char* name, const char* params, const std::string& tail) {
+    src << "  static constexpr bool PIPELINED = true;\n";
+    src << "  struct L {\n" << g.ldecls << "  };\n";
+    src << "  static __device__ __forceinline__ void tile_load(const CometKParams& prm, i64 base, i64 n, L& ld) {\n" << kRowInit << g.prefetch_body() << "  }\n";
+    src << "  static __device__ __forceinline__ void " << name << "(const CometKParams& prm, i64 base, i64 n, L& ld, " << params << ") {\n" << kRowInit << g.laliases
+        << g.decls << g.body("", true) << tail;
+  }
+
+  void emit_ungrouped(std::ostringstream& src) {
+    emit_tile(src, "tile", "u64* acc", "  }\n");
     src << "  static __device__ __forceinline__ void kexport(const CometKParams& prm, const u64* acc) {\n"
         << "    unsigned long long* aux = (unsigned long long*)prm.out[" << kOutErr << "] + 2; (void)aux;\n" << al.kexport_code << "  }\n";
     src << "  static __device__ __forceinline__ void finalize(const CometKParams& prm, const u64* acc) {\n" << fin << "  }\n};\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_agg(const CometKParams prm) { comet::agg_nogroup_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_agg_final(const CometKParams prm) { comet::agg_nogroup_final_body<P>(prm); }\n";
     d.kernels = {"k_agg", "k_agg_final"};
-  } else {
+  }
+
+  // P::pick: per first / last, the child expression at the row whose ordinal won — if that row is one of this launch's (comet_device.hpp "first / last")
+  void emit_pick(std::ostringstream& src, const GenMaker& make_gen) {
+    std::string calls;
+    for (size_t i = 0; i < al.pick_reqs.size(); i++) {
+      const auto& rq = al.pick_reqs[i];
+      Gen gp = make_gen();
+      Val pv = gp.named(gp.gen(rq.child));
+      std::string lo, hi, ok = pv.ok.empty() ? std::string("1ull") : "(" + pv.ok + ") ? 1ull : 0ull";
+      AggLowering::value_words(pv, pv.v, lo, hi);
+      for (std::string* e : {&lo, &hi, &ok})
+        for (size_t p0 = e->find("[r]"); p0 != std::string::npos; p0 = e->find("[r]")) e->replace(p0, 3, "[0]");
+      src << "  static __device__ __forceinline__ void pick" << i << "(const CometKParams& prm, i64 prow, u64* acc) {\n    bool k[R] = {true}; i64 idx[R] = {prow};\n"
+          << gp.decls << gp.body() << "    acc[" << rq.p.val << "] = " << lo << ";";
+      if (!hi.empty()) src << " acc[" << rq.p.val + 1 << "] = " << hi << ";";
+      src << " acc[" << rq.p.ok << "] = " << ok << ";\n  }\n";
+      calls += "    { const i64 o_ = (i64)acc[" + std::to_string(rq.p.ord) + "]; if (o_ >= b_ && o_ - b_ < prm.n) pick" + std::to_string(i) + "(prm, o_ - b_, acc); }\n";
+      for (size_t c = 0; c < d.in_used.size() && c < gp.in_used.size(); c++) d.in_used[c] = d.in_used[c] || gp.in_used[c];
+    }
+    src << "  static __device__ __forceinline__ void pick(const CometKParams& prm, u64* acc) {\n    const i64 b_ = prm.iarg[" << kRowBaseArg << "];\n" << calls << "  }\n";
+  }
+
+  void emit_grouped(std::ostringstream& src, const GenMaker& make_gen, bool materialised_source) {
     // LDS budget: private copies [GC][NPW][COPIES] + table slots ≈ 20 KiB per block (8 blocks = 32 waves per CU)
     d.NPW = al.npw;
     const int copies = 32;
     int gc = 8;
     while (gc > 1 && gc * al.npw * copies * 8 > 10 * 1024) gc >>= 1;
-    if (const char* e = getenv("COMET_GEN_GC")) gc = std::max(1, std::min(16, atoi(e)));
     const int slot_bytes = 8 + 8 * (d.NK + al.npw + 1);
     int cap = 1024;
     while (cap > 16 && cap * slot_bytes > 10 * 1024) cap >>= 1;
@@ -4372,52 +4223,22 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
     emit_switch("int kop(int k)", al.kops, "comet::", "comet::G_OR64");
     src << "  static __device__ __forceinline__ void kinit(u64* kacc) { for (int k = 0; k < (NKW > 0 ? NKW : 1); k++) kacc[k] = 0; }\n";
     src << "  static __device__ __forceinline__ void fold(const u64* pw, u64* val) {\n" << al.fold_code << "  }\n";
-    const std::string rowinit = "    bool k[R]; i64 idx[R];\n    _Pragma(\"unroll\") for (int r = 0; r < R; r++) { idx[r] = base + (i64)r * comet::kBlock + threadIdx.x; k[r] = idx[r] < n; }\n";
     const std::string update = "    _Pragma(\"unroll\") for (int r = 0; r < R; r++) {\n      if (k[r]) {\n        u64 key[NK]; u64 pv[NPW];\n" + key_code + al.pv_code +
                                al.kfeed_code + "        comet::group_update<P>(grp, true, key, pv);\n      }\n    }\n  }\n";
-    src << "  static constexpr bool PIPELINED = " << (g.pipelined ? "true" : "false") << ";\n";
-    if (g.pipelined) {
-      src << "  struct L {\n" << g.ldecls << "  };\n";
-      src << "  static __device__ __forceinline__ void tile_load(const CometKParams& prm, i64 base, i64 n, L& ld) {\n" << rowinit << g.prefetch_body() << "  }\n";
-      src << "  static __device__ __forceinline__ void tile_grouped(const CometKParams& prm, i64 base, i64 n, L& ld, const comet::GroupCtx<P>& grp, u64* kacc) {\n"
-          << rowinit << g.laliases << g.decls << g.body("", true) << update;
-    } else {
-      src << "  static __device__ __forceinline__ void tile_grouped(const CometKParams& prm, i64 base, i64 n, const comet::GroupCtx<P>& grp, u64* kacc) {\n"
-          << rowinit << g.decls << g.body() << update;
-    }
-    if (!al.pick_reqs.empty()) {
-      // P::pick: per first / last, the child expression at the row whose ordinal won — if that row is one of this launch's (comet_device.hpp "first / last")
-      std::string calls;
-      for (size_t i = 0; i < al.pick_reqs.size(); i++) {
-        const auto& rq = al.pick_reqs[i];
-        Gen gp(d.in_types, in_has_validity_all);
-        if (str_fixed_len) gp.str_fixed_len = *str_fixed_len;
-        Val pv = gp.named(gp.gen(rq.child));
-        std::string lo, hi, ok = pv.ok.empty() ? std::string("1ull") : "(" + pv.ok + ") ? 1ull : 0ull";
-        AggLowering::value_words(pv, pv.v, lo, hi);
-        for (std::string* e : {&lo, &hi, &ok})
-          for (size_t p0 = e->find("[r]"); p0 != std::string::npos; p0 = e->find("[r]")) e->replace(p0, 3, "[0]");
-        src << "  static __device__ __forceinline__ void pick" << i << "(const CometKParams& prm, i64 prow, u64* acc) {\n    bool k[R] = {true}; i64 idx[R] = {prow};\n"
-            << gp.decls << gp.body() << "    acc[" << rq.p.val << "] = " << lo << ";";
-        if (!hi.empty()) src << " acc[" << rq.p.val + 1 << "] = " << hi << ";";
-        src << " acc[" << rq.p.ok << "] = " << ok << ";\n  }\n";
-        calls += "    { const i64 o_ = (i64)acc[" + std::to_string(rq.p.ord) + "]; if (o_ >= b_ && o_ - b_ < prm.n) pick" + std::to_string(i) + "(prm, o_ - b_, acc); }\n";
-        for (size_t c = 0; c < d.in_used.size() && c < gp.in_used.size(); c++) d.in_used[c] = d.in_used[c] || gp.in_used[c];
-      }
-      src << "  static __device__ __forceinline__ void pick(const CometKParams& prm, u64* acc) {\n    const i64 b_ = prm.iarg[" << kRowBaseArg << "];\n" << calls << "  }\n";
-    }
+    emit_tile(src, "tile_grouped", "const comet::GroupCtx<P>& grp, u64* kacc", update);
+    const bool picks = !al.pick_reqs.empty();
+    if (picks) emit_pick(src, make_gen);
     src << "  static __device__ __forceinline__ void emit_group(const CometKParams& prm, const u64* key, const u64* acc, i64 pos) {\n"
         << key_emit << fin << "  }\n};\n";
-    if (!al.pick_reqs.empty())
-      src << "extern \"C\" __global__ __launch_bounds__(256) void k_gpick(const CometKParams prm) { comet::agg_grouped_pick_body<P>(prm); }\n";
+    if (picks) src << "extern \"C\" __global__ __launch_bounds__(256) void k_gpick(const CometKParams prm) { comet::agg_grouped_pick_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256, COMET_WAVES_GAGG) void k_gagg(const CometKParams prm) { comet::agg_grouped_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_gemit(const CometKParams prm) { comet::agg_grouped_emit_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_grehash(const CometKParams prm) { comet::agg_grouped_rehash_body<P>(prm); }\n";
-    src << "extern \"C\" __global__ __launch_bounds__(256) void k_pack(const CometKParams prm) { comet::pack_validity_body((const u8*)prm.out[0], (u8*)prm.out[1], prm.n); }\n";
+    src << kPackKernel;
     // (only where the path can apply — a merging aggregate, or one over a materialised source such as a join's output: a Partial aggregate over a Scan sees chunks
     // of a stream, and its three extra kernels would only lengthen the cold compile: SF100 Q1's plan 497 → 680 ms)
     // (… a Partial aggregate keyed by Utf8 columns is "materialised" only so that long strings can be swapped for row indices — TPC-H Q1's shape: four groups)
-    const bool part_kernels = d.merges_states || (source_types != nullptr && d.str_key_cols.empty());
+    const bool part_kernels = d.merges_states || (materialised_source && d.str_key_cols.empty());
     if (part_kernels) {
       // a grouped aggregate over one chunk may run partitioned (comet_device.hpp template C''): count / scatter passes over the rows, an LDS merge + emit per partition
       src << "extern \"C\" __global__ __launch_bounds__(256) void k_gphist(const CometKParams prm) { comet::agg_part_pass_body<P, 1>(prm); }\n";
@@ -4425,12 +4246,80 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
       src << "extern \"C\" __global__ __launch_bounds__(256) void k_gpmerge(const CometKParams prm) { comet::agg_part_merge_body<P>(prm); }\n";
     }
     d.kernels = {"k_gagg", "k_gemit", "k_grehash", "k_pack"};
-    if (!al.pick_reqs.empty()) d.kernels.push_back("k_gpick");
+    if (picks) d.kernels.push_back("k_gpick");
     if (part_kernels) {
       d.kernels.push_back("k_gphist");
       d.kernels.push_back("k_gpscat");
       d.kernels.push_back("k_gpmerge");
     }
+  }
+
+  void finish(std::ostringstream& src, const GenMaker& make_gen, bool materialised_source) {
+    d.NW = al.nw;
+    d.fix_sums = al.fix_sums;
+    d.NK = nk;
+    d.R = grouped ? 2 : 4;
+    d.max_rows_exact = max_rows_exact;
+    d.in_used = g.in_used;
+    src << "struct P {\n  static constexpr int R = " << d.R << ";\n  static constexpr int NW = " << d.NW << ";\n";
+    src << "  static __device__ __forceinline__ void init(u64* a) {\n" << al.init_code << "  }\n";
+    src << "  static __device__ __forceinline__ void combine(u64* a, const u64* b) {\n" << al.combine_code << "  }\n";
+    if (grouped) emit_grouped(src, make_gen, materialised_source);
+    else emit_ungrouped(src);
+  }
+};
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// generate_pipeline
+// ---------------------------------------------------------------------------------------------
+PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in_has_validity, const std::vector<DType>* source_types,
+                               const std::vector<int>* str_fixed_len, const std::vector<int>* dict_id_col) {
+  // 1. the chain root → leaf
+  const std::vector<const Operator*> chain = collect_chain(root, source_types != nullptr);
+  const Operator& scan = *chain.back();
+  PipelineDesc d;
+  SiteScope site_scope(d);
+  d.in_types = source_types ? *source_types : scan.scan_fields;
+  for (auto* op : chain) d.op_names.push_back(op_name(op->proto_tag));
+  if (in_has_validity.size() != d.in_types.size()) throw CometError("internal: validity mask arity mismatch");
+  if (d.in_types.size() > COMET_MAX_IN) throw CometError("too many scan columns for one GPU pipeline");
+
+  // 2. fold leaf → root; the derived columns the fold noted follow the source's
+  const std::vector<ExprP> source_cols = bound_columns(d.in_types);
+  SourceColsScope source_cols_scope(&source_cols);
+  DerivedScope derived_scope(&d.derived);
+  const FoldedChain f = fold_pipeline(chain, source_cols, d);
+  const std::vector<bool> valid_all = append_derived_columns(d, in_has_validity, f.agg != nullptr);
+  const GenMaker make_gen{d.in_types, valid_all, str_fixed_len};
+  Gen g = make_gen();
+  g.pipelined = f.agg != nullptr;   // aggregate sinks prefetch tile t+1's first-stage columns while computing tile t
+  for (auto& p : f.preds) g.add_predicate(p);
+
+  std::ostringstream src;
+  src << "// generated by datafusion-comet_amd codegen — fused pipeline: ";
+  for (auto& n : d.op_names) src << n << " <- ";
+  src << "input\n";
+  // An aggregate sink reads every column byte once and keeps nothing but its accumulators: its column loads are non-temporal (streaming)
+  // loads — SF100 Q1's k_gagg 7.24-7.58 -> 7.01-7.13 ms in three alternating pairs on one box.  Join probes keep ordinary loads (their
+  // bitmap and build rows want the L2; both of SF100 Q3's got ~3 % slower with streaming loads).
+  if (f.agg) src << "#ifndef COMET_LD_NT\n#define COMET_LD_NT 1\n#endif\n";
+  src << "#include \"comet_device.hpp\"\nusing namespace comet;\n";
+
+  std::ostringstream ex;
+  for (auto& p : f.preds) ex << "  filter: " << explain_expr(p) << "\n";
+
+  // 3. the sink
+  if (!f.agg) {
+    Gen ge = make_gen();
+    OutputSink sink{d, ge, valid_all, ex, {}};
+    sink.finish(src, g, f.cols);
+  } else {
+    AggSink sink(d, g, !f.group_exprs.empty(), ex);
+    if (sink.grouped) sink.lower_group_keys(f.group_exprs, dict_id_col);
+    sink.lower_aggregates(f.agg_ins);
+    sink.finish(src, make_gen, source_types != nullptr);
   }
   d.source = with_optional_headers(src.str());
   d.explain = ex.str();

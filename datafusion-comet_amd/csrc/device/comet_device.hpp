@@ -2310,15 +2310,6 @@ CDEV COMET_LDS LSlot<P::NK, P::NPW>* lds_find_or_insert(const GroupCtx<P>& g, co
 template <class P>
 CDEV void group_update(const GroupCtx<P>& g, bool active, const u64* key, const u64* pv) {
   if (!active) return;
-#if defined(COMET_EXPERIMENT) && COMET_EXPERIMENT == 1
-  {  // floor measurement: keep key/pv alive, no probe, no update
-    u64 x = 0;
-    for (int k = 0; k < P::NK; k++) x ^= key[k];
-    for (int k = 0; k < P::NPW; k++) x += pv[k];
-    if (x == 0x123456789abcdefull) atomicOr(g.err, 128u);
-    return;
-  }
-#endif
   if (g.part_mode) {      // (uniform: a partition pass of template C'')
     const u32 p = (u32)__umul64hi(hash_key<P::NK>(key), (u64)g.np);
     if (g.part_mode == 1) {
