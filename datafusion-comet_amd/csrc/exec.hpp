@@ -199,6 +199,7 @@ class ExecutionContext {
   std::vector<DType> infer_schema(const Operator& op);
   DevTable materialize(const Operator& op);
   DevTable scan_parquet(const Operator& native_scan);
+  friend struct ParquetScan;         // parquet_scan.cpp: the stages of scan_parquet
   int64_t launch_fused_filter(Variant& v, CometKParams& prm, int64_t n);
   DevTable run_chain_to_device(const Operator& top, const DevTable& in);
   void extend_derived(DevTable& in, const std::vector<DerivedCol>& derived);

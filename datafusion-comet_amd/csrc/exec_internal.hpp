@@ -122,7 +122,6 @@ int plans_executing();
 
 // per-process stream / event pools (exec_memory.cpp)
 hipStream_t pool_get_stream(int dev);
-hipStream_t shared_copy_stream(int dev);      // one per device for all scans: never returned to the pool, never synchronised as a whole
 void pool_put_stream(int dev, hipStream_t s);
 hipEvent_t pool_get_event(int dev);
 void pool_put_event(int dev, hipEvent_t e);

@@ -266,20 +266,6 @@ void detail::plan_execution_begins() { g_plans_executing.fetch_add(1); }
 void detail::plan_execution_ends() { g_plans_executing.fetch_sub(1); }
 int detail::plans_executing() { return g_plans_executing.load(); }
 
-// COMET_PQ_SHARED_COPY_STREAM=1: one host → device copy stream per device for every Parquet scan of the process (the link is one FIFO whoever
-// queues the copies, and every stream with pending work wants a hardware queue: GPU_MAX_HW_QUEUES of them, and 32 queues time-slice the
-// runlist — 74 ms for a wave that takes 20).  Measured and not the default: one submission that stalls then holds every task's copies.
-hipStream_t detail::shared_copy_stream(int dev) {
-  std::lock_guard<std::mutex> lk(pools().mu);
-  static std::map<int, hipStream_t> shared;
-  auto it = shared.find(dev);
-  if (it != shared.end()) return it->second;
-  hipStream_t s;
-  HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  shared[dev] = s;
-  return s;
-}
-
 hipEvent_t detail::pool_get_event(int dev) {
   {
     std::lock_guard<std::mutex> lk(pools().mu);

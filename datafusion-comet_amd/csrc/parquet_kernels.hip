@@ -237,18 +237,7 @@ __device__ __forceinline__ i64 pq_uniform_i64(i64 v) {
   return (i64)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)((u64)v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)v));
 }
 
-// Every block decodes one CONTIGUOUS slice of the column; a wave takes 64·R consecutive rows per step (every lane R consecutive rows
-// of them), so the page and the hybrid run of a wave's first row only ever move FORWARD.
-//   * The wave keeps its current page and run — and the row / value index at which the NEXT page / run starts — in wave-uniform
-//     scalars: the common step needs no table load at all, only "am I still before the next boundary" compares.  (A PqPage / PqRun
-//     struct copy lives in scratch memory: measured, every step paid scratch round trips.)
-//   * R rows per lane would give R independent index → dictionary → store chains per lane and let a lane's bit-packed indices come out
-//     of ONE 8-byte load; measured on MI355X (profiles/r2_parquet_decode.txt) R = 4 was no faster than R = 1 — with 256 rows per wave
-//     step every second step crosses a ≤ 504-value run and sends lanes down the per-element path — so R = 1 is what runs.
-//   * Elements beyond the wave's page or run (a boundary inside the 256 rows) find their page / run by stepping forward from the wave's.
 // The value of an element is produced as a 128-bit payload whose low out_width bytes are stored.
-struct PqElem { i128 val; bool ok; };
-
 __device__ __forceinline__ i128 pq_convert(int kind, const u8* src, int width, int dec_up, u32 boolbit) {
   switch (kind) {
     case PQ_COPY4: return (i128)(u128)pq_ld32(src);
@@ -273,165 +262,12 @@ __device__ __forceinline__ i128 pq_convert(int kind, const u8* src, int width, i
   }
 }
 
-__global__ __launch_bounds__(256) void pq_decode_fixed_kernel(PqDecodeArgs a) {
-  constexpr int R = 1;                                   // consecutive rows per lane
-  constexpr i64 kTile = 256 * R;                         // rows per block and step (256 per wave)
-  const i64 per_block = (((a.n_rows + gridDim.x - 1) / gridDim.x) + kTile - 1) / kTile * kTile;
-  const i64 begin = (i64)blockIdx.x * per_block;
-  const i64 end = begin + per_block < a.n_rows ? begin + per_block : a.n_rows;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = (int)(threadIdx.x & 63u);
-  constexpr i64 kNever = 0x7fffffffffffffffll;
-  const u8* __restrict__ bytes = a.bytes;
-  const u8* __restrict__ dict = a.dict;
-  int p = -1;                                   // the wave's page …
-  i64 pg_row_start = 0, pg_values_off = 0, pg_dict_off = 0, next_page_row = -1;   // … and the first row of the page after it
-  i32 pg_encoding = 0, pg_bit_width = 0, pg_kind = 0, pg_width = 0, pg_dec_up = 0, pg_idx_first = 0, pg_idx_count = 0, pg_val_skip = 0;
-  int r = -1, run_page = -1;                    // the wave's run (dictionary pages) …
-  i64 rn_byte_off = 0;
-  i32 rn_value_start = 0, rn_is_rle = 0, next_run_val = 0;   // … and the first value index of the run after it (within the page)
-  u32 rn_rle_value = 0;
-  for (i64 base = begin; base < end; base += kTile) {
-    const i64 row0 = base + (i64)wave * (64 * R);          // first of this wave's 256 rows (wave-uniform)
-    if (row0 >= end) break;
-    if (p < 0 || row0 >= next_page_row) {
-      if (p < 0) p = pq_find_page(a.pages, a.npages, row0);
-      else
-        while (p + 1 < a.npages && a.pages[p + 1].row_start <= row0) p++;
-      const PqPage* q = a.pages + p;
-      pg_row_start = q->row_start; pg_values_off = q->values_off; pg_dict_off = q->dict_off;
-      pg_encoding = q->encoding; pg_bit_width = q->bit_width; pg_kind = q->kind; pg_width = q->width; pg_dec_up = q->dec_scale_up;
-      pg_idx_first = q->idx_run_first; pg_idx_count = q->idx_run_count; pg_val_skip = q->val_skip;
-      next_page_row = p + 1 < a.npages ? a.pages[p + 1].row_start : kNever;
-    }
-    if (pg_encoding == 1) {
-      // the run holding the wave's first value
-      const i32 v0 = (a.max_def > 0 ? (i32)(a.vidx[row0] - a.vidx[pg_row_start]) : (i32)(row0 - pg_row_start)) + pg_val_skip;
-      const int last0 = pg_idx_first + pg_idx_count - 1;
-      bool reload = false;
-      if (run_page != p) {
-        int lo = pg_idx_first, hi = last0;
-        while (lo < hi) {
-          int mid = (lo + hi + 1) >> 1;
-          if (a.idx_runs[mid].value_start <= v0) lo = mid;
-          else hi = mid - 1;
-        }
-        r = lo;
-        run_page = p;
-        reload = true;
-      } else if (v0 >= next_run_val) {
-        while (r < last0 && a.idx_runs[r + 1].value_start <= v0) r++;
-        reload = true;
-      }
-      if (reload) {
-        const PqRun* q = a.idx_runs + r;
-        rn_byte_off = q->byte_off; rn_value_start = q->value_start; rn_is_rle = q->is_rle; rn_rle_value = q->rle_value;
-        next_run_val = r < last0 ? a.idx_runs[r + 1].value_start : 0x7fffffff;
-      }
-    }
-    const i64 lrow = row0 + (i64)lane * R;                 // this lane's first row
-    // ---- phase 1: where does every element's value come from (index loads happen here) ----
-    const u8* src[R];
-    u32 boolbit[R];
-    i32 kind[R], width[R], dec_up[R];
-    bool ok[R];
-    // fast path: the lane's rows lie in the wave's page and bit-packed run and the column has no NULLs → ONE load holds all indices
-    const bool no_nulls = a.max_def == 0;
-    const i32 lv0 = (i32)(lrow - pg_row_start) + pg_val_skip;
-    const bool all_here = lrow + R <= end && lrow + R <= next_page_row;
-    const bool packed_fast = pg_encoding == 1 && no_nulls && all_here && !rn_is_rle && lv0 + R <= next_run_val && pg_bit_width * R <= 56;
-    u64 packed = 0;
-    if (packed_fast) {
-      const i64 bit = (i64)(lv0 - rn_value_start) * pg_bit_width;
-      packed = pq_ld64(bytes + rn_byte_off + (bit >> 3)) >> (bit & 7);
-    }
-#pragma unroll
-    for (int k = 0; k < R; k++) {
-      const i64 row = lrow + k;
-      ok[k] = row < end && (!a.valid_out || a.valid_out[row] != 0);
-      src[k] = nullptr;
-      boolbit[k] = 0;
-      kind[k] = pg_kind; width[k] = pg_width; dec_up[k] = pg_dec_up;
-      if (!ok[k]) continue;
-      if (packed_fast) {
-        const u32 idx = (u32)((packed >> (k * pg_bit_width)) & ((1ull << pg_bit_width) - 1));
-        src[k] = dict + pg_dict_off + (i64)idx * pg_width;
-        continue;
-      }
-      // the element's own page: the wave's, unless a page boundary falls inside this step
-      i64 l_row_start = pg_row_start, l_values_off = pg_values_off, l_dict_off = pg_dict_off;
-      i32 l_encoding = pg_encoding, l_bit_width = pg_bit_width, l_idx_first = pg_idx_first, l_idx_count = pg_idx_count, l_val_skip = pg_val_skip;
-      const bool here = row < next_page_row;
-      if (!here) {
-        int qi = p;
-        while (qi + 1 < a.npages && a.pages[qi + 1].row_start <= row) qi++;
-        const PqPage* q = a.pages + qi;
-        l_row_start = q->row_start; l_values_off = q->values_off; l_dict_off = q->dict_off;
-        l_encoding = q->encoding; l_bit_width = q->bit_width; kind[k] = q->kind; width[k] = q->width; dec_up[k] = q->dec_scale_up;
-        l_idx_first = q->idx_run_first; l_idx_count = q->idx_run_count; l_val_skip = q->val_skip;
-      }
-      const i32 v = (a.max_def > 0 ? (i32)(a.vidx[row] - a.vidx[l_row_start]) : (i32)(row - l_row_start)) + l_val_skip;
-      if (l_encoding == 1) {
-        u32 idx;
-        if (here && v < next_run_val) {            // v ≥ rn_value_start holds: v ≥ v0 ≥ the run's first value
-          if (rn_is_rle) {
-            idx = rn_rle_value;
-          } else {
-            const int bw = l_bit_width;
-            const i64 bit = (i64)(v - rn_value_start) * bw;
-            const u64 w = pq_ld64(bytes + rn_byte_off + (bit >> 3));   // bw <= 32 → the value fits in 5 bytes; staging is padded
-            idx = (u32)((w >> (bit & 7)) & ((bw >= 32) ? 0xffffffffull : ((1ull << bw) - 1)));
-          }
-        } else if (here) {
-          // a later run of the wave's page: step forward from the wave's run
-          int rr = r;
-          const int last = l_idx_first + l_idx_count - 1;
-          while (rr < last && a.idx_runs[rr + 1].value_start <= v) rr++;
-          const PqRun* q = a.idx_runs + rr;
-          if (q->is_rle) {
-            idx = q->rle_value;
-          } else {
-            const int bw = l_bit_width;
-            const i64 bit = (i64)(v - q->value_start) * bw;
-            const u64 w = pq_ld64(bytes + q->byte_off + (bit >> 3));
-            idx = (u32)((w >> (bit & 7)) & ((bw >= 32) ? 0xffffffffull : ((1ull << bw) - 1)));
-          }
-        } else {
-          idx = pq_hybrid_value(a.idx_runs, l_idx_first, l_idx_count, bytes, l_bit_width, v);
-        }
-        src[k] = dict + l_dict_off + (i64)idx * width[k];
-      } else if (kind[k] == PQ_BOOL) {
-        boolbit[k] = (bytes[l_values_off + (v >> 3)] >> (v & 7)) & 1;
-      } else {
-        src[k] = bytes + l_values_off + (i64)v * width[k];
-      }
-    }
-    // ---- phase 2: the values (dictionary / page loads), all issued before any store ----
-    i128 val[R];
-#pragma unroll
-    for (int k = 0; k < R; k++) val[k] = ok[k] ? pq_convert(kind[k], src[k], width[k], dec_up[k], boolbit[k]) : (i128)0;   // NULL rows store zeros
-    // ---- phase 3: stores (a lane's four values are contiguous) ----
-#pragma unroll
-    for (int k = 0; k < R; k++) {
-      const i64 row = lrow + k;
-      if (row >= end) continue;
-      switch (a.out_width) {
-        case 1: ((u8*)a.values_out)[row] = (u8)val[k]; break;
-        case 2: ((u16*)a.values_out)[row] = (u16)val[k]; break;
-        case 4: ((u32*)a.values_out)[row] = (u32)val[k]; break;
-        case 8: ((u64*)a.values_out)[row] = (u64)val[k]; break;
-        default: ((i128*)a.values_out)[row] = val[k]; break;
-      }
-    }
-  }
-}
-
 // 3b. values, a RUN at a time (columns without NULLs): one wave per unit of work — a bit-packed run of dictionary indices (≤ 504 values as
 // the writers emit them), an RLE run, or a 4096-value chunk of a PLAIN page.  Everything about the unit is wave-uniform (one PqRun and one
 // PqPage, loaded once through the scalar path); lane l decodes values l, l + 64, l + 128, … of the unit, eight per pass with all index and
-// dictionary loads issued before the first store, and consecutive lanes store consecutive rows.  The row-at-a-time kernel above spends a
-// dependent index → dictionary → store chain per 64 rows and drops to a per-element path at every run boundary; here there are no
-// boundaries inside a unit.
+// dictionary loads issued before the first store, and consecutive lanes store consecutive rows.  (A kernel that walked ROWS spent a
+// dependent index → dictionary → store chain per 64 rows and dropped to a per-element path at every run boundary; here there are no
+// boundaries inside a unit.)
 // (decoded columns are written once and read by a LATER kernel: streaming stores, which do not claim L2 lines the dictionary and the packed
 // indices want; COMET_PQ_STORE=plain restores ordinary stores)
 template <int OW>
@@ -789,10 +625,6 @@ __global__ __launch_bounds__(256) void pq_u32_scan_apply_kernel(const u32* in, i
 }
 __global__ __launch_bounds__(256) void pq_pack_kernel(const u8* bytes, u8* bitmap, i64 n) { pack_validity_body(bytes, bitmap, n); }
 
-static int grid_slices(i64 n) {   // contiguous slices of >= 4 tiles, enough blocks to fill 256 CUs several times over
-  i64 g = (n + 1023) / 1024;
-  return (int)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
-}
 static int grid_rows(i64 n) {
   i64 g = (n + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
@@ -800,30 +632,6 @@ static int grid_rows(i64 n) {
 static int grid_tiles(i64 n) {
   i64 g = (n + 1023) / 1024;
   return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
-// Pulls slices of pinned host memory into HBM: workgroup (x, y) moves the x-th 64 KiB piece of slice y — sixteen 16-byte loads per thread
-// in flight across PCIe, then sixteen stores.  One launch moves every slice that is ready (parquet_scan.cpp: a hipMemcpyAsync per slice
-// costs ≈ 40 µs of latency whatever its size).
-__global__ __launch_bounds__(256) void pq_upload_kernel(const PqCopyDesc* __restrict__ descs) {
-  typedef unsigned V4 __attribute__((vector_size(16)));
-  const PqCopyDesc d = descs[blockIdx.y];
-  const u64 piece = (u64)blockIdx.x << 16;
-  if (piece >= d.len) return;
-  const u64 nvec = (d.len - piece < 65536 ? d.len - piece : 65536) >> 4;
-  const V4* src = (const V4*)(d.src + piece);
-  V4* dst = (V4*)(d.dst + piece);
-  V4 v[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    const u64 i = (u64)threadIdx.x + (u64)k * 256;
-    if (i < nvec) v[k] = __builtin_nontemporal_load(src + i);
-  }
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    const u64 i = (u64)threadIdx.x + (u64)k * 256;
-    if (i < nvec) dst[i] = v[k];
-  }
 }
 
 extern "C" {
@@ -863,7 +671,6 @@ void pq_launch_decode_runs(const PqDecodeArgs* a, void* st) {
   hipLaunchKernelGGL(pq_decode_runs_kernel, blocks, 256, 0, (hipStream_t)st, *a);
 }
 void pq_launch_expand_nulls(const PqDecodeArgs* a, void* st) { hipLaunchKernelGGL(pq_expand_nulls_kernel, grid_rows(a->n_rows), 256, 0, (hipStream_t)st, *a); }
-void pq_launch_decode_fixed(const PqDecodeArgs* a, void* st) { hipLaunchKernelGGL(pq_decode_fixed_kernel, grid_slices(a->n_rows), 256, 0, (hipStream_t)st, *a); }
 void pq_launch_string_lengths(const PqDecodeArgs* a, void* st) { hipLaunchKernelGGL(pq_string_lengths_kernel, grid_rows(a->n_rows), 256, 0, (hipStream_t)st, *a); }
 void pq_launch_string_copy(const PqDecodeArgs* a, void* st) { hipLaunchKernelGGL(pq_string_copy_kernel, grid_rows(a->n_rows), 256, 0, (hipStream_t)st, *a); }
 void pq_launch_u32_scan(const uint32_t* in, int64_t n, uint64_t* tiles, int32_t* out, void* st) {
@@ -874,12 +681,5 @@ void pq_launch_u32_scan(const uint32_t* in, int64_t n, uint64_t* tiles, int32_t*
 }
 void pq_launch_pack(const uint8_t* bytes, uint8_t* bitmap, int64_t n, void* st) {
   hipLaunchKernelGGL(pq_pack_kernel, grid_rows(n), 256, 0, (hipStream_t)st, bytes, bitmap, (i64)n);
-}
-void pq_launch_upload(const PqCopyDesc* descs, int n, void* st) {
-  if (n <= 0) return;
-  uint64_t longest = 0;
-  for (int i = 0; i < n; i++) longest = std::max<uint64_t>(longest, descs[i].len);      // (the descriptors sit in pinned host memory: the host reads them too)
-  if (!longest) return;
-  hipLaunchKernelGGL(pq_upload_kernel, dim3((unsigned)((longest + 65535) >> 16), (unsigned)n), 256, 0, (hipStream_t)st, descs);
 }
 }

@@ -32,7 +32,6 @@ void pool_put_stream(int dev, hipStream_t s);
 hipEvent_t pool_get_event(int dev);
 void pool_put_event(int dev, hipEvent_t e);
 int plans_executing();
-hipStream_t shared_copy_stream(int dev);
 } }
 #include "device/snappy2.hpp"
 #include "snappy2.hpp"
@@ -52,7 +51,6 @@ void pq_launch_list_elem_entries(const uint8_t* def, int64_t n, int def_slot, co
 void pq_launch_list_flags(const uint8_t* def, const uint8_t* rep, int64_t n, int def_slot, uint32_t* starts, uint32_t* elems, void* st);
 void pq_launch_list_assemble(const uint8_t* def, const uint8_t* rep, int64_t n, int64_t rows, int def_list, int def_slot, int max_def, const int32_t* start_idx, const int32_t* elem_idx,
                              const uint8_t* values, int width, int32_t* offsets, uint8_t* list_valid, uint8_t* elem_valid, uint8_t* elem_values, uint32_t* err, void* st);
-void pq_launch_decode_fixed(const PqDecodeArgs* a, void* st);
 void pq_launch_decode_runs(const PqDecodeArgs* a, void* st);
 void pq_launch_store_u32(const uint32_t* src, uint32_t* dst, void* st);
 void pq_launch_count_runs(const PqPendingRuns* pend, int n, const uint8_t* bytes, uint32_t* counts, uint32_t* err, void* st);
@@ -62,8 +60,6 @@ void pq_launch_string_lengths(const PqDecodeArgs* a, void* st);
 void pq_launch_string_copy(const PqDecodeArgs* a, void* st);
 void pq_launch_u32_scan(const uint32_t* in, int64_t n, uint64_t* tiles, int32_t* out, void* st);
 void pq_launch_pack(const uint8_t* bytes, uint8_t* bitmap, int64_t n, void* st);
-void pq_launch_snappy(const PqInflate* jobs, int njobs, uint8_t* bytes, uint32_t* err, void* st);
-void pq_launch_upload(const PqCopyDesc* descs, int n, void* st);
 }
 
 namespace comet {
@@ -1121,7 +1117,7 @@ void decode_chunk_host(const ChunkSource& src, const StructField& want, const Sc
   size_t keep_i = 0;            // first kept range that may still overlap the next page
   std::vector<uint8_t> tmp;
   // a PLAIN page's values cut into chunks of 4096: the units the run-at-a-time decode kernel hands to its waves
-  static const int32_t kPlainChunk = getenv("COMET_PQ_PLAIN_CHUNK") ? std::max(512, atoi(getenv("COMET_PQ_PLAIN_CHUNK")) & ~511) : 2048;
+  constexpr int32_t kPlainChunk = 2048;
   auto plain_chunks = [&](PqPage& pg, int64_t values_off_flagged) {
     if (cp.is_string) return;
     pg.idx_run_first = (int32_t)idx_runs.size();
@@ -1183,9 +1179,8 @@ void decode_chunk_host(const ChunkSource& src, const StructField& want, const Sc
     // Fixed-width columns: every kept piece gets its OWN units for the run-at-a-time kernel — the page's runs (or PLAIN chunks) clipped to
     // the piece's values, a bit-packed run possibly starting inside a byte (PqRun.pad = the bit) — so pruned scans decode at the same rate
     // as full ones (they took the row-at-a-time kernel, a quarter of the HBM roofline).  The page's own runs leave the table: nothing
-    // refers to them any more.  (Strings keep the shared runs and the row-at-a-time path; COMET_PQ_DECODE_ROWS keeps it for everything.)
-    static const bool clip_units = getenv("COMET_PQ_DECODE_ROWS") == nullptr;
-    const bool clip = clip_units && !cp.is_string;
+    // refers to them any more.  (Strings keep the shared runs: their kernels walk rows.)
+    const bool clip = !cp.is_string;
     std::vector<PqRun> page_runs;
     if (clip) {
       page_runs.assign(idx_runs.begin() + pg.idx_run_first, idx_runs.begin() + pg.idx_run_first + pg.idx_run_count);
@@ -1943,86 +1938,332 @@ static void trace_line(int scan, const char* fmt, ...) {
   fprintf(stderr, "[comet] parquet#%d: %s", scan, buf);
 }
 
-DevTable ExecutionContext::scan_parquet(const Operator& op) {
-  static const bool trace = getenv("COMET_TRACE_STAGES") != nullptr;
+namespace {
+
+// What a scan is told from outside, each environment variable and configuration key read HERE and nowhere else.  The per-scan decisions that
+// follow from them and from the files (ParquetScan::place_decompression) need to know which switches were set at all, so that is kept too.
+struct ScanSettings {
+  ScanOptions so;
+  bool zstd_explicit = false;        // COMET_DEVICE_ZSTD was set: the cost model does not turn the zstd pipeline off
+  bool zstd_dict_explicit = false;   // COMET_DEVICE_ZSTD_DICT was set: the few-threads rule does not decide it
+  int runs_snappy = -1;              // COMET_DEVICE_RUNS_SNAPPY: 0 / 1, -1 = the few-threads rule decides
+  bool page_index = true;
+  bool bloom_filters = true;         // datafusion.execution.parquet.bloom_filter_on_read (default true) reaches the reference's scan through spark.comet.datafusion.* (jni_api.rs:611-620, parquet_exec.rs:251-252)
+  int max_inflight = 1;              // spark.comet.gpu.scanThreads / COMET_SCAN_THREADS bound the pool
+  int host_threads = 1;
+  int few_threads_max = 4;           // COMET_PQ_FEW_THREADS: up to this many scan threads are "a few" (tools/gpu_run.sh forces the few-thread paths with it)
+};
+ScanSettings resolve_settings(const Operator& op, const std::vector<std::pair<std::string, std::string>>& config) {
+  auto on = [](const std::string& v) { return v != "false" && v != "0"; };
+  ScanSettings s;
+  s.so = ScanOptions::of(op);
+  if (const char* e = getenv("COMET_DEVICE_DECOMPRESS")) s.so.device_snappy_mode = !strcmp(e, "auto") ? -1 : atoi(e) != 0;
+  if (const char* e = getenv("COMET_DEVICE_DICT_PAGES")) s.so.device_dict_pages = atoi(e) != 0;
+  if (const char* e = getenv("COMET_PARQUET_READ_IN_PLACE")) s.so.read_in_place = atoi(e) != 0;
+  if (const char* e = getenv("COMET_DEVICE_ZSTD")) { s.so.device_zstd = atoi(e) != 0; s.zstd_explicit = true; }
+  if (const char* e = getenv("COMET_DEVICE_ZSTD_DICT")) { s.so.device_zstd_dict = atoi(e) != 0; s.zstd_dict_explicit = true; }
+  if (const char* e = getenv("COMET_DEVICE_RUNS")) s.so.device_runs = atoi(e) != 0;
+  if (const char* e = getenv("COMET_DEVICE_RUNS_SNAPPY")) s.runs_snappy = atoi(e) != 0;
+  if (const char* e = getenv("COMET_PARQUET_PAGE_INDEX")) s.page_index = atoi(e) != 0;
+  if (const char* e = getenv("COMET_PARQUET_BLOOM_FILTER")) s.bloom_filters = atoi(e) != 0;
+  static const int kFewThreads = getenv("COMET_PQ_FEW_THREADS") ? atoi(getenv("COMET_PQ_FEW_THREADS")) : 4;
+  s.few_threads_max = kFewThreads;
+  s.max_inflight = ScanPool::get().size();
+  for (auto& kv : config) {
+    if (kv.first == "spark.comet.gpu.scan.deviceDecompress") s.so.device_snappy_mode = kv.second == "auto" ? -1 : on(kv.second);
+    if (kv.first == "spark.comet.gpu.scan.pageIndex" || kv.first == "spark.sql.parquet.columnindex.access.enabled") s.page_index = on(kv.second);
+    if (kv.first == "spark.comet.datafusion.execution.parquet.bloom_filter_on_read") s.bloom_filters = on(kv.second);
+    if (kv.first == "spark.comet.gpu.scanThreads") s.max_inflight = std::max(1, atoi(kv.second.c_str()));
+  }
+  s.host_threads = std::max(1, std::min(s.max_inflight, ScanPool::get().size()));
+  return s;
+}
+
+// A LONE task with a few scan threads (a Spark task owns one core; nothing else executes in the process) leaves to the device whatever the
+// device can do: the index sections of dictionary-encoded pages are inflated there whatever the codec, and their run headers are walked there
+// (SF10 Q6 with one scan thread: zstd 84 → 39 ms, the host no longer inflates 165 MB of index sections; snappy 25 ms, the host no longer
+// looks through every compressed page for its run headers — ≈ 6 µs a page).  Not so a scan with a dozen threads — they are idle anyway, and a
+// column whose run table the device sizes is decoded one host round trip later (zstd 16.9 against 15.0 ms) — and not so a task that is one
+// of many: eight tasks at once have sixteen cores between them and ONE device, whose decompression kernels are then the bound (zstd: a kernel
+// running 0.81 of the wave); measured over the SF10 Q6 file, eight / sixteen tasks: 19.1 / 25.5 ms (snappy) and 25.5 / 28.7 ms (zstd) with the
+// host doing its part, 22.7 / 32.4 and 31.2 / 32.5 ms with the device taking everything (profiles/r5_executor_shape.md).
+constexpr int kLonePlans = 2;      // up to this many plans executing: the task is "alone"
+bool is_few_threads(const ScanSettings& st, int plans_executing) { return st.host_threads <= st.few_threads_max && plans_executing <= kLonePlans; }
+
+// Where the pages of fixed-width columns are decompressed, from the bytes such pages hold and the host threads there are to inflate them.
+// Measured on MI355X (profiles/r3_snappy_pipeline.json): the multi-kernel pipeline inflates PLAIN pages at 70–80 GB/s of output whatever
+// their number (it parallelises inside the pages), plus about half a millisecond of launches; a host core decompresses the same bytes at
+// ~1 GB/s.  Only a small scan on a host with many idle threads is better off on the host.
+// zstd (profiles/r3_zstd_pipeline.json): the sequence decoder is one scalar lane per 128 KiB block — what bounds it is that lane's
+// instruction count, not the number of blocks — so the device inflates at a rate that a host with a dozen idle cores matches; a Spark
+// task, which owns one core, is better off on the device by a wide margin.
+void decide_device_decompression(ScanSettings& st, int64_t plain_snappy_bytes, int64_t plain_zstd_bytes) {
+  ScanOptions& so = st.so;
+  if (so.device_snappy_mode >= 0) {
+    so.device_snappy = so.device_snappy_mode != 0;
+    return;
+  }
+  // the two codecs decide separately: snappy pages by the pipeline's rate against ~1 GB/s per host thread, zstd pages by the model above
+  const double T = (double)st.host_threads, sb = (double)plain_snappy_bytes, zb = (double)plain_zstd_bytes;
+  const bool snappy_on_device = plain_snappy_bytes > 0 && 0.5 + sb / 60e6 < sb / 1e6 / T;
+  const bool zstd_on_device = plain_zstd_bytes > 0 && so.device_zstd && kDeviceZstdSetupMs + zb / kDeviceZstdBytesPerMs < zb / kHostZstdBytesPerMs / T;
+  so.device_snappy = snappy_on_device || zstd_on_device;
+  if (!zstd_on_device && !st.zstd_explicit) so.device_zstd = false;
+}
+
+// one leaf of the nested column `top` (StructField::nest says which kind)
+StructField nested_leaf(const StructField& top, int nest, const std::string& name, const DType& t, bool nullable = true) {
+  StructField lf;
+  lf.name = name;
+  lf.dtype = t;
+  lf.nullable = nullable;
+  lf.nest = nest;
+  lf.parent = top.name;
+  lf.parent_field_id = top.field_id;
+  return lf;
+}
+
+// A chunk that is read in place is read in pieces of this size by whichever threads are free
+constexpr size_t kReadPiece = (size_t)2 << 20;
+// Pieces that are READY and lie this close together in the column's staging block cross as one copy
+constexpr size_t kMergeGap = (size_t)512 << 10;
+// (zstd: the sequence kernel lasts as long as ONE block's serial chain — ≈ 3.4 ms for 16 K sequences — whatever the number of blocks,
+// up to the 4096 the GPU holds at once, and a stream runs its groups one behind the other: five groups of 1300 blocks on two streams
+// took three chains in a row (SF10 Q6: device idle at 20.7 ms with every launch issued by 5.3 ms).  Groups of ≈ 2800 blocks: two of
+// them fill the GPU side by side)
+constexpr size_t kZGroupBlocks = 2800, kZGroupBlocksHeld = 4096;
+// (snappy: a lone few-thread task gets its big column at the rate one or two pread() loops reach — groups of 12 MB start inflating
+// while the rest is still being read; a scan with many threads keeps groups of 48 MB, fewer launches)
+constexpr size_t kSGroupBytesFew = (size_t)12 << 20, kSGroupBytesMany = (size_t)48 << 20;
+
+}  // namespace
+
+// One scan_parquet call: what its stages share, a member function per stage (ExecutionContext::scan_parquet is the driver).
+struct ParquetScan {
+  enum class TopKind { Flat, Struct, List, ListOfStructs };
+  struct TopCol { TopKind kind = TopKind::Flat; size_t first = 0, count = 0; };
+  // shared state outlives the scan only through the shared_ptr the tasks hold
+  struct Progress {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<char> done;
+    size_t finished = 0;
+    std::atomic<bool> cancelled{false};
+    std::atomic<size_t> next{0};
+  };
+  // The unit of host work is a PIECE, in the order the device consumes the bytes (columns largest first, their chunks in row order).  A chunk
+  // that is read in place is read in pieces of a couple of MiB by whichever threads are free, and the thread that lands its last piece walks
+  // its pages — so the chunks of a column become ready ONE AFTER THE OTHER at the rate all readers reach together (32 whole-chunk reads
+  // side by side finished together: the first copy of SF10 Q6 left at 2.5 ms, with a third of the file read); every other chunk is one
+  // piece (read, decompress, walk — as before).
+  struct Piece { size_t t; size_t lo, len; bool whole; };
+  struct ColumnDevice { DevBuf bytes, tables; PinnedBuf h_tables; std::vector<std::unique_ptr<Snappy2Scratch>> snappy2; std::vector<std::unique_ptr<Zstd2Scratch>> zstd2; };
+  // (the column has pages whose run headers the device walks — their descriptors, the prefix sum of their run counts and the total are there)
+  struct DeviceRuns { std::shared_ptr<DevBuf> pend, offsets; int npend = 0; int64_t total = 0; };
+  // [0, S) of the column's byte buffer: what the host staged (decompressed pages, or compressed bodies for the device); [S, 2S): pages the device decompresses
+  // (the staged region: the chunks' slots, then their raw areas — what crosses compressed, contiguous; the decompressed region mirrors the slots only)
+  struct ColumnUpload { size_t c; std::shared_ptr<ColumnDevice> cd; size_t S; bool may_inflate; };
+  struct Deferred { ColumnUpload u; std::shared_ptr<PinnedBuf> readback; hipEvent_t done; std::vector<const uint8_t*> at;
+                    DeviceRuns dr; std::shared_ptr<DevBuf> counts; bool finished = false; };
+  // where the parts of a column's concatenated tables lie, and what the decode kernels need to know about them
+  struct ColumnTables { size_t off_pages, off_def, off_idx, off_dict, off_doffs, off_soffs, off_rep, n_pages, n_idx, n_idx_dev; bool any_optional; };
+  // the chunk groups of one column that wait for their decompression launch, and the column's pieces that wait for their copy
+  struct GroupState {
+    std::vector<PqInflate> jobs, zjobs;
+    std::vector<comet_zstd2::ZBlock> zblocks;
+    size_t bytes = 0, zstd_chunks = 0;
+    size_t pend_lo[2] = {0, 0}, pend_hi[2] = {0, 0};      // two runs of pieces are open at a time: what the host staged (in the slots) and the chunks' raw areas (behind them, contiguous)
+    size_t pending_piece_bytes() const { return (pend_hi[0] - pend_lo[0]) + (pend_hi[1] - pend_lo[1]); }
+  };
+
+  ExecutionContext& ctx;
+  const Operator& op;
+  const hipStream_t stream_;
+  const int device_id_;
+  const bool trace = g_host_timers;              // COMET_TRACE_STAGES, read once per process
   const int scan_id = g_scan_seq.fetch_add(1);
   int64_t miss0[4] = {0, 0, 0, 0};
-  if (trace) pool_miss_counters(miss0);
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto ms_since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
-  // The scan works on LEAVES: a top-level column of a flat type is its own leaf; a struct column is one leaf per field, a list column the one
-  // leaf of its elements (one level of nesting: parquet_support.rs:249-383 converts structs, lists and maps of any depth).  Every leaf runs
-  // through the same machinery — its entries (rows; a list leaf: its level entries) are decoded into values + validity — and a nested
-  // column is assembled from its leaves' values and LEVELS at the end (pq_levels_kernel and the assembly kernels in parquet_kernels.hip).
-  const size_t ntop = op.required_schema.size();
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  double ms_since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
+
+  // ---- Members are destroyed in REVERSE order of declaration, on the error path too, and that order carries correctness: the read-back guard
+  // (stream sync) goes first, then the group-stream guard, then the copy-stream guard (sync, then streams and events go back to the pools),
+  // then `drain` (cancel, then wait for every task) — and only then `col_staged`, `chunks` and `sels`, which the tasks and the copies read.
+  // So: data first, `drain` behind everything a task touches, the three guards last.  Do not reorder. ----
+  DevTable out, lf_out;                          // lf_out: the leaves' columns (types / cols / has_valid), out: what the scan returns
+  // leaves
+  size_t ntop = 0, ncol = 0, npart = 0;
   std::vector<StructField> fields;               // the leaves
-  struct TopCol { int kind = 0; size_t first = 0, count = 0; };      // kind 0 flat, 1 struct, 2 list
-  std::vector<TopCol> tops(ntop);
+  std::vector<TopCol> tops;
   std::vector<int> top_of;                       // leaf → its top-level column
+  bool any_nested = false;
+  ScanSettings st;
+  bool few_threads = false;
+  // layout
+  std::vector<Sel> sels;
+  int64_t total_rows = 0;
+  size_t nsel = 0, ntasks = 0;
+  std::vector<HostChunk> chunks;
+  std::vector<ColumnPlan> plans;                  // what the column looks like in the files that have it (string-ness, output width)
+  std::vector<ColumnPlan> chunk_plans;            // per (column, row group): plan_column of that file, computed once
+  std::vector<char> chunk_missing;                // per (column, row group): this file lacks the column
+  std::vector<char> all_missing;                  // no selected file has the column and it has no default: all-NULL fast path
+  std::vector<std::vector<size_t>> slot_off;
+  // raw areas (chunks read in place): raw_off[c][si] from raw_base[c], which lies behind the column's last staging slot
+  std::vector<std::vector<size_t>> raw_off;
+  std::vector<size_t> raw_base;
+  std::vector<std::unique_ptr<PinnedBuf>> col_staged;
+  // a leaf's ENTRIES: its rows — or, the element leaf of a list, its level entries (ColumnMetaData.num_values); per row group where they start
+  std::vector<std::vector<int64_t>> ent_off;
+  std::vector<int64_t> ent_total;
+  std::vector<size_t> order;                      // the columns in the order they are taken
+  // host stage
+  std::shared_ptr<Progress> prog;
+  std::vector<Piece> pieces;
+  std::unique_ptr<std::atomic<int>[]> pieces_left;
+  std::mutex piece_err_mu;
+  // device side
+  std::vector<std::shared_ptr<ColumnDevice>> keep;
+  std::vector<hipEvent_t> events;
+  hipStream_t copy_stream = nullptr;
+  int n_group_streams = 0;
+  std::vector<hipStream_t> group_streams;
+  std::vector<char> group_dirty;
+  size_t group_rr = 0;
+  hipEvent_t groups_may_start = nullptr;      // recorded on stream_ behind the set-up the groups depend on (the error words' memset)
+  std::shared_ptr<DevBuf> tiles, inflate_err, vidx;      // inflate_err: one word per column, first failing page of the device decompression (job << 8 | code), 0 = fine
+  // the LEVELS of nested leaves, one byte per entry (queue_decode fills them; the assembly at the end reads them)
+  std::vector<std::shared_ptr<DevBuf>> leaf_def, leaf_rep;
+  std::vector<std::shared_ptr<DevBuf>> leaf_raw_values;      // a list leaf: its values over ENTRIES (the elements are compacted out of them)
+  std::deque<Deferred> deferred;      // (a deque: entries are finished in place while later columns append)
+  // whatever happens, no task may still reference this object when it unwinds (armed once the workers are submitted)
+  struct Drain {
+    std::shared_ptr<Progress> p; size_t n = 0;
+    ~Drain() {
+      if (!p) return;
+      p->cancelled.store(true);
+      std::unique_lock<std::mutex> lk(p->mu);
+      p->cv.wait(lk, [&] { return p->finished == n; });
+    }
+  } drain;
+  // (streams and events come from the process-wide pools: creating a stream costs 10 ms and destroying one 2 ms when eight tasks do it at
+  // once — hipStreamCreateWithFlags was a quarter of the wall time of eight concurrent scans, profiles/r4_executor_hip_api.txt)
+  struct StreamGuard {
+    int dev; hipStream_t& s; std::vector<hipEvent_t>& ev;
+    ~StreamGuard() {
+      if (s) { (void)hipStreamSynchronize(s); detail::pool_put_stream(dev, s); }
+      for (hipEvent_t e : ev) detail::pool_put_event(dev, e);
+    }
+  } stream_guard{device_id_, copy_stream, events};
+  struct GroupStreamGuard {
+    int dev; std::vector<hipStream_t>& gs;
+    ~GroupStreamGuard() { for (hipStream_t x : gs) { (void)hipStreamSynchronize(x); detail::pool_put_stream(dev, x); } }
+  } group_stream_guard{device_id_, group_streams};
+  // (an error thrown while read-backs are in flight: they land in pinned staging memory that goes back to its pool — wait for them first)
+  struct ReadbackGuard {
+    hipStream_t s;
+    const std::deque<Deferred>& d;
+    bool done = false;
+    ~ReadbackGuard() { if (!done && !d.empty()) (void)hipStreamSynchronize(s); }
+  } readback_guard{stream_, deferred};
+
+  ParquetScan(ExecutionContext& c, const Operator& o) : ctx(c), op(o), stream_(c.stream_), device_id_(c.device_id_) {
+    if (trace) pool_miss_counters(miss0);
+  }
+
+  // ---- the stages, in the order the driver runs them ----
+  void collect_leaves();
+  bool select();
+  void lay_out();
+  void place_decompression();
+  void start_host_stage();
+  void open_streams();
+  void upload_column(size_t c);
+  void finish_deferred();
+  void assemble_nested();
+  void partition_columns();
+  DevTable epilogue();
+
+  // ---- their parts ----
+  const Expr* default_of(size_t leaf) const;
+  const pq::ColumnMeta& chunk_meta(size_t c, size_t si) const { return sels[si].meta->row_groups[(size_t)sels[si].rg].columns[(size_t)chunk_plans[c * nsel + si].leaf]; }
+  void cut_pieces();
+  void run_task(size_t t, bool raw_read);
+  void read_piece(const Piece& pc);
+  void process_piece(size_t pi);
+  bool finish_counted_columns();
+  void wait_for(size_t t);
+  hipEvent_t get_event();
+  void upload(void* dst, const void* src, size_t len);
+  void upload_fence(hipStream_t waiter);
+  hipStream_t next_group_stream();
+  void join_groups();
+  void all_null_column(size_t c);
+  void flush_run(const ColumnUpload& u, GroupState& g, int w);
+  void push_piece(const ColumnUpload& u, GroupState& g, size_t lo, size_t hi);
+  void launch_group(const ColumnUpload& u, GroupState& g, size_t si);
+  void defer_behind_run_count(const ColumnUpload& u, size_t pending_bytes);
+  void defer_behind_readback(const ColumnUpload& u, size_t pending_bytes);
+  void parse_returned_sections(Deferred& d);
+  void finish_counted(Deferred& d);
+  void finish_column(const ColumnUpload& u, const DeviceRuns* dr);
+  ColumnTables send_tables(const ColumnUpload& u, const DeviceRuns* dr);
+  void queue_decode(const ColumnUpload& u, const ColumnTables& tb);
+  struct ListShape { std::shared_ptr<DevBuf> starts, elems, start_idx, elem_idx, offsets, lvb, lbm, evb; };
+  ListShape list_shape(size_t l0, bool clear_elem_valid, const uint8_t* values, int w, uint8_t* elem_values);
+  DeviceColumnView list_of_structs(size_t t);
+  DeviceColumnView struct_column(size_t t);
+  DeviceColumnView list_column(size_t t);
+  void check_device_errors();
+};
+
+// The scan works on LEAVES: a top-level column of a flat type is its own leaf; a struct column is one leaf per field, a list column the one
+// leaf of its elements (one level of nesting: parquet_support.rs:249-383 converts structs, lists and maps of any depth).  Every leaf runs
+// through the same machinery — its entries (rows; a list leaf: its level entries) are decoded into values + validity — and a nested
+// column is assembled from its leaves' values and LEVELS at the end (pq_levels_kernel and the assembly kernels in parquet_kernels.hip).
+void ParquetScan::collect_leaves() {
+  ntop = op.required_schema.size();
+  tops.assign(ntop, TopCol());
   for (size_t t = 0; t < ntop; t++) {
     const StructField& f = op.required_schema[t];
+    const DType& ft = f.dtype;
     tops[t].first = fields.size();
-    if (f.dtype.id == TypeId::Struct) {
-      tops[t].kind = 1;
-      if (f.dtype.kids.empty()) throw CometError("Parquet column '" + f.name + "': a struct without fields");
-      for (size_t k = 0; k < f.dtype.kids.size(); k++) {
-        if (f.dtype.kids[k].is_nested()) throw CometError("Parquet column '" + f.name + "': nesting deeper than one level is not supported by the GPU scan yet");
-        StructField lf;
-        lf.name = k < f.dtype.kid_names.size() ? f.dtype.kid_names[k] : std::string();
-        lf.dtype = f.dtype.kids[k];
-        lf.nullable = k < f.dtype.kid_nullable.size() ? f.dtype.kid_nullable[k] != 0 : true;
-        lf.nest = 1;
-        lf.parent = f.name;
-        lf.parent_field_id = f.field_id;
-        fields.push_back(lf);
-        top_of.push_back((int)t);
+    if (ft.id == TypeId::Struct) {
+      tops[t].kind = TopKind::Struct;
+      if (ft.kids.empty()) throw CometError("Parquet column '" + f.name + "': a struct without fields");
+      for (size_t k = 0; k < ft.kids.size(); k++) {
+        if (ft.kids[k].is_nested()) throw CometError("Parquet column '" + f.name + "': nesting deeper than one level is not supported by the GPU scan yet");
+        fields.push_back(nested_leaf(f, 1, k < ft.kid_names.size() ? ft.kid_names[k] : std::string(), ft.kids[k], k < ft.kid_nullable.size() ? ft.kid_nullable[k] != 0 : true));
       }
-    } else if (f.dtype.id == TypeId::List || f.dtype.id == TypeId::Map) {
+    } else if (ft.id == TypeId::List || ft.id == TypeId::Map) {
       // (a map is a list of (key, value) entry structs — in the file: <rep> group m (MAP) { repeated group key_value { required key; <rep> value } } —
       // and in HBM: the same offsets + entries layout, Arrow's)
-      tops[t].kind = 2;
-      if (f.dtype.kids.size() != 1) throw CometError("Parquet column '" + f.name + "': a list without an element type");
-      const DType& el = f.dtype.kids[0];
-      if (f.dtype.id == TypeId::Map && (el.id != TypeId::Struct || el.kids.size() != 2)) throw CometError("Parquet column '" + f.name + "': a map type without (key, value) entries");
+      tops[t].kind = TopKind::List;
+      if (ft.kids.size() != 1) throw CometError("Parquet column '" + f.name + "': a list without an element type");
+      const DType& el = ft.kids[0];
+      if (ft.id == TypeId::Map && (el.id != TypeId::Struct || el.kids.size() != 2)) throw CometError("Parquet column '" + f.name + "': a map type without (key, value) entries");
       if (el.id == TypeId::Struct && !el.kids.empty()) {
         // a list of structs: one leaf per field of the element struct, all under the same repeated group (the same repetition levels)
-        tops[t].kind = 3;
+        tops[t].kind = TopKind::ListOfStructs;
         for (size_t k = 0; k < el.kids.size(); k++) {
           if (el.kids[k].is_nested()) throw CometError("Parquet column '" + f.name + "': nesting deeper than a list of flat structs is not supported by the GPU scan yet");
-          StructField lf;
-          lf.name = k < el.kid_names.size() ? el.kid_names[k] : std::string();
-          lf.dtype = el.kids[k];
-          lf.nest = 3;
-          lf.parent = f.name;
-          lf.parent_field_id = f.field_id;
-          fields.push_back(lf);
-          top_of.push_back((int)t);
+          fields.push_back(nested_leaf(f, 3, k < el.kid_names.size() ? el.kid_names[k] : std::string(), el.kids[k]));
         }
-        tops[t].count = fields.size() - tops[t].first;
-        continue;
+      } else {
+        if (el.is_nested()) throw CometError("Parquet column '" + f.name + "': lists of " + el.str() + " are not supported by the GPU scan yet (lists of flat types and of flat structs are)");
+        fields.push_back(nested_leaf(f, 2, "element", el));
       }
-      if (el.is_nested()) throw CometError("Parquet column '" + f.name + "': lists of " + el.str() + " are not supported by the GPU scan yet (lists of flat types and of flat structs are)");
-      StructField lf;
-      lf.name = "element";
-      lf.dtype = el;
-      lf.nest = 2;
-      lf.parent = f.name;
-      lf.parent_field_id = f.field_id;
-      fields.push_back(lf);
-      top_of.push_back((int)t);
-    } else if (f.dtype.is_nested()) {
-      throw CometError("Parquet column '" + f.name + "': " + f.dtype.str() + " columns are not supported by the GPU scan yet");
+    } else if (ft.is_nested()) {
+      throw CometError("Parquet column '" + f.name + "': " + ft.str() + " columns are not supported by the GPU scan yet");
     } else {
       fields.push_back(f);
-      top_of.push_back((int)t);
     }
     tops[t].count = fields.size() - tops[t].first;
+    top_of.resize(fields.size(), (int)t);
+    any_nested |= tops[t].kind != TopKind::Flat;
   }
-  bool any_nested = false;
-  for (auto& tc : tops) any_nested |= tc.kind != 0;
-  const size_t ncol = fields.size();
-  const size_t npart = op.partition_schema.size();
-  DevTable out, lf_out;                          // lf_out: the leaves' columns (types / cols / has_valid), out: what the scan returns
+  ncol = fields.size();
+  npart = op.partition_schema.size();
   for (auto& f : op.required_schema) out.types.push_back(f.dtype);
   for (auto& f : op.partition_schema) out.types.push_back(f.dtype);
   out.cols.assign(ntop + npart, DeviceColumnView());
@@ -2030,72 +2271,56 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
   for (auto& f : fields) lf_out.types.push_back(f.dtype);
   lf_out.cols.assign(ncol, DeviceColumnView());
   lf_out.has_valid.assign(ncol, false);
-  if (op.files.empty()) return out;   // EmptyExec (planner.rs:1548-1556)
-  if (op.encryption_enabled) throw CometError("Parquet modular encryption is not supported by the GPU scan");
-  ScanOptions so = ScanOptions::of(op);
-  if (const char* e = getenv("COMET_DEVICE_DECOMPRESS")) so.device_snappy_mode = !strcmp(e, "auto") ? -1 : atoi(e) != 0;
-  if (const char* e = getenv("COMET_DEVICE_DICT_PAGES")) so.device_dict_pages = atoi(e) != 0;
-  if (const char* e = getenv("COMET_PARQUET_READ_IN_PLACE")) so.read_in_place = atoi(e) != 0;
-  if (const char* e = getenv("COMET_DEVICE_ZSTD")) so.device_zstd = atoi(e) != 0;
-  if (const char* e = getenv("COMET_DEVICE_ZSTD_DICT")) so.device_zstd_dict = atoi(e) != 0;
-  if (const char* e = getenv("COMET_DEVICE_RUNS")) so.device_runs = atoi(e) != 0;
-  for (auto& kv : config_)
-    if (kv.first == "spark.comet.gpu.scan.deviceDecompress") so.device_snappy_mode = kv.second == "auto" ? -1 : (kv.second != "false" && kv.second != "0");
-  if (op.default_values.size() != op.default_values_indexes.size()) throw CometError("NativeScan: default_values and default_values_indexes differ in length");
-  auto default_of = [&](size_t leaf) -> const Expr* {
-    if (fields[leaf].nest != 0) return nullptr;      // (default values belong to top-level columns)
-    const size_t c = (size_t)top_of[leaf];
-    for (size_t k = 0; k < op.default_values_indexes.size(); k++)
-      if ((size_t)op.default_values_indexes[k] == c) return op.default_values[k].get();
-    return nullptr;
-  };
+}
 
-  bool page_index = true;
-  if (const char* e = getenv("COMET_PARQUET_PAGE_INDEX")) page_index = atoi(e) != 0;
-  for (auto& kv : config_)
-    if (kv.first == "spark.comet.gpu.scan.pageIndex" || kv.first == "spark.sql.parquet.columnindex.access.enabled") page_index = kv.second != "false" && kv.second != "0";
-  // pass 1: open files, pick row groups (midpoint rule), prune by statistics and page index, total rows
-  std::vector<Sel> sels;
-  int64_t total_rows = 0, rg_pruned = 0, rows_pruned = 0;
-  if (any_nested) page_index = false;            // (a kept row range does not say which ENTRIES of a list leaf it covers)
-  // datafusion.execution.parquet.bloom_filter_on_read (default true) reaches the reference's scan through spark.comet.datafusion.* (jni_api.rs:611-620, parquet_exec.rs:251-252)
-  bool bloom_filters = true;
-  int64_t rg_bloom = 0;
-  if (const char* e = getenv("COMET_PARQUET_BLOOM_FILTER")) bloom_filters = atoi(e) != 0;
-  for (auto& kv : config_)
-    if (kv.first == "spark.comet.datafusion.execution.parquet.bloom_filter_on_read") bloom_filters = kv.second != "false" && kv.second != "0";
-  select_row_groups(op, page_index, sels, total_rows, rg_pruned, rows_pruned, bloom_filters, &rg_bloom);
-  row_groups_pruned_ += rg_pruned;
-  row_groups_pruned_bloom_ += rg_bloom;
-  rows_pruned_page_index_ += rows_pruned;
+const Expr* ParquetScan::default_of(size_t leaf) const {
+  if (fields[leaf].nest != 0) return nullptr;      // (default values belong to top-level columns)
+  const size_t c = (size_t)top_of[leaf];
+  for (size_t k = 0; k < op.default_values_indexes.size(); k++)
+    if ((size_t)op.default_values_indexes[k] == c) return op.default_values[k].get();
+  return nullptr;
+}
+
+// pass 1: open files, pick row groups (midpoint rule), prune by statistics and page index, total rows; → false: nothing to read
+bool ParquetScan::select() {
+  if (any_nested) st.page_index = false;            // (a kept row range does not say which ENTRIES of a list leaf it covers)
+  int64_t rg_pruned = 0, rows_pruned = 0, rg_bloom = 0;
+  select_row_groups(op, st.page_index, sels, total_rows, rg_pruned, rows_pruned, st.bloom_filters, &rg_bloom);
+  ctx.row_groups_pruned_ += rg_pruned;
+  ctx.row_groups_pruned_bloom_ += rg_bloom;
+  ctx.rows_pruned_page_index_ += rows_pruned;
   out.rows = total_rows;
-  bytes_scanned_ = 0;
-  if (total_rows == 0) return out;
+  ctx.bytes_scanned_ = 0;
+  if (total_rows == 0) return false;
   if (total_rows >= ((int64_t)1 << 31)) throw CometError("GPU Parquet scan: more than 2^31 rows in one partition");
-
   if (trace) trace_line(scan_id, "scan began at %.2f ms of the process clock; footers + row-group selection done at %.2f ms\n", process_clock_ms() - ms_since(), ms_since());
-  // Host threads prepare the column chunks (decompression dominates: ~1 GB/s per core for zstd) straight into one pinned
-  // block per column; this thread concatenates a finished column's tables, uploads and decodes the whole column at once.
-  // spark.comet.gpu.scanThreads / COMET_SCAN_THREADS bound the pool.
-  const size_t nsel = sels.size();
-  const size_t ntasks = ncol * nsel;
-  std::vector<HostChunk> chunks(ntasks);
-  std::vector<ColumnPlan> plans(ncol);            // what the column looks like in the files that have it (string-ness, output width)
-  std::vector<char> chunk_missing(ntasks, 0);     // per (column, row group): this file lacks the column
-  std::vector<char> all_missing(ncol, 0);         // no selected file has the column and it has no default: all-NULL fast path
-  std::vector<std::vector<size_t>> slot_off(ncol, std::vector<size_t>(nsel + 1, 0));
-  // raw areas (chunks read in place): raw_off[c][si] from raw_base[c], which lies behind the column's last staging slot
-  std::vector<std::vector<size_t>> raw_off(ncol, std::vector<size_t>(nsel + 1, 0));
-  std::vector<size_t> raw_base(ncol, 0);
-  std::vector<std::unique_ptr<PinnedBuf>> col_staged(ncol);
-  // a leaf's ENTRIES: its rows — or, the element leaf of a list, its level entries (ColumnMetaData.num_values); per row group where they start
-  std::vector<std::vector<int64_t>> ent_off(ncol, std::vector<int64_t>(nsel + 1, 0));
-  std::vector<int64_t> ent_total(ncol, 0);
+  return true;
+}
+
+// Host threads prepare the column chunks (decompression dominates: ~1 GB/s per core for zstd) straight into one pinned
+// block per column; this thread concatenates a finished column's tables, uploads and decodes the whole column at once.
+// Here: every chunk's plan, its staging slot and raw area in that block, and where its entries start.
+// (sized with so.device_zstd and so.read_in_place as they were SET: the per-scan decision about zstd comes later and only ever turns it off)
+void ParquetScan::lay_out() {
+  const ScanOptions& so = st.so;
+  nsel = sels.size();
+  ntasks = ncol * nsel;
+  chunks = std::vector<HostChunk>(ntasks);
+  plans.assign(ncol, ColumnPlan());
+  chunk_plans.assign(ntasks, ColumnPlan());
+  chunk_missing.assign(ntasks, 0);
+  all_missing.assign(ncol, 0);
+  slot_off.assign(ncol, std::vector<size_t>(nsel + 1, 0));
+  raw_off.assign(ncol, std::vector<size_t>(nsel + 1, 0));
+  raw_base.assign(ncol, 0);
+  col_staged.resize(ncol);
+  ent_off.assign(ncol, std::vector<int64_t>(nsel + 1, 0));
+  ent_total.assign(ncol, 0);
   for (size_t c = 0; c < ncol; c++) {
     bool have = false;
     const Expr* dflt = default_of(c);
     for (size_t si = 0; si < nsel; si++) {
-      ColumnPlan cp = plan_column(fields[c], *sels[si].meta, so);
+      const ColumnPlan& cp = chunk_plans[c * nsel + si] = plan_column(fields[c], *sels[si].meta, so);
       const pq::RowGroup& rg = sels[si].meta->row_groups[(size_t)sels[si].rg];
       if (!cp.missing && (size_t)cp.leaf >= rg.columns.size()) throw CometError("parquet: column index out of range");
       ent_off[c][si + 1] = ent_off[c][si] + ((!cp.missing && cp.max_rep > 0) ? rg.columns[(size_t)cp.leaf].num_values : sels[si].rows);
@@ -2114,7 +2339,7 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
     }
     raw_base[c] = (slot_off[c][nsel] + 64 + 63) & ~(size_t)63;
     if (!have) {
-      plans[c] = plan_column(fields[c], *sels[0].meta, so);
+      plans[c] = chunk_plans[c * nsel];
       all_missing[c] = dflt == nullptr || dflt->lit_null;
     }
     plans[c].out_width = out_width_of(fields[c].dtype);
@@ -2123,38 +2348,19 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
     col_staged[c].reset(new PinnedBuf());
     col_staged[c]->ensure(raw_base[c] + raw_off[c][nsel] + 64);
   }
-  // shared state outlives this frame only through the shared_ptr the tasks hold
-  struct Progress {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<char> done;
-    size_t finished = 0;
-    std::atomic<bool> cancelled{false};
-    std::atomic<size_t> next{0};
-  };
-  auto prog = std::make_shared<Progress>();
-  prog->done.assign(ntasks, 0);
-  int max_inflight = ScanPool::get().size();
-  for (auto& kv : config_)
-    if (kv.first == "spark.comet.gpu.scanThreads") max_inflight = std::max(1, atoi(kv.second.c_str()));
-  const int host_threads = std::max(1, std::min(max_inflight, ScanPool::get().size()));
-  // A LONE task with a few scan threads (a Spark task owns one core; nothing else executes in the process) leaves to the device whatever the
-  // device can do: the index sections of dictionary-encoded pages are inflated there whatever the codec, and their run headers are walked there
-  // (SF10 Q6 with one scan thread: zstd 84 → 39 ms, the host no longer inflates 165 MB of index sections; snappy 25 ms, the host no longer
-  // looks through every compressed page for its run headers — ≈ 6 µs a page).  Not so a scan with a dozen threads — they are idle anyway, and a
-  // column whose run table the device sizes is decoded one host round trip later (zstd 16.9 against 15.0 ms) — and not so a task that is one
-  // of many: eight tasks at once have sixteen cores between them and ONE device, whose decompression kernels are then the bound (zstd: a kernel
-  // running 0.81 of the wave); measured over the SF10 Q6 file, eight / sixteen tasks: 19.1 / 25.5 ms (snappy) and 25.5 / 28.7 ms (zstd) with the
-  // host doing its part, 22.7 / 32.4 and 31.2 / 32.5 ms with the device taking everything (profiles/r5_executor_shape.md).
-  static const int kFewThreads = getenv("COMET_PQ_FEW_THREADS") ? atoi(getenv("COMET_PQ_FEW_THREADS")) : 4;
-  static const int kLonePlans = getenv("COMET_PQ_LONE_PLANS") ? atoi(getenv("COMET_PQ_LONE_PLANS")) : 2;
-  const bool few_threads = host_threads <= kFewThreads && detail::plans_executing() <= kLonePlans;
-  if (getenv("COMET_DEVICE_ZSTD_DICT") == nullptr) so.device_zstd_dict = few_threads;
-  so.device_runs_snappy = few_threads;
-  if (const char* e = getenv("COMET_DEVICE_RUNS_SNAPPY")) so.device_runs_snappy = atoi(e) != 0;
+}
+
+// What the device takes over from the host threads in THIS scan, and the order of the columns.  The sequence matters: the few-threads rule
+// sets device_zstd_dict and device_runs_snappy, the byte count reads them, the cost model then sets device_snappy (and may clear device_zstd);
+// host tasks start only after all of that.
+void ParquetScan::place_decompression() {
+  ScanOptions& so = st.so;
+  few_threads = is_few_threads(st, detail::plans_executing());
+  if (!st.zstd_dict_explicit) so.device_zstd_dict = few_threads;
+  so.device_runs_snappy = st.runs_snappy >= 0 ? st.runs_snappy != 0 : few_threads;
   // Columns are taken largest first: the big PLAIN columns are the ones whose pages the device decompresses, and that kernel then runs
   // while the host threads are still preparing the small (dictionary-encoded) columns.
-  std::vector<size_t> order(ncol);
+  order.resize(ncol);
   std::vector<int64_t> col_bytes(ncol, 0);
   int64_t plain_snappy_bytes = 0;     // uncompressed bytes of chunks that are snappy, fixed-width and (by bytes per value) mostly PLAIN
   int64_t plain_zstd_bytes = 0;       // … zstd, fixed-width, mostly PLAIN
@@ -2162,77 +2368,53 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
     order[c] = c;
     for (size_t si = 0; si < nsel; si++) {
       if (chunk_missing[c * nsel + si]) continue;
-      ColumnPlan cp = plan_column(fields[c], *sels[si].meta, so);
-      const pq::ColumnMeta& cm = sels[si].meta->row_groups[(size_t)sels[si].rg].columns[(size_t)cp.leaf];
+      const ColumnPlan& cp = chunk_plans[c * nsel + si];
+      const pq::ColumnMeta& cm = chunk_meta(c, si);
       col_bytes[c] += cm.total_compressed;
+      const bool fixed_width = !cp.is_string && !cp.nested_leaf() && cp.src_width > 0 && cm.num_values > 0;
+      const bool mostly_plain = (double)cm.total_uncompressed >= 0.75 * (double)cp.src_width * (double)cm.num_values;
       // snappy chunks of fixed-width columns are what the device inflates: PLAIN pages, and dictionary-encoded pages whose run headers the
       // host reads through the compressed stream
-      if (cm.codec == pq::SNAPPY && !cp.is_string && !cp.nested_leaf() && cp.src_width > 0 && cm.num_values > 0 &&
-          (so.device_dict_pages || (double)cm.total_uncompressed >= 0.75 * (double)cp.src_width * (double)cm.num_values))
-        plain_snappy_bytes += cm.total_uncompressed;
+      if (cm.codec == pq::SNAPPY && fixed_width && (so.device_dict_pages || mostly_plain)) plain_snappy_bytes += cm.total_uncompressed;
       // … and zstd chunks: PLAIN pages, and — when the chunk is read whole — dictionary-encoded pages (index sections come back for their run headers)
-      if (cm.codec == pq::ZSTD && so.device_zstd && !cp.is_string && !cp.nested_leaf() && cp.src_width > 0 && cm.num_values > 0 &&
-          ((so.device_zstd_dict && sels[si].keep == nullptr) || (double)cm.total_uncompressed >= 0.75 * (double)cp.src_width * (double)cm.num_values))
-        plain_zstd_bytes += cm.total_uncompressed;
+      if (cm.codec == pq::ZSTD && so.device_zstd && fixed_width && ((so.device_zstd_dict && sels[si].keep == nullptr) || mostly_plain)) plain_zstd_bytes += cm.total_uncompressed;
     }
   }
   std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return col_bytes[a] > col_bytes[b]; });
-  // COMET_PQ_ORDER=small_first: the small columns' chunks are prepared and sent first (their slices cross in latency-bound copies that then
-  // overlap the big column's host work), the big column last; =big_first (default) starts the device pipeline of the big column as early as possible
   // A lone few-thread task takes its small columns first: a column whose run table the device sizes is finished one host round trip after its
-  // pages are inflated, and with the big column last those round trips happen WHILE the big column is read and crosses.
-  static const char* order_env = getenv("COMET_PQ_ORDER");
-  const bool small_first = order_env ? !strcmp(order_env, "small_first") : few_threads;
-  if (small_first) std::reverse(order.begin(), order.end());
-  // Measured on MI355X (profiles/r3_snappy_pipeline.json): the multi-kernel pipeline inflates PLAIN pages at 70–80 GB/s of output whatever
-  // their number (it parallelises inside the pages), plus about half a millisecond of launches; a host core decompresses the same bytes at
-  // ~1 GB/s.  Only a small scan on a host with many idle threads is better off on the host.
-  // zstd (profiles/r3_zstd_pipeline.json): the sequence decoder is one scalar lane per 128 KiB block — what bounds it is that lane's
-  // instruction count, not the number of blocks — so the device inflates at a rate that a host with a dozen idle cores matches; a Spark
-  // task, which owns one core, is better off on the device by a wide margin.
-  if (so.device_snappy_mode >= 0) {
-    so.device_snappy = so.device_snappy_mode != 0;
-  } else {
-    // the two codecs decide separately: snappy pages by the pipeline's rate against ~1 GB/s per host thread, zstd pages by the model above
-    const double T = (double)host_threads, sb = (double)plain_snappy_bytes, zb = (double)plain_zstd_bytes;
-    const bool snappy_on_device = plain_snappy_bytes > 0 && 0.5 + sb / 60e6 < sb / 1e6 / T;
-    const bool zstd_on_device = plain_zstd_bytes > 0 && so.device_zstd && kDeviceZstdSetupMs + zb / kDeviceZstdBytesPerMs < zb / kHostZstdBytesPerMs / T;
-    so.device_snappy = snappy_on_device || zstd_on_device;
-    if (!zstd_on_device && getenv("COMET_DEVICE_ZSTD") == nullptr) so.device_zstd = false;
-  }
+  // pages are inflated, and with the big column last those round trips happen WHILE the big column is read and crosses.  Every other scan
+  // starts the device pipeline of the big column as early as possible.
+  if (few_threads) std::reverse(order.begin(), order.end());
+  decide_device_decompression(st, plain_snappy_bytes, plain_zstd_bytes);
   if (trace) trace_line(scan_id, "%.1f MB of snappy / %.1f MB of zstd pages of fixed-width columns, decompressed on the %s%s\n", (double)plain_snappy_bytes / 1e6,
                      (double)plain_zstd_bytes / 1e6, so.device_snappy ? "device" : "host", so.device_snappy && plain_zstd_bytes && !so.device_zstd ? " (zstd: host)" : "");
-  auto run_task = [&](size_t t, bool raw_read) {
-    const size_t c = t / nsel, si = t % nsel;
-    ChunkSource src{sels[si].file.get(), sels[si].meta.get(), sels[si].rg, sels[si].keep.get()};
-    if (all_missing[c]) return;
-    uint8_t* slot = (uint8_t*)col_staged[c]->p + slot_off[c][si];
-    const size_t cap = slot_off[c][si + 1] - slot_off[c][si];
-    const size_t rcap = raw_off[c][si + 1] - raw_off[c][si];
-    uint8_t* rarea = rcap ? (uint8_t*)col_staged[c]->p + raw_base[c] + raw_off[c][si] : nullptr;
-    if (chunk_missing[t]) synth_chunk(fields[c], default_of(c), sels[si].rows, chunks[t], slot, cap);
-    else { HostTimer tm(g_ns_chunk); decode_chunk_host(src, fields[c], so, chunks[t], slot, cap, rarea, rcap, raw_read); }
-  };
-  // The unit of host work is a PIECE, in the order the device consumes the bytes (columns largest first, their chunks in row order).  A chunk
-  // that is read in place is read in pieces of a couple of MiB by whichever threads are free, and the thread that lands its last piece walks
-  // its pages — so the chunks of a column become ready ONE AFTER THE OTHER at the rate all readers reach together (32 whole-chunk reads
-  // side by side finished together: the first copy of SF10 Q6 left at 2.5 ms, with a third of the file read); every other chunk is one
-  // piece (read, decompress, walk — as before).
-  struct Piece { size_t t; size_t lo, len; bool whole; };
-  std::vector<Piece> pieces;
-  std::unique_ptr<std::atomic<int>[]> pieces_left(new std::atomic<int>[ntasks]);
-  static const size_t kReadPiece = getenv("COMET_PQ_READ_PIECE") ? (size_t)std::max(64 << 10, atoi(getenv("COMET_PQ_READ_PIECE"))) : ((size_t)2 << 20);
+}
+
+void ParquetScan::run_task(size_t t, bool raw_read) {
+  const size_t c = t / nsel, si = t % nsel;
+  ChunkSource src{sels[si].file.get(), sels[si].meta.get(), sels[si].rg, sels[si].keep.get()};
+  if (all_missing[c]) return;
+  uint8_t* slot = (uint8_t*)col_staged[c]->p + slot_off[c][si];
+  const size_t cap = slot_off[c][si + 1] - slot_off[c][si];
+  const size_t rcap = raw_off[c][si + 1] - raw_off[c][si];
+  uint8_t* rarea = rcap ? (uint8_t*)col_staged[c]->p + raw_base[c] + raw_off[c][si] : nullptr;
+  if (chunk_missing[t]) synth_chunk(fields[c], default_of(c), sels[si].rows, chunks[t], slot, cap);
+  else { HostTimer tm(g_ns_chunk); decode_chunk_host(src, fields[c], st.so, chunks[t], slot, cap, rarea, rcap, raw_read); }
+}
+
+void ParquetScan::cut_pieces() {
+  pieces_left.reset(new std::atomic<int>[ntasks]);
   for (size_t oi = 0; oi < ncol; oi++)
     for (size_t si = 0; si < nsel; si++) {
       const size_t c = order[oi], t = c * nsel + si;
       pieces_left[t].store(1);
       bool split = false;
-      if (!all_missing[c] && !chunk_missing[t] && raw_off[c][si + 1] > raw_off[c][si] && so.device_snappy) {
-        ColumnPlan cp = plan_column(fields[c], *sels[si].meta, so);
-        const pq::ColumnMeta& cm = sels[si].meta->row_groups[(size_t)sels[si].rg].columns[(size_t)cp.leaf];
+      if (!all_missing[c] && !chunk_missing[t] && raw_off[c][si + 1] > raw_off[c][si] && st.so.device_snappy) {
+        const ColumnPlan& cp = chunk_plans[t];
+        const pq::ColumnMeta& cm = chunk_meta(c, si);
         const int64_t off = chunk_file_offset(cm);
         // (a chunk that lies outside its file stays whole: decode_chunk_host says so)
-        if (in_place_shape(cm, cp.is_string || cp.nested_leaf(), so) && off >= 0 && cm.total_compressed > 0 && (size_t)(off + cm.total_compressed) <= sels[si].file->size &&
+        if (in_place_shape(cm, cp.is_string || cp.nested_leaf(), st.so) && off >= 0 && cm.total_compressed > 0 && (size_t)(off + cm.total_compressed) <= sels[si].file->size &&
             raw_off[c][si + 1] - raw_off[c][si] >= in_place_extra(cm)) {
           const size_t total = (size_t)cm.total_compressed;
           size_t np = 0;
@@ -2249,47 +2431,54 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
       }
       if (!split) pieces.push_back(Piece{t, 0, 0, true});
     }
+}
+
+void ParquetScan::read_piece(const Piece& pc) {
+  const size_t c = pc.t / nsel, si = pc.t % nsel;
+  const pq::ColumnMeta& cm = chunk_meta(c, si);
+  HostTimer tc(g_ns_chunk);
+  HostTimer tm(g_ns_read);
+  sels[si].file->read_at((uint8_t*)col_staged[c]->p + raw_base[c] + raw_off[c][si] + pc.lo, pc.len, chunk_file_offset(cm) + (int64_t)pc.lo);
+}
+
+void ParquetScan::process_piece(size_t pi) {
+  const Piece& pc = pieces[pi];
+  const size_t t = pc.t;
+  if (!pc.whole && !prog->cancelled.load()) {
+    try {
+      read_piece(pc);
+    } catch (...) {
+      std::lock_guard<std::mutex> lk(piece_err_mu);
+      if (!chunks[t].err) chunks[t].err = std::current_exception();
+    }
+  }
+  if (pieces_left[t].fetch_sub(1) != 1) return;      // another thread lands the chunk's last piece
+  if (!prog->cancelled.load() && !chunks[t].err) {
+    try {
+      run_task(t, !pc.whole);
+    } catch (...) {
+      chunks[t].err = std::current_exception();
+    }
+  }
+  {
+    std::lock_guard<std::mutex> lk(prog->mu);
+    prog->done[t] = 1;
+    prog->finished++;
+  }
+  prog->cv.notify_all();
+}
+
+// `max_inflight` workers take the pieces in order (spark.comet.gpu.scanThreads: a task's share of the executor's pool — one, for a
+// Spark task that owns one core), each from the shared cursor until none is left.  A worker holds `prog` by shared_ptr and this object by
+// pointer: that stays valid only because `drain` waits for every task before anything they touch is destroyed.
+void ParquetScan::start_host_stage() {
+  prog = std::make_shared<Progress>();
+  prog->done.assign(ntasks, 0);
+  cut_pieces();
   const size_t npieces = pieces.size();
-  auto read_piece = [&](const Piece& pc) {
-    const size_t c = pc.t / nsel, si = pc.t % nsel;
-    ColumnPlan cp = plan_column(fields[c], *sels[si].meta, so);
-    const pq::ColumnMeta& cm = sels[si].meta->row_groups[(size_t)sels[si].rg].columns[(size_t)cp.leaf];
-    HostTimer tc(g_ns_chunk);
-    HostTimer tm(g_ns_read);
-    sels[si].file->read_at((uint8_t*)col_staged[c]->p + raw_base[c] + raw_off[c][si] + pc.lo, pc.len, chunk_file_offset(cm) + (int64_t)pc.lo);
-  };
-  // `max_inflight` workers take the pieces in order (spark.comet.gpu.scanThreads: a task's share of the executor's pool — one, for a
-  // Spark task that owns one core), each from the shared cursor until none is left
-  const size_t nworkers = std::min<size_t>(npieces, (size_t)std::max(1, std::min(max_inflight, ScanPool::get().size())));
-  std::mutex piece_err_mu;
-  auto process_piece = [&, prog](size_t pi) {
-    const Piece& pc = pieces[pi];
-    const size_t t = pc.t;
-    if (!pc.whole && !prog->cancelled.load()) {
-      try {
-        read_piece(pc);
-      } catch (...) {
-        std::lock_guard<std::mutex> lk(piece_err_mu);
-        if (!chunks[t].err) chunks[t].err = std::current_exception();
-      }
-    }
-    if (pieces_left[t].fetch_sub(1) != 1) return;      // another thread lands the chunk's last piece
-    if (!prog->cancelled.load() && !chunks[t].err) {
-      try {
-        run_task(t, !pc.whole);
-      } catch (...) {
-        chunks[t].err = std::current_exception();
-      }
-    }
-    {
-      std::lock_guard<std::mutex> lk(prog->mu);
-      prog->done[t] = 1;
-      prog->finished++;
-    }
-    prog->cv.notify_all();
-  };
+  const size_t nworkers = std::min<size_t>(npieces, (size_t)st.host_threads);
   for (size_t wk = 0; wk < nworkers; wk++) {
-    ScanPool::get().submit([prog, npieces, &process_piece]() {
+    ScanPool::get().submit([prog = prog, npieces, this]() {
       for (;;) {
         const size_t pi = prog->next.fetch_add(1);
         if (pi >= npieces) break;
@@ -2297,689 +2486,620 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
       }
     });
   }
-  // whatever happens below, no task may still reference this frame when it unwinds
-  struct Drain {
-    std::shared_ptr<Progress> p; size_t n;
-    ~Drain() {
-      p->cancelled.store(true);
-      std::unique_lock<std::mutex> lk(p->mu);
-      p->cv.wait(lk, [&] { return p->finished == n; });
-    }
-  } drain{prog, ntasks};
-  // While the chunk it needs is not ready, the task's own thread READS pieces too instead of sleeping (a task with one scan thread got its
-  // 62 MB of SF10 Q6 at the 8 GB/s one pread() loop reaches next to seven others: 7.5 of its 17 ms).  Only pieces of chunks that are read in
-  // place — 2 MiB of pread(), at most the page-header walk of the chunk whose last piece this is; a chunk that is decompressed on the host
-  // would keep this thread from the copies and launches that are waiting for it.
-  static const bool help_reading = getenv("COMET_PQ_TASK_READS") == nullptr || atoi(getenv("COMET_PQ_TASK_READS")) != 0;
-  // (while_waiting: what else this thread has to do between pieces — columns whose run counts have come back from the device are finished
-  // there; → true while it wants to be called again soon)
-  std::function<bool()> while_waiting;
-  auto wait_for = [&](size_t t) {
-    for (;;) {
-      {
-        std::lock_guard<std::mutex> lk(prog->mu);
-        if (prog->done[t]) break;
-      }
-      const bool again = while_waiting ? while_waiting() : false;
-      size_t pi = prog->next.load();
-      bool took = false;
-      while (help_reading && pi < npieces && !pieces[pi].whole) {
-        if (prog->next.compare_exchange_weak(pi, pi + 1)) { took = true; break; }
-      }
-      if (took) { process_piece(pi); continue; }
-      std::unique_lock<std::mutex> lk(prog->mu);
-      if (again) { prog->cv.wait_for(lk, std::chrono::microseconds(150), [&] { return prog->done[t] != 0; }); continue; }
-      prog->cv.wait(lk, [&] { return prog->done[t] != 0; });
-      break;
-    }
-    if (chunks[t].err) std::rethrow_exception(chunks[t].err);
-  };
+  drain.p = prog;
+  drain.n = ntasks;
+}
 
-  struct ColumnDevice { DevBuf bytes, tables; PinnedBuf h_tables; std::vector<std::unique_ptr<Snappy2Scratch>> snappy2; std::vector<std::unique_ptr<Zstd2Scratch>> zstd2; };
-  std::vector<std::shared_ptr<ColumnDevice>> keep;
-  // The chunks' slices cross PCIe as soon as they are ready, one hipMemcpyAsync each (≈ 40 µs of submission and completion latency per copy
-  // whatever its size).  Two alternatives sit behind switches because they were measured and lost (SF10 Q6 from snappy Parquet, 16.6 ms
-  // with one copy per slice): COMET_PQ_UPLOAD=kernel batches the ready slices into ONE launch of a kernel that reads the pinned staging
-  // memory across PCIe itself (22.5 ms: the SDMA engines move a slice at 50+ GB/s, a kernel's reads of host memory reach half of that);
-  // COMET_PQ_COPY_STREAMS=n spreads the copies over n streams (17–18 ms, noisier).
-  // (streams and events come from the process-wide pools: creating a stream costs 10 ms and destroying one 2 ms when eight tasks do it at
-  // once — hipStreamCreateWithFlags was a quarter of the wall time of eight concurrent scans, profiles/r4_executor_hip_api.txt)
-  // (COMET_PQ_SHARED_COPY_STREAM=1: ONE copy stream for all scans of the process, detail::shared_copy_stream — measured and lost: a submission
-  // that stalls holds every task's copies behind it, 22.7 / 32.5 ms against 19.0 / 23.2 for eight / sixteen snappy tasks)
-  static const bool shared_copies = getenv("COMET_PQ_SHARED_COPY_STREAM") != nullptr && atoi(getenv("COMET_PQ_SHARED_COPY_STREAM")) != 0;
-  hipStream_t copy_stream = shared_copies ? detail::shared_copy_stream(device_id_) : detail::pool_get_stream(device_id_);
-  std::vector<hipStream_t> extra_streams;
-  std::vector<hipEvent_t> events;
-  PinnedBuf upload_descs;
-  struct StreamGuard {
-    int dev; hipStream_t& s; std::vector<hipStream_t>& extra; std::vector<hipEvent_t>& ev; bool shared;
-    ~StreamGuard() {
-      for (hipStream_t x : extra) { (void)hipStreamSynchronize(x); detail::pool_put_stream(dev, x); }
-      if (s && shared) {
-        // this scan's copies (read from pinned staging that is about to go back to its pool) are behind an event of its own; other scans' later
-        // copies are none of its business
-        hipEvent_t e = detail::pool_get_event(dev);
-        if (hipEventRecord(e, s) == hipSuccess) (void)hipEventSynchronize(e);
-        detail::pool_put_event(dev, e);
-      } else if (s) { (void)hipStreamSynchronize(s); detail::pool_put_stream(dev, s); }
-      for (hipEvent_t e : ev) detail::pool_put_event(dev, e);
-    }
-  } stream_guard{device_id_, copy_stream, extra_streams, events, shared_copies};
-  auto get_event = [&]() {
-    hipEvent_t e = detail::pool_get_event(device_id_);
-    events.push_back(e);
-    return e;
-  };
-  static const bool upload_by_kernel = getenv("COMET_PQ_UPLOAD") && !strcmp(getenv("COMET_PQ_UPLOAD"), "kernel");
-  static const int n_copy_streams = getenv("COMET_PQ_COPY_STREAMS") ? std::max(1, std::min(8, atoi(getenv("COMET_PQ_COPY_STREAMS")))) : 1;
-  for (int k = 1; k < n_copy_streams && !upload_by_kernel; k++) {
-    extra_streams.push_back(detail::pool_get_stream(device_id_));
+// a column whose run counts the device has delivered is finished as soon as this thread notices — between the chunks of the columns behind it;
+// → true while one is still open (the caller wants to look again soon)
+bool ParquetScan::finish_counted_columns() {
+  bool open = false;
+  for (Deferred& d : deferred) {
+    if (d.finished || !d.dr.npend) continue;
+    if (hipEventQuery(d.done) == hipSuccess) finish_counted(d);
+    else open = true;
   }
-  const size_t max_descs = ntasks * 2 + ncol + 16;
-  upload_descs.ensure(max_descs * sizeof(PqCopyDesc) + 64);
-  size_t descs_used = 0, batch_first = 0, rr = 0;
-  std::vector<char> stream_dirty(extra_streams.size() + 1, 0);
-  auto upload = [&](void* dst, const void* src, size_t len) {
-    if (!len) return;
-    if (upload_by_kernel) {
-      if (descs_used >= max_descs) throw CometError("internal: upload descriptor array too small");
-      PqCopyDesc& d = ((PqCopyDesc*)upload_descs.p)[descs_used++];
-      d.src = (const uint8_t*)src;
-      d.dst = (uint8_t*)dst;
-      d.len = (uint64_t)len;
-    } else {
-      const size_t k = rr++ % (extra_streams.size() + 1);
-      const double t_copy = trace ? ms_since() : 0;
-      HIP_CHECK(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, k ? extra_streams[k - 1] : copy_stream));
-      if (trace && ms_since() - t_copy > 0.3) trace_line(scan_id, "hipMemcpyAsync of %.2f MB held this thread %.2f ms (from %.2f ms)\n", (double)len / 1e6, ms_since() - t_copy, t_copy);
-      stream_dirty[k] = 1;
+  return open;
+}
+
+// While the chunk it needs is not ready, the task's own thread READS pieces too instead of sleeping (a task with one scan thread got its
+// 62 MB of SF10 Q6 at the 8 GB/s one pread() loop reaches next to seven others: 7.5 of its 17 ms).  Only pieces of chunks that are read in
+// place — 2 MiB of pread(), at most the page-header walk of the chunk whose last piece this is; a chunk that is decompressed on the host
+// would keep this thread from the copies and launches that are waiting for it.
+void ParquetScan::wait_for(size_t t) {
+  const size_t npieces = pieces.size();
+  for (;;) {
+    {
+      std::lock_guard<std::mutex> lk(prog->mu);
+      if (prog->done[t]) break;
     }
-  };
-  // everything queued so far is on its way (kernel path: one launch for the batch)
-  auto upload_flush = [&]() {
-    if (upload_by_kernel && descs_used > batch_first) {
-      pq_launch_upload((const PqCopyDesc*)upload_descs.p + batch_first, (int)(descs_used - batch_first), copy_stream);
-      batch_first = descs_used;
+    const bool again = finish_counted_columns();
+    size_t pi = prog->next.load();
+    bool took = false;
+    while (pi < npieces && !pieces[pi].whole) {
+      if (prog->next.compare_exchange_weak(pi, pi + 1)) { took = true; break; }
     }
-  };
-  // `waiter` runs behind every upload queued so far
-  auto upload_fence = [&](hipStream_t waiter) {
-    upload_flush();
-    hipEvent_t e = get_event();
-    HIP_CHECK(hipEventRecord(e, copy_stream));
-    HIP_CHECK(hipStreamWaitEvent(waiter, e, 0));
-    for (size_t k = 0; k < extra_streams.size(); k++)
-      if (stream_dirty[k + 1]) {
-        hipEvent_t x = get_event();
-        HIP_CHECK(hipEventRecord(x, extra_streams[k]));
-        HIP_CHECK(hipStreamWaitEvent(waiter, x, 0));
-        stream_dirty[k + 1] = 0;
-      }
-  };
-  // The decompression pipelines of a column's chunk groups run on streams of their own, taken in turn: a group's kernels are a chain
-  // (zstd: the sequence kernel lasts as long as ONE block's serial chain whatever the number of blocks — two groups side by side take no
-  // longer than one; snappy: the one-lane-per-page hop kernel and the tails of the others leave most of the GPU idle), so the next group's
-  // first kernels run under the previous group's last ones.  The column's decode kernels wait for every group (join_groups).
-  // (… while few plans execute.  With several at once the other tasks' kernels fill those gaps, and every extra stream is a hardware queue
-  // the tasks compete for — see detail::shared_copy_stream: the groups then run on the plan's own stream)
-  static const int group_streams_env = getenv("COMET_PQ_GROUP_STREAMS") ? std::max(0, std::min(8, atoi(getenv("COMET_PQ_GROUP_STREAMS")))) : -1;
-  const int n_group_streams = group_streams_env >= 0 ? group_streams_env : detail::plans_executing() >= 3 ? 0 : 2;
-  std::vector<hipStream_t> group_streams;
-  std::vector<hipEvent_t> group_events;
-  std::vector<char> group_dirty;
-  struct GroupStreamGuard {
-    int dev; std::vector<hipStream_t>& gs;
-    ~GroupStreamGuard() { for (hipStream_t x : gs) { (void)hipStreamSynchronize(x); detail::pool_put_stream(dev, x); } }
-  } group_stream_guard{device_id_, group_streams};
-  size_t group_rr = 0;
-  hipEvent_t groups_may_start = nullptr;      // recorded on stream_ behind the set-up the groups depend on (the error words' memset)
-  auto next_group_stream = [&]() -> hipStream_t {
-    if (n_group_streams == 0) return stream_;
-    const size_t k = group_rr++ % (size_t)n_group_streams;
-    if (k >= group_streams.size()) {
-      hipStream_t x = detail::pool_get_stream(device_id_);
-      group_streams.push_back(x);
-      group_dirty.push_back(0);
-      HIP_CHECK(hipStreamWaitEvent(x, groups_may_start, 0));
-    }
-    group_dirty[k] = 1;
-    return group_streams[k];
-  };
-  auto join_groups = [&]() {                  // stream_ runs behind every group launched so far
-    for (size_t k = 0; k < group_streams.size(); k++)
-      if (group_dirty[k]) {
-        hipEvent_t e = get_event();
-        HIP_CHECK(hipEventRecord(e, group_streams[k]));
-        HIP_CHECK(hipStreamWaitEvent(stream_, e, 0));
-        group_dirty[k] = 0;
-      }
-  };
-  auto tiles = std::make_shared<DevBuf>();
+    if (took) { process_piece(pi); continue; }
+    std::unique_lock<std::mutex> lk(prog->mu);
+    if (again) { prog->cv.wait_for(lk, std::chrono::microseconds(150), [&] { return prog->done[t] != 0; }); continue; }
+    prog->cv.wait(lk, [&] { return prog->done[t] != 0; });
+    break;
+  }
+  if (chunks[t].err) std::rethrow_exception(chunks[t].err);
+}
+
+hipEvent_t ParquetScan::get_event() {
+  hipEvent_t e = detail::pool_get_event(device_id_);
+  events.push_back(e);
+  return e;
+}
+
+// The chunks' slices cross PCIe as soon as they are ready, one hipMemcpyAsync each on the scan's own copy stream (≈ 40 µs of submission and
+// completion latency per copy whatever its size).  Measured and lost against it (SF10 Q6 from snappy Parquet, 16.6 ms with one copy per
+// slice): one launch of a kernel that reads the pinned staging memory across PCIe itself (22.5 ms: the SDMA engines move a slice at
+// 50+ GB/s, a kernel's reads of host memory reach half of that); the copies spread over n streams (17–18 ms, noisier); ONE copy stream for
+// all scans of the process (a submission that stalls holds every task's copies behind it, 22.7 / 32.5 ms against 19.0 / 23.2 for eight /
+// sixteen snappy tasks).
+void ParquetScan::upload(void* dst, const void* src, size_t len) {
+  if (!len) return;
+  const double t_copy = trace ? ms_since() : 0;
+  HIP_CHECK(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, copy_stream));
+  if (trace && ms_since() - t_copy > 0.3) trace_line(scan_id, "hipMemcpyAsync of %.2f MB held this thread %.2f ms (from %.2f ms)\n", (double)len / 1e6, ms_since() - t_copy, t_copy);
+}
+// `waiter` runs behind every upload queued so far
+void ParquetScan::upload_fence(hipStream_t waiter) {
+  hipEvent_t e = get_event();
+  HIP_CHECK(hipEventRecord(e, copy_stream));
+  HIP_CHECK(hipStreamWaitEvent(waiter, e, 0));
+}
+
+// The decompression pipelines of a column's chunk groups run on streams of their own, taken in turn: a group's kernels are a chain
+// (zstd: the sequence kernel lasts as long as ONE block's serial chain whatever the number of blocks — two groups side by side take no
+// longer than one; snappy: the one-lane-per-page hop kernel and the tails of the others leave most of the GPU idle), so the next group's
+// first kernels run under the previous group's last ones.  The column's decode kernels wait for every group (join_groups).
+// (… while few plans execute.  With several at once the other tasks' kernels fill those gaps, and every extra stream is a hardware queue
+// the tasks compete for: the groups then run on the plan's own stream)
+void ParquetScan::open_streams() {
+  copy_stream = detail::pool_get_stream(device_id_);
+  n_group_streams = detail::plans_executing() >= 3 ? 0 : 2;
+  tiles = std::make_shared<DevBuf>();
   int64_t max_entries = total_rows;
   for (size_t c = 0; c < ncol; c++) max_entries = std::max(max_entries, ent_total[c]);
   tiles->ensure((size_t)((max_entries + 1023) / 1024 + 2) * 8);
-  // one word per column: first failing page of the device decompression (job << 8 | code), 0 = fine
-  auto inflate_err = std::make_shared<DevBuf>();
+  inflate_err = std::make_shared<DevBuf>();
   inflate_err->ensure(ncol * 4 + 16);
   HIP_CHECK(hipMemsetAsync(inflate_err->p, 0, ncol * 4 + 16, stream_));
   groups_may_start = get_event();
   HIP_CHECK(hipEventRecord(groups_may_start, stream_));
-  auto vidx = std::make_shared<DevBuf>();
-
-  // everything behind a column's uploads: its tables (pages, runs, dictionaries) assembled and sent, the decode kernels queued.  A column
-  // with dictionary-encoded pages the DEVICE inflates comes here late — their run headers are read back first (below).
-  static const bool one_wave_snappy = getenv("COMET_SNAPPY_ONE_WAVE") != nullptr && atoi(getenv("COMET_SNAPPY_ONE_WAVE")) != 0;
-  // (`dr`: the column has pages whose run headers the device walks — their descriptors, the prefix sum of their run counts and the total are there)
-  struct DeviceRuns { std::shared_ptr<DevBuf> pend, offsets; int npend = 0; int64_t total = 0; };
-  // the LEVELS of nested leaves, one byte per entry (finish_column fills them; the assembly at the end reads them)
-  std::vector<std::shared_ptr<DevBuf>> leaf_def(ncol), leaf_rep(ncol);
-  std::vector<std::shared_ptr<DevBuf>> leaf_raw_values(ncol);      // a list leaf: its values over ENTRIES (the elements are compacted out of them)
-  auto finish_column = [&](const size_t c, const std::shared_ptr<ColumnDevice>& cd, const size_t S, const bool may_inflate, const DeviceRuns* dr) {
-    const ColumnPlan& cp = plans[c];
-    const bool is_string = cp.is_string;
-    const int64_t nrows = ent_total[c];           // the leaf's entries (a list's element leaf: more than the scan has rows)
-    auto values = std::make_shared<DevBuf>();
-    auto valid_bytes = std::make_shared<DevBuf>();
-    auto lengths = std::make_shared<DevBuf>();
-    bool any_optional = false;
-    size_t n_pages = 0, n_def = 0, n_idx = 0, n_dict = 0, n_doffs = 0, n_soffs = 0, n_jobs = 0, n_zjobs = 0, n_rep = 0;
-    for (size_t si = 0; si < nsel; si++) {
-      HostChunk& hc = chunks[c * nsel + si];
-      any_optional |= hc.max_def > 0 && (!hc.no_nulls || cp.nested_leaf());      // (a nested leaf always keeps its levels: the assembly reads them)
-      n_pages += hc.pages.size();
-      n_def += (hc.no_nulls && !cp.nested_leaf()) ? 0 : hc.def_runs.size();
-      n_rep += hc.rep_runs.size();
-      n_idx += hc.idx_runs.size();
-      n_dict += (hc.dict_bytes.size() + 15) & ~(size_t)15;
-      n_doffs += hc.dict_offs.size();
-      n_soffs += hc.str_offs.size();
-      n_jobs += hc.inflate.size();
-      n_zjobs += hc.zinflate.size();
-    }
-    if ((n_jobs || n_zjobs) && !may_inflate) throw CometError("internal: device pages in a column without a decompression region");
-    if (trace) trace_line(scan_id, "column %zu host chunks ready at %.2f ms\n", c, ms_since());
-    // concatenate the chunks' tables: offsets become column-global
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    size_t o = 0;
-    const size_t off_pages = o; o = al(o + n_pages * sizeof(PqPage));
-    const size_t off_def = o; o = al(o + n_def * sizeof(PqRun) + 16);
-    const size_t n_idx_dev = dr ? (size_t)dr->total : 0;      // runs the device writes behind the host's
-    const size_t off_idx = o; o = al(o + (n_idx + n_idx_dev) * sizeof(PqRun) + 16);
-    const size_t off_dict = o; o = al(o + n_dict + 16);
-    const size_t off_doffs = o; o = al(o + n_doffs * 4 + 16);
-    const size_t off_soffs = o; o = al(o + n_soffs * 8 + 16);
-    const size_t off_jobs = o; o = al(o + n_jobs * sizeof(PqInflate) + 16);
-    const size_t off_rep = o; o = al(o + n_rep * sizeof(PqRun) + 16);
-    cd->h_tables.ensure(o + 16);
-    cd->tables.ensure(o + 16);
-    char* tb_h = (char*)cd->h_tables.p;
-    bool runs_kernel_ok = true;
-    {
-      PqPage* P = (PqPage*)(tb_h + off_pages);
-      PqRun* D = (PqRun*)(tb_h + off_def);
-      PqRun* I = (PqRun*)(tb_h + off_idx);
-      uint8_t* DB = (uint8_t*)(tb_h + off_dict);
-      int32_t* DO = (int32_t*)(tb_h + off_doffs);
-      int64_t* SO = (int64_t*)(tb_h + off_soffs);
-      PqInflate* J = (PqInflate*)(tb_h + off_jobs);
-      PqRun* RP = (PqRun*)(tb_h + off_rep);
-      size_t ip = 0, id = 0, ii = 0, idb = 0, ido = 0, iso = 0, ij = 0, irp = 0;
-      runs_kernel_ok = true;
-      for (size_t si = 0; si < nsel; si++) {
-        HostChunk& hc = chunks[c * nsel + si];
-        const int64_t base = (int64_t)slot_off[c][si];
-        // an offset into the chunk's slot of the staged region, or (flagged) of the device-decompressed region behind it
-        auto global_off = [&](int64_t v) { return (v & kInflatedBit) ? (v & ~kInflatedBit) + base + (int64_t)S : v + base; };
-        const bool nulls = hc.max_def > 0 && (!hc.no_nulls || cp.nested_leaf());
-        for (const PqInflate& src : hc.inflate) {
-          PqInflate job = src;
-          job.src_off += base;
-          job.dst_off += base + (int64_t)S;
-          J[ij++] = job;
-        }
-        for (const PqPage& src : hc.pages) {
-          PqPage pg = src;
-          pg.row_start += ent_off[c][si];
-          pg.rep_run_first += (int32_t)irp;
-          pg.values_off = global_off(pg.values_off);
-          pg.str_first += (int64_t)iso;
-          if (nulls) pg.def_run_first += (int32_t)id;
-          else pg.def_run_first = pg.def_run_count = 0;
-          pg.idx_run_first += (int32_t)ii;
-          // (a dictionary the device inflated sits in the column's byte buffer: addressed from the dictionary table's base like the others)
-          pg.dict_off = hc.dev_dict >= 0 ? (int64_t)((char*)cd->bytes.p + base + (int64_t)S + hc.dev_dict - ((char*)cd->tables.p + off_dict)) : (int64_t)idb;
-          pg.dict_offs_first = (int32_t)ido;
-          P[ip++] = pg;
-        }
-        if (nulls)
-          for (const PqRun& r : hc.def_runs) { D[id] = r; D[id].byte_off = global_off(r.byte_off); id++; }
-        for (const PqRun& r : hc.idx_runs) { I[ii] = r; I[ii].byte_off = global_off(r.byte_off); ii++; }
-        for (const PqRun& r : hc.rep_runs) { RP[irp] = r; RP[irp].byte_off = global_off(r.byte_off); irp++; }
-        // every index run (and PLAIN chunk) learns its page: the run-at-a-time kernel starts from the run
-        for (size_t gp = ip - hc.pages.size(); gp < ip; gp++)
-          for (int32_t r = P[gp].idx_run_first; r < P[gp].idx_run_first + P[gp].idx_run_count; r++) I[r].page = (int32_t)gp;
-        // (pieces of a pruned page have their own clipped units unless COMET_PQ_DECODE_ROWS keeps the shared runs and the row-at-a-time kernel)
-        runs_kernel_ok &= sels[si].keep == nullptr || getenv("COMET_PQ_DECODE_ROWS") == nullptr;
-        if (!hc.dict_bytes.empty()) memcpy(DB + idb, hc.dict_bytes.data(), hc.dict_bytes.size());
-        idb += (hc.dict_bytes.size() + 15) & ~(size_t)15;
-        if (!hc.dict_offs.empty()) memcpy(DO + ido, hc.dict_offs.data(), hc.dict_offs.size() * 4);
-        ido += hc.dict_offs.size();
-        for (int64_t v : hc.str_offs) SO[iso++] = v ? v + base : 0;
-      }
-      if (n_pages >= ((size_t)1 << 31) || n_idx + n_idx_dev >= ((size_t)1 << 31)) throw CometError("parquet: too many pages / runs in one column");
-    }
-    cd->tables.ensure(o + 16);
-    upload(cd->tables.p, cd->h_tables.p, (o + 15) & ~(size_t)15);
-    upload_fence(stream_);
-    const char* tb = (const char*)cd->tables.p;
-    if (dr && dr->npend)      // the device-walked pages' runs go behind the host's; each such page's (first, count) is filled in on the device
-      pq_launch_write_runs((const PqPendingRuns*)dr->pend->p, dr->npend, (const uint8_t*)cd->bytes.p, (const int32_t*)dr->offsets->p, (int32_t)n_idx,
-                           (PqRun*)((char*)cd->tables.p + off_idx), (PqPage*)((char*)cd->tables.p + off_pages), stream_);
-    if (n_jobs) {
-      if (n_jobs >= ((size_t)1 << 23)) throw CometError("parquet: too many pages in one column");
-      // (the multi-kernel pipeline was launched group by group while the slices crossed PCIe, above)
-      if (one_wave_snappy) {
-        pq_launch_snappy((const PqInflate*)(tb + off_jobs), (int)n_jobs, (uint8_t*)cd->bytes.p, (uint32_t*)inflate_err->p + c, stream_);
-        pages_inflated_on_device_ += (int64_t)n_jobs;
-      }
-    }
-
-    PqDecodeArgs a;
-    memset(&a, 0, sizeof a);
-    a.pages = (const PqPage*)(tb + off_pages);
-    a.npages = (int32_t)n_pages;
-    a.max_def = any_optional ? std::max(cp.max_def, 1) : 0;      // (the validity kernel compares with it; every other kernel asks "> 0")
-    a.rep_runs = (const PqRun*)(tb + off_rep);
-    a.max_rep = cp.max_rep;
-    a.def_runs = (const PqRun*)(tb + off_def);
-    a.idx_runs = (const PqRun*)(tb + off_idx);
-    a.bytes = (const uint8_t*)cd->bytes.p;
-    a.dict = (const uint8_t*)(tb + off_dict);
-    a.dict_offs = (const int32_t*)(tb + off_doffs);
-    a.plain_str_offs = (const int64_t*)(tb + off_soffs);
-    a.n_rows = nrows;
-    a.out_width = cp.out_width;
-    a.n_idx_runs = (int32_t)(n_idx + n_idx_dev);
-    if (any_optional) {
-      valid_bytes->ensure((size_t)nrows + 16);
-      if (!vidx->p) vidx->ensure((size_t)nrows * 4 + 16);
-      a.valid_out = (uint8_t*)valid_bytes->p;
-      a.vidx = (uint32_t*)vidx->p;
-      pq_launch_validity(&a, stream_);
-      pq_launch_vidx(a.valid_out, nrows, (uint64_t*)tiles->p, a.vidx, stream_);
-    }
-    if (fields[c].nest != 0) {
-      leaf_def[c] = std::make_shared<DevBuf>();
-      leaf_def[c]->ensure((size_t)nrows + 16);
-      if (any_optional) pq_launch_levels(&a, 0, (uint8_t*)leaf_def[c]->p, stream_);
-      else HIP_CHECK(hipMemsetAsync(leaf_def[c]->p, cp.max_def, (size_t)nrows + 16, stream_));      // a chunk without level runs: everything defined
-      out.owners.push_back(leaf_def[c]);
-      if (fields[c].nest >= 2) {
-        leaf_rep[c] = std::make_shared<DevBuf>();
-        leaf_rep[c]->ensure((size_t)nrows + 16);
-        PqDecodeArgs ar = a;
-        if (!any_optional) ar.max_def = std::max(cp.max_def, 1);
-        pq_launch_levels(&ar, 1, (uint8_t*)leaf_rep[c]->p, stream_);
-        out.owners.push_back(leaf_rep[c]);
-      }
-    }
-    if (!is_string) {
-      values->ensure((size_t)nrows * cp.out_width + 16);
-      a.values_out = values->p;
-      // a column without NULLs (and without pruned pages) is decoded a RUN at a time: a wave takes one bit-packed run / RLE run / chunk of
-      // a PLAIN page and every lane decodes 8 of its values with all loads in flight at once; otherwise row by row
-      static const bool force_rows = getenv("COMET_PQ_DECODE_ROWS") != nullptr;
-      if (runs_kernel_ok && !force_rows) {
-        if (any_optional) {
-          // with NULLs a page's runs hold fewer values than it has rows: the values are decoded densely by their ordinal among the
-          // column's non-NULL values (vidx of the page's first row + index in the page), then spread to their rows
-          auto dense = std::make_shared<DevBuf>();
-          dense->ensure((size_t)nrows * cp.out_width + 16);
-          a.dense_out = dense->p;
-          pq_launch_decode_runs(&a, stream_);
-          pq_launch_expand_nulls(&a, stream_);
-          a.dense_out = nullptr;
-          out.owners.push_back(dense);
-        } else {
-          pq_launch_decode_runs(&a, stream_);
-        }
-      } else {
-        pq_launch_decode_fixed(&a, stream_);
-      }
-    } else {
-      lengths->ensure((size_t)nrows * 4 + 16);
-      a.lengths_out = (uint32_t*)lengths->p;
-      pq_launch_string_lengths(&a, stream_);
-    }
-    DeviceColumnView cv;
-    if (is_string) {
-      auto offsets = std::make_shared<DevBuf>();
-      offsets->ensure((size_t)(nrows + 1) * 4 + 16);
-      pq_launch_u32_scan((const uint32_t*)lengths->p, nrows, (uint64_t*)tiles->p, (int32_t*)offsets->p, stream_);
-      int32_t total_bytes = 0;
-      read_small(&total_bytes, (char*)offsets->p + (size_t)nrows * 4, 4);
-      auto data = std::make_shared<DevBuf>();
-      data->ensure((size_t)std::max(total_bytes, 1) + 16);
-      a.str_offsets = (const int32_t*)offsets->p;
-      a.str_bytes_out = (uint8_t*)data->p;
-      pq_launch_string_copy(&a, stream_);
-      cv.data = offsets->p;
-      cv.aux = data->p;
-      out.owners.push_back(offsets);
-      out.owners.push_back(data);
-      out.owners.push_back(lengths);
-    } else if (lf_out.types[c].id == TypeId::Bool) {
-      auto bits = std::make_shared<DevBuf>();
-      bits->ensure((size_t)((nrows + 7) / 8) + 16);
-      pq_launch_pack((const uint8_t*)values->p, (uint8_t*)bits->p, nrows, stream_);
-      cv.data = bits->p;
-      out.owners.push_back(bits);
-      out.owners.push_back(values);
-    } else {
-      cv.data = values->p;
-      out.owners.push_back(values);
-      leaf_raw_values[c] = values;
-    }
-    if (any_optional) {
-      auto bm = std::make_shared<DevBuf>();
-      bm->ensure((size_t)((nrows + 7) / 8) + 16);
-      pq_launch_pack((const uint8_t*)valid_bytes->p, (uint8_t*)bm->p, nrows, stream_);
-      cv.valid = (const uint8_t*)bm->p;
-      lf_out.has_valid[c] = true;
-      out.owners.push_back(bm);
-    }
-    out.owners.push_back(valid_bytes);
-    lf_out.cols[c] = cv;
-  };
-  struct Deferred { size_t c; std::shared_ptr<ColumnDevice> cd; size_t S; bool may_inflate; std::shared_ptr<PinnedBuf> readback; hipEvent_t done; std::vector<const uint8_t*> at;
-                    DeviceRuns dr; std::shared_ptr<DevBuf> counts; bool finished = false; };
-  std::deque<Deferred> deferred;      // (a deque: entries are finished in place while later columns append)
-  // a column whose run counts the device has delivered is finished as soon as this thread notices — between the chunks of the columns behind it
-  static const bool eager_finish = getenv("COMET_PQ_EAGER_FINISH") == nullptr || atoi(getenv("COMET_PQ_EAGER_FINISH")) != 0;
-  auto finish_counted = [&](Deferred& d) {
-    int32_t total = 0;
-    memcpy(&total, (char*)d.readback->p + (((size_t)d.dr.npend * sizeof(PqPendingRuns) + 15) & ~(size_t)15) + 16, 4);
-    if (total < 0) throw CometError("parquet: too many runs in one column");
-    d.dr.total = total;
-    if (trace) trace_line(scan_id, "column %zu: %d runs counted on the device at %.2f ms\n", d.c, total, ms_since());
-    finish_column(d.c, d.cd, d.S, d.may_inflate, &d.dr);
-    out.owners.push_back(d.dr.pend);
-    out.owners.push_back(d.dr.offsets);
-    out.owners.push_back(d.counts);
-    d.finished = true;
-  };
-  while_waiting = [&]() -> bool {
-    if (!eager_finish) return false;
-    bool open = false;
-    for (Deferred& d : deferred) {
-      if (d.finished || !d.dr.npend) continue;
-      if (hipEventQuery(d.done) == hipSuccess) finish_counted(d);
-      else open = true;
-    }
-    return open;
-  };
-  // (an error thrown while read-backs are in flight: they land in pinned staging memory that goes back to its pool — wait for them first)
-  struct ReadbackGuard {
-    hipStream_t s;
-    const std::deque<Deferred>& d;
-    bool done = false;
-    ~ReadbackGuard() { if (!done && !d.empty()) (void)hipStreamSynchronize(s); }
-  } readback_guard{stream_, deferred};
-  for (size_t oi = 0; oi < ncol; oi++) {
-    const size_t c = order[oi];
-    const ColumnPlan& cp = plans[c];
-    if (all_missing[c]) {
-      // all-NULL column: zeroed values, zeroed validity bitmap
-      DeviceColumnView mv;
-      auto zeros = std::make_shared<DevBuf>();
-      const size_t vb = cp.is_string ? (size_t)(total_rows + 1) * 4 : lf_out.types[c].id == TypeId::Bool ? (size_t)((total_rows + 7) / 8) : (size_t)total_rows * cp.out_width;
-      zeros->ensure(vb + 16);
-      HIP_CHECK(hipMemsetAsync(zeros->p, 0, vb + 16, stream_));
-      auto bm = std::make_shared<DevBuf>();
-      bm->ensure((size_t)((total_rows + 7) / 8) + 16);
-      HIP_CHECK(hipMemsetAsync(bm->p, 0, (size_t)((total_rows + 7) / 8) + 16, stream_));
-      mv.data = zeros->p;
-      mv.valid = (const uint8_t*)bm->p;
-      if (cp.is_string) mv.aux = zeros->p;   // no bytes are ever addressed (all offsets 0)
-      lf_out.has_valid[c] = true;
-      lf_out.cols[c] = mv;
-      out.owners.push_back(zeros);
-      out.owners.push_back(bm);
-      for (size_t si = 0; si < nsel; si++) wait_for(c * nsel + si);
-      continue;
-    }
-    auto cd = std::make_shared<ColumnDevice>();
-    keep.push_back(cd);
-    // the column's page bytes cross PCIe in slices as soon as their chunks are ready, on the copy stream
-    // [0, S): what the host staged (decompressed pages, or compressed bodies for the device); [S, 2S): pages the device decompresses
-    // (the staged region: the chunks' slots, then their raw areas — what crosses compressed, contiguous; the decompressed region mirrors the slots only)
-    const size_t S = (raw_base[c] + raw_off[c][nsel] + 64 + 15) & ~(size_t)15;
-    const bool may_inflate = so.device_snappy && !cp.is_string && !cp.missing;
-    cd->bytes.ensure(may_inflate ? S + ((slot_off[c][nsel] + 64 + 15) & ~(size_t)15) + 64 : S);
-    size_t n_jobs = 0, n_zjobs = 0;
-    std::vector<PqInflate> group_jobs, zgroup_jobs;
-    std::vector<comet_zstd2::ZBlock> zgroup_blocks;
-    size_t group_bytes = 0, zstd_chunks_in_group = 0;
-    // A copy costs ≈ 40–60 µs of submission and completion latency whatever its size (a 1 MB slice crosses in 20 µs), and one stream
-    // carries them one after the other: a column of 60 small chunks spent more time between its copies than in them.  So pieces that are
-    // READY and lie close together in the column's staging block cross as ONE copy — the bytes between them (a slot's unused tail) ride
-    // along; a piece waits for company only while no thread would have to wait for it.
-    // Two runs of pieces are open at a time: what the host staged (in the slots) and the chunks' raw areas (behind them, contiguous).
-    constexpr size_t kMergeGap = (size_t)512 << 10;
-    size_t pend_lo[2] = {0, 0}, pend_hi[2] = {0, 0};
-    auto flush_run = [&](int w) {
-      if (pend_hi[w] > pend_lo[w]) upload((char*)cd->bytes.p + pend_lo[w], (char*)col_staged[c]->p + pend_lo[w], pend_hi[w] - pend_lo[w]);
-      pend_lo[w] = pend_hi[w] = 0;
-    };
-    auto flush_pieces = [&]() { flush_run(0); flush_run(1); };
-    auto pending_piece_bytes = [&]() { return (pend_hi[0] - pend_lo[0]) + (pend_hi[1] - pend_lo[1]); };
-    auto push_piece = [&](size_t lo, size_t hi) {
-      if (hi <= lo) return;
-      const int w = lo >= raw_base[c] ? 1 : 0;
-      if (pend_hi[w] > pend_lo[w] && lo >= pend_lo[w] && lo <= pend_hi[w] + kMergeGap) { pend_hi[w] = std::max(pend_hi[w], hi); return; }
-      flush_run(w);
-      pend_lo[w] = lo;
-      pend_hi[w] = hi;
-    };
-    for (size_t si = 0; si < nsel; si++) {
-      {
-        bool ready;
-        { std::lock_guard<std::mutex> lk(prog->mu); ready = prog->done[c * nsel + si] != 0; }
-        // what is ready crosses while this thread waits — once it is worth a copy: a task with one scan thread gets its chunks one by one, and a
-        // hipMemcpyAsync per 0.7 MB chunk cost each of eight concurrent tasks 120 µs a call (profiles/r4_executor_hip_api.txt)
-        if (!ready && pending_piece_bytes() >= ((size_t)2 << 20)) { flush_pieces(); upload_flush(); }
-      }
-      const double t_wait = trace ? ms_since() : 0;
-      if (while_waiting) (void)while_waiting();
-      wait_for(c * nsel + si);
-      if (trace && ms_since() - t_wait > 0.3) trace_line(scan_id, "column %zu waited %.2f ms for chunk %zu (until %.2f ms)\n", c, ms_since() - t_wait, si, ms_since());
-      HostChunk& hc = chunks[c * nsel + si];
-      // is the chunk behind this one ready too?  Then its slices join this batch (one launch for all of them)
-      bool next_ready = false;
-      if (si + 1 < nsel) {
-        std::lock_guard<std::mutex> lk(prog->mu);
-        next_ready = prog->done[c * nsel + si + 1] != 0;
-      }
-      bytes_scanned_ += hc.compressed;
-      n_jobs += hc.inflate.size();
-      n_zjobs += hc.zinflate.size();
-      // only the bytes the chunk actually staged cross PCIe
-      if (hc.spos) push_piece(slot_off[c][si], slot_off[c][si] + std::min((hc.spos + 16 + 15) & ~(size_t)15, slot_off[c][si + 1] - slot_off[c][si]));
-      if (hc.raw_hi > hc.raw_lo) {      // page bodies read in place: from where pread() put them (+ the few bytes behind the last one the kernels' vector loads touch)
-        const size_t raw_end = raw_base[c] + raw_off[c][si + 1] - slot_off[c][si];      // slot-relative, like raw_lo / raw_hi
-        const size_t lo = hc.raw_lo & ~(size_t)15, hi = std::min((hc.raw_hi + 32 + 15) & ~(size_t)15, raw_end);
-        push_piece(slot_off[c][si] + lo, slot_off[c][si] + hi);
-      }
-      // Pages the device decompresses: the pipeline is launched for a GROUP of chunks as soon as their slices are across, so it runs
-      // while the column's later chunks are still being read and uploaded (launched once per column it started only after the last slice:
-      // 7 ms of decompression behind 10 ms of upload, SF10 Q6).  COMET_SNAPPY_ONE_WAVE=1 keeps the one-wave-per-page kernel, per column.
-      if (!one_wave_snappy)
-        for (const PqInflate& src : hc.inflate) {
-          PqInflate job = src;
-          job.src_off += (int64_t)slot_off[c][si];
-          job.dst_off += (int64_t)slot_off[c][si] + (int64_t)S;
-          group_jobs.push_back(job);
-          group_bytes += (size_t)job.src_len;
-        }
-      {
-        const int32_t first_block = (int32_t)zgroup_blocks.size();
-        zgroup_blocks.insert(zgroup_blocks.end(), hc.zblocks.begin(), hc.zblocks.end());
-        for (const PqInflate& src : hc.zinflate) {
-          PqInflate job = src;
-          job.src_off += (int64_t)slot_off[c][si];
-          job.dst_off += (int64_t)slot_off[c][si] + (int64_t)S;
-          job.preamble += first_block;
-          zgroup_jobs.push_back(job);
-          group_bytes += (size_t)job.src_len;
-        }
-      }
-      // (zstd: the sequence kernel lasts as long as ONE block's serial chain — ≈ 3.4 ms for 16 K sequences — whatever the number of blocks,
-      // up to the 4096 the GPU holds at once, and a stream runs its groups one behind the other: five groups of 1300 blocks on two streams
-      // took three chains in a row (SF10 Q6: device idle at 20.7 ms with every launch issued by 5.3 ms).  Groups of ≈ 2800 blocks: two of
-      // them fill the GPU side by side)
-      // (a launch is a chain's latency however small it is: what is left of the column joins this group when it fits the GPU with it —
-      // judged by the blocks per chunk seen so far)
-      zstd_chunks_in_group += hc.zinflate.empty() ? 0 : 1;
-      const size_t zleft_est = zstd_chunks_in_group ? (nsel - 1 - si) * zgroup_blocks.size() / zstd_chunks_in_group : 0;
-      static const size_t kZGroupBlocks = getenv("COMET_PQ_ZGROUP_BLOCKS") ? (size_t)std::max(64, atoi(getenv("COMET_PQ_ZGROUP_BLOCKS"))) : 2800;
-      const bool zfull = zgroup_blocks.size() >= kZGroupBlocks && zgroup_blocks.size() + zleft_est > (kZGroupBlocks == 2800 ? (size_t)4096 : kZGroupBlocks * 3 / 2);
-      // (snappy: a lone few-thread task gets its big column at the rate one or two pread() loops reach — groups of 12 MB start inflating
-      // while the rest is still being read; a scan with many threads keeps groups of 48 MB, fewer launches)
-      static const size_t kSGroupEnv = getenv("COMET_PQ_SGROUP_MB") ? (size_t)std::max(1, atoi(getenv("COMET_PQ_SGROUP_MB"))) << 20 : 0;
-      const size_t sgroup_bytes = kSGroupEnv ? kSGroupEnv : few_threads ? ((size_t)12 << 20) : ((size_t)48 << 20);
-      const bool group_full = (!group_jobs.empty() || !zgroup_jobs.empty()) && ((zgroup_jobs.empty() ? group_bytes >= sgroup_bytes : zfull) || si + 1 == nsel);
-      if (group_full || si + 1 == nsel) flush_pieces();
-      if (!next_ready || group_full) upload_flush();
-      if (group_full) {
-        if (group_jobs.size() >= ((size_t)1 << 23) || zgroup_jobs.size() >= ((size_t)1 << 23)) throw CometError("parquet: too many pages in one column");
-        const double t_launch = trace ? ms_since() : 0;
-        // The pipelines' tables cross on the COPY stream, behind the page bytes; the group's stream is then fenced behind both and gets kernels
-        // only.  (A host → device copy queued on a stream that waits for another stream's event holds the calling thread until that event has
-        // happened: with the tables sent on the group's stream every launch here cost its task 7–10 ms — the time its page bytes needed to
-        // cross — and eight concurrent tasks issued nothing else meanwhile: the first session of round 5, stage traces.)
-        Snappy2Scratch* sn = nullptr;
-        Zstd2Scratch* zs = nullptr;
-        if (!group_jobs.empty()) {
-          cd->snappy2.emplace_back(new Snappy2Scratch());
-          sn = cd->snappy2.back().get();
-          sn->stage(group_jobs.data(), (int)group_jobs.size(), copy_stream);
-        }
-        if (!zgroup_jobs.empty()) {
-          cd->zstd2.emplace_back(new Zstd2Scratch());
-          zs = cd->zstd2.back().get();
-          zs->stage(zgroup_jobs.data(), (int)zgroup_jobs.size(), zgroup_blocks.data(), copy_stream);
-        }
-        stream_dirty[0] = 1;
-        hipStream_t gs = next_group_stream();
-        const double t_stream = trace ? ms_since() : 0;
-        upload_fence(gs);
-        const double t_fence = trace ? ms_since() : 0;
-        if (sn) sn->launch((uint8_t*)cd->bytes.p, (uint32_t*)inflate_err->p + c, gs);
-        if (zs) zs->launch((uint8_t*)cd->bytes.p, (uint32_t*)inflate_err->p + c, gs);
-        if (trace) trace_line(scan_id, "column %zu group of %zu snappy / %zu zstd pages (%zu blocks, %.1f MB) up to chunk %zu launched at %.2f ms\n", c, group_jobs.size(),
-                           zgroup_jobs.size(), zgroup_blocks.size(), (double)group_bytes / 1e6, si, ms_since());
-        if (trace && ms_since() - t_launch > 0.3)
-          trace_line(scan_id, "… that launch took %.2f ms of this thread (tables + stream %.2f, fence %.2f, kernels %.2f)\n", ms_since() - t_launch, t_stream - t_launch, t_fence - t_stream,
-                     ms_since() - t_fence);
-        pages_inflated_on_device_ += (int64_t)(group_jobs.size() + zgroup_jobs.size());
-        group_jobs.clear();
-        zgroup_jobs.clear();
-        zgroup_blocks.clear();
-        group_bytes = 0;
-        zstd_chunks_in_group = 0;
-      }
-    }
-    // Dictionary-encoded pages the device inflates (zstd: their literals are entropy-coded, the host cannot look through the compressed stream
-    // as it does with snappy): the index sections come BACK once the device has inflated them — a few MB per column at PCIe speed — and the
-    // host reads the run headers out of them (the decoded values never come back).  Such a column is finished behind all uploads.
-    flush_pieces();
-    join_groups();
-    size_t pending_bytes = 0;
-    for (size_t si = 0; si < nsel; si++)
-      for (const HostChunk::Pending& pe : chunks[c * nsel + si].pending) pending_bytes += ((pe.end - pe.begin) + 15) & ~(size_t)15;
-    if (pending_bytes && so.device_runs) {
-      // The device walks the run headers where the sections lie (device/pq_runs.hpp): one descriptor per page in the coordinates of the column's
-      // byte buffer, a count pass, a prefix sum — and FOUR BYTES come back (the total, which sizes the run table) instead of the sections.
-      Deferred d{c, cd, S, may_inflate, std::make_shared<PinnedBuf>(), get_event(), {}, {}, nullptr};
-      size_t npend = 0, page_base = 0;
-      for (size_t si = 0; si < nsel; si++) npend += chunks[c * nsel + si].pending.size();
-      if (npend >= ((size_t)1 << 30)) throw CometError("parquet: too many pages in one column");
-      d.readback->ensure(npend * sizeof(PqPendingRuns) + 128);
-      PqPendingRuns* pd = (PqPendingRuns*)d.readback->p;
-      size_t k = 0;
-      for (size_t si = 0; si < nsel; si++) {
-        const HostChunk& hc = chunks[c * nsel + si];
-        for (const HostChunk::Pending& pe : hc.pending) {
-          PqPendingRuns& x = pd[k++];
-          x.begin = (int64_t)(slot_off[c][si] + S + pe.begin);
-          x.end = (int64_t)(slot_off[c][si] + S + pe.end);
-          x.bit_width = hc.pages[pe.page].bit_width;
-          x.max_values = pe.values;
-          x.page = (int32_t)(page_base + pe.page);      // column-global: the chunks' pages are concatenated in row-group order (finish_column)
-          x.pad = 0;
-        }
-        page_base += hc.pages.size();
-      }
-      d.dr.pend = std::make_shared<DevBuf>();
-      d.dr.offsets = std::make_shared<DevBuf>();
-      d.counts = std::make_shared<DevBuf>();
-      d.dr.pend->ensure(npend * sizeof(PqPendingRuns) + 16);
-      d.counts->ensure(npend * 4 + 16);
-      d.dr.offsets->ensure((npend + 1) * 4 + 16);
-      d.dr.npend = (int)npend;
-      // (descriptors on the copy stream, stream_ fenced behind it: no host → device copy on a stream that waits — see the group launch above)
-      upload(d.dr.pend->p, pd, (npend * sizeof(PqPendingRuns) + 15) & ~(size_t)15);
-      upload_fence(stream_);
-      pq_launch_count_runs((const PqPendingRuns*)d.dr.pend->p, (int)npend, (const uint8_t*)cd->bytes.p, (uint32_t*)d.counts->p, (uint32_t*)inflate_err->p + c, stream_);
-      auto rtiles = std::make_shared<DevBuf>();
-      rtiles->ensure((size_t)((npend + 1023) / 1024 + 2) * 8);
-      pq_launch_u32_scan((const uint32_t*)d.counts->p, (int64_t)npend, (uint64_t*)rtiles->p, (int32_t*)d.dr.offsets->p, stream_);
-      out.owners.push_back(rtiles);
-      // the total lands behind the descriptors in the same pinned block, STORED there by a one-lane kernel (pinned host memory is device
-      // addressable): a device → host copy command on this stream would hold the calling thread until the decompression before it is done
-      pq_launch_store_u32((const uint32_t*)((char*)d.dr.offsets->p + npend * 4), (uint32_t*)((char*)d.readback->p + ((npend * sizeof(PqPendingRuns) + 15) & ~(size_t)15) + 16), stream_);
-      HIP_CHECK(hipEventRecord(d.done, stream_));
-      deferred.push_back(std::move(d));
-      if (trace) trace_line(scan_id, "column %zu: the device walks the run headers of %zu pages (%.1f MB of index sections stay where they are)\n", c, npend, (double)pending_bytes / 1e6);
-      continue;
-    }
-    if (pending_bytes) {
-      // where they land: the chunk's own pinned slot, between its staged bytes and the page bodies read in place — a device-inflated chunk
-      // leaves that part (sized for host-inflated pages) unused; a chunk without the room gets a buffer of its own
-      Deferred d{c, cd, S, may_inflate, std::make_shared<PinnedBuf>(), get_event(), {}, {}, nullptr};
-      size_t spill = 0;
-      for (size_t si = 0; si < nsel; si++) {
-        const HostChunk& hc = chunks[c * nsel + si];
-        size_t need = 0;
-        for (const HostChunk::Pending& pe : hc.pending) need += ((pe.end - pe.begin) + 15) & ~(size_t)15;
-        const size_t lo = (hc.spos + 63) & ~(size_t)63, hi = slot_off[c][si + 1] - slot_off[c][si];
-        if (lo + need > hi) spill += need;
-      }
-      if (spill) d.readback->ensure(spill + 64);
-      size_t at = 0;
-      for (size_t si = 0; si < nsel; si++) {
-        const HostChunk& hc = chunks[c * nsel + si];
-        size_t need = 0;
-        for (const HostChunk::Pending& pe : hc.pending) need += ((pe.end - pe.begin) + 15) & ~(size_t)15;
-        const size_t lo = (hc.spos + 63) & ~(size_t)63, hi = slot_off[c][si + 1] - slot_off[c][si];
-        const bool in_slot = lo + need <= hi;
-        uint8_t* to = in_slot ? (uint8_t*)col_staged[c]->p + slot_off[c][si] + lo : (uint8_t*)d.readback->p + at;
-        if (!in_slot) at += need;
-        for (const HostChunk::Pending& pe : hc.pending) {
-          HIP_CHECK(hipMemcpyAsync(to, (char*)cd->bytes.p + slot_off[c][si] + S + pe.begin, pe.end - pe.begin, hipMemcpyDeviceToHost, stream_));
-          d.at.push_back(to);
-          to += ((pe.end - pe.begin) + 15) & ~(size_t)15;
-        }
-      }
-      HIP_CHECK(hipEventRecord(d.done, stream_));
-      deferred.push_back(std::move(d));
-      if (trace) trace_line(scan_id, "column %zu waits for %.1f MB of index sections from the device\n", c, (double)pending_bytes / 1e6);
-      continue;
-    }
-    finish_column(c, cd, S, may_inflate, nullptr);
+  vidx = std::make_shared<DevBuf>();
+  leaf_def.resize(ncol);
+  leaf_rep.resize(ncol);
+  leaf_raw_values.resize(ncol);
+}
+hipStream_t ParquetScan::next_group_stream() {
+  if (n_group_streams == 0) return stream_;
+  const size_t k = group_rr++ % (size_t)n_group_streams;
+  if (k >= group_streams.size()) {
+    hipStream_t x = detail::pool_get_stream(device_id_);
+    group_streams.push_back(x);
+    group_dirty.push_back(0);
+    HIP_CHECK(hipStreamWaitEvent(x, groups_may_start, 0));
   }
+  group_dirty[k] = 1;
+  return group_streams[k];
+}
+void ParquetScan::join_groups() {                  // stream_ runs behind every group launched so far
+  for (size_t k = 0; k < group_streams.size(); k++)
+    if (group_dirty[k]) {
+      hipEvent_t e = get_event();
+      HIP_CHECK(hipEventRecord(e, group_streams[k]));
+      HIP_CHECK(hipStreamWaitEvent(stream_, e, 0));
+      group_dirty[k] = 0;
+    }
+}
+
+// (a) of finishing a column: the chunks' tables (pages, runs, dictionaries) concatenated — offsets become column-global — and sent
+ParquetScan::ColumnTables ParquetScan::send_tables(const ColumnUpload& u, const DeviceRuns* dr) {
+  const size_t c = u.c, S = u.S;
+  ColumnDevice* cd = u.cd.get();
+  const ColumnPlan& cp = plans[c];
+  ColumnTables tb{};
+  size_t n_def = 0, n_dict = 0, n_doffs = 0, n_soffs = 0, n_jobs = 0, n_zjobs = 0, n_rep = 0;
+  for (size_t si = 0; si < nsel; si++) {
+    HostChunk& hc = chunks[c * nsel + si];
+    tb.any_optional |= hc.max_def > 0 && (!hc.no_nulls || cp.nested_leaf());      // (a nested leaf always keeps its levels: the assembly reads them)
+    tb.n_pages += hc.pages.size();
+    n_def += (hc.no_nulls && !cp.nested_leaf()) ? 0 : hc.def_runs.size();
+    n_rep += hc.rep_runs.size();
+    tb.n_idx += hc.idx_runs.size();
+    n_dict += (hc.dict_bytes.size() + 15) & ~(size_t)15;
+    n_doffs += hc.dict_offs.size();
+    n_soffs += hc.str_offs.size();
+    n_jobs += hc.inflate.size();
+    n_zjobs += hc.zinflate.size();
+  }
+  if ((n_jobs || n_zjobs) && !u.may_inflate) throw CometError("internal: device pages in a column without a decompression region");
+  if (trace) trace_line(scan_id, "column %zu host chunks ready at %.2f ms\n", c, ms_since());
+  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  tb.n_idx_dev = dr ? (size_t)dr->total : 0;      // runs the device writes behind the host's
+  size_t o = 0;
+  tb.off_pages = o; o = al(o + tb.n_pages * sizeof(PqPage));
+  tb.off_def = o; o = al(o + n_def * sizeof(PqRun) + 16);
+  tb.off_idx = o; o = al(o + (tb.n_idx + tb.n_idx_dev) * sizeof(PqRun) + 16);
+  tb.off_dict = o; o = al(o + n_dict + 16);
+  tb.off_doffs = o; o = al(o + n_doffs * 4 + 16);
+  tb.off_soffs = o; o = al(o + n_soffs * 8 + 16);
+  tb.off_rep = o; o = al(o + n_rep * sizeof(PqRun) + 16);
+  cd->h_tables.ensure(o + 16);
+  cd->tables.ensure(o + 16);
+  char* tb_h = (char*)cd->h_tables.p;
+  PqPage* P = (PqPage*)(tb_h + tb.off_pages);
+  PqRun* D = (PqRun*)(tb_h + tb.off_def);
+  PqRun* I = (PqRun*)(tb_h + tb.off_idx);
+  uint8_t* DB = (uint8_t*)(tb_h + tb.off_dict);
+  int32_t* DO = (int32_t*)(tb_h + tb.off_doffs);
+  int64_t* SO = (int64_t*)(tb_h + tb.off_soffs);
+  PqRun* RP = (PqRun*)(tb_h + tb.off_rep);
+  size_t ip = 0, id = 0, ii = 0, idb = 0, ido = 0, iso = 0, irp = 0;
+  for (size_t si = 0; si < nsel; si++) {
+    HostChunk& hc = chunks[c * nsel + si];
+    const int64_t base = (int64_t)slot_off[c][si];
+    // an offset into the chunk's slot of the staged region, or (flagged) of the device-decompressed region behind it
+    auto global_off = [&](int64_t v) { return (v & kInflatedBit) ? (v & ~kInflatedBit) + base + (int64_t)S : v + base; };
+    const bool nulls = hc.max_def > 0 && (!hc.no_nulls || cp.nested_leaf());
+    for (const PqPage& src : hc.pages) {
+      PqPage pg = src;
+      pg.row_start += ent_off[c][si];
+      pg.rep_run_first += (int32_t)irp;
+      pg.values_off = global_off(pg.values_off);
+      pg.str_first += (int64_t)iso;
+      if (nulls) pg.def_run_first += (int32_t)id;
+      else pg.def_run_first = pg.def_run_count = 0;
+      pg.idx_run_first += (int32_t)ii;
+      // (a dictionary the device inflated sits in the column's byte buffer: addressed from the dictionary table's base like the others)
+      pg.dict_off = hc.dev_dict >= 0 ? (int64_t)((char*)cd->bytes.p + base + (int64_t)S + hc.dev_dict - ((char*)cd->tables.p + tb.off_dict)) : (int64_t)idb;
+      pg.dict_offs_first = (int32_t)ido;
+      P[ip++] = pg;
+    }
+    if (nulls)
+      for (const PqRun& r : hc.def_runs) { D[id] = r; D[id].byte_off = global_off(r.byte_off); id++; }
+    for (const PqRun& r : hc.idx_runs) { I[ii] = r; I[ii].byte_off = global_off(r.byte_off); ii++; }
+    for (const PqRun& r : hc.rep_runs) { RP[irp] = r; RP[irp].byte_off = global_off(r.byte_off); irp++; }
+    // every index run (and PLAIN chunk) learns its page: the run-at-a-time kernel starts from the run
+    for (size_t gp = ip - hc.pages.size(); gp < ip; gp++)
+      for (int32_t r = P[gp].idx_run_first; r < P[gp].idx_run_first + P[gp].idx_run_count; r++) I[r].page = (int32_t)gp;
+    if (!hc.dict_bytes.empty()) memcpy(DB + idb, hc.dict_bytes.data(), hc.dict_bytes.size());
+    idb += (hc.dict_bytes.size() + 15) & ~(size_t)15;
+    if (!hc.dict_offs.empty()) memcpy(DO + ido, hc.dict_offs.data(), hc.dict_offs.size() * 4);
+    ido += hc.dict_offs.size();
+    for (int64_t v : hc.str_offs) SO[iso++] = v ? v + base : 0;
+  }
+  if (tb.n_pages >= ((size_t)1 << 31) || tb.n_idx + tb.n_idx_dev >= ((size_t)1 << 31)) throw CometError("parquet: too many pages / runs in one column");
+  upload(cd->tables.p, cd->h_tables.p, (o + 15) & ~(size_t)15);
+  upload_fence(stream_);
+  if (dr && dr->npend)      // the device-walked pages' runs go behind the host's; each such page's (first, count) is filled in on the device
+    pq_launch_write_runs((const PqPendingRuns*)dr->pend->p, dr->npend, (const uint8_t*)cd->bytes.p, (const int32_t*)dr->offsets->p, (int32_t)tb.n_idx,
+                         (PqRun*)((char*)cd->tables.p + tb.off_idx), (PqPage*)((char*)cd->tables.p + tb.off_pages), stream_);
+  // (the pages the device inflates: their pipeline was launched group by group while the slices crossed PCIe, launch_group)
+  if (n_jobs >= ((size_t)1 << 23)) throw CometError("parquet: too many pages in one column");
+  return tb;
+}
+
+// (b) of finishing a column: the decode kernels queued on stream_, the leaf's DeviceColumnView built
+void ParquetScan::queue_decode(const ColumnUpload& u, const ColumnTables& t) {
+  const size_t c = u.c;
+  ColumnDevice* cd = u.cd.get();
+  const ColumnPlan& cp = plans[c];
+  const bool is_string = cp.is_string, any_optional = t.any_optional;
+  const int64_t nrows = ent_total[c];           // the leaf's entries (a list's element leaf: more than the scan has rows)
+  auto values = std::make_shared<DevBuf>();
+  auto valid_bytes = std::make_shared<DevBuf>();
+  auto lengths = std::make_shared<DevBuf>();
+  const char* tb = (const char*)cd->tables.p;
+  PqDecodeArgs a;
+  memset(&a, 0, sizeof a);
+  a.pages = (const PqPage*)(tb + t.off_pages);
+  a.npages = (int32_t)t.n_pages;
+  a.max_def = any_optional ? std::max(cp.max_def, 1) : 0;      // (the validity kernel compares with it; every other kernel asks "> 0")
+  a.rep_runs = (const PqRun*)(tb + t.off_rep);
+  a.max_rep = cp.max_rep;
+  a.def_runs = (const PqRun*)(tb + t.off_def);
+  a.idx_runs = (const PqRun*)(tb + t.off_idx);
+  a.bytes = (const uint8_t*)cd->bytes.p;
+  a.dict = (const uint8_t*)(tb + t.off_dict);
+  a.dict_offs = (const int32_t*)(tb + t.off_doffs);
+  a.plain_str_offs = (const int64_t*)(tb + t.off_soffs);
+  a.n_rows = nrows;
+  a.out_width = cp.out_width;
+  a.n_idx_runs = (int32_t)(t.n_idx + t.n_idx_dev);
+  if (any_optional) {
+    valid_bytes->ensure((size_t)nrows + 16);
+    if (!vidx->p) vidx->ensure((size_t)nrows * 4 + 16);
+    a.valid_out = (uint8_t*)valid_bytes->p;
+    a.vidx = (uint32_t*)vidx->p;
+    pq_launch_validity(&a, stream_);
+    pq_launch_vidx(a.valid_out, nrows, (uint64_t*)tiles->p, a.vidx, stream_);
+  }
+  if (fields[c].nest != 0) {
+    leaf_def[c] = std::make_shared<DevBuf>();
+    leaf_def[c]->ensure((size_t)nrows + 16);
+    if (any_optional) pq_launch_levels(&a, 0, (uint8_t*)leaf_def[c]->p, stream_);
+    else HIP_CHECK(hipMemsetAsync(leaf_def[c]->p, cp.max_def, (size_t)nrows + 16, stream_));      // a chunk without level runs: everything defined
+    out.owners.push_back(leaf_def[c]);
+    if (fields[c].nest >= 2) {
+      leaf_rep[c] = std::make_shared<DevBuf>();
+      leaf_rep[c]->ensure((size_t)nrows + 16);
+      PqDecodeArgs ar = a;
+      if (!any_optional) ar.max_def = std::max(cp.max_def, 1);
+      pq_launch_levels(&ar, 1, (uint8_t*)leaf_rep[c]->p, stream_);
+      out.owners.push_back(leaf_rep[c]);
+    }
+  }
+  if (!is_string) {
+    values->ensure((size_t)nrows * cp.out_width + 16);
+    a.values_out = values->p;
+    // a fixed-width column is decoded a RUN at a time: a wave takes one bit-packed run / RLE run / chunk of a PLAIN page (the kept pieces of a
+    // pruned page have clipped units of their own, decode_chunk_host) and every lane decodes 8 of its values with all loads in flight at once
+    if (any_optional) {
+      // with NULLs a page's runs hold fewer values than it has rows: the values are decoded densely by their ordinal among the
+      // column's non-NULL values (vidx of the page's first row + index in the page), then spread to their rows
+      auto dense = std::make_shared<DevBuf>();
+      dense->ensure((size_t)nrows * cp.out_width + 16);
+      a.dense_out = dense->p;
+      pq_launch_decode_runs(&a, stream_);
+      pq_launch_expand_nulls(&a, stream_);
+      a.dense_out = nullptr;
+      out.owners.push_back(dense);
+    } else {
+      pq_launch_decode_runs(&a, stream_);
+    }
+  } else {
+    lengths->ensure((size_t)nrows * 4 + 16);
+    a.lengths_out = (uint32_t*)lengths->p;
+    pq_launch_string_lengths(&a, stream_);
+  }
+  DeviceColumnView cv;
+  if (is_string) {
+    auto offsets = std::make_shared<DevBuf>();
+    offsets->ensure((size_t)(nrows + 1) * 4 + 16);
+    pq_launch_u32_scan((const uint32_t*)lengths->p, nrows, (uint64_t*)tiles->p, (int32_t*)offsets->p, stream_);
+    int32_t total_bytes = 0;
+    ctx.read_small(&total_bytes, (char*)offsets->p + (size_t)nrows * 4, 4);
+    auto data = std::make_shared<DevBuf>();
+    data->ensure((size_t)std::max(total_bytes, 1) + 16);
+    a.str_offsets = (const int32_t*)offsets->p;
+    a.str_bytes_out = (uint8_t*)data->p;
+    pq_launch_string_copy(&a, stream_);
+    cv.data = offsets->p;
+    cv.aux = data->p;
+    out.owners.push_back(offsets);
+    out.owners.push_back(data);
+    out.owners.push_back(lengths);
+  } else if (lf_out.types[c].id == TypeId::Bool) {
+    auto bits = std::make_shared<DevBuf>();
+    bits->ensure((size_t)((nrows + 7) / 8) + 16);
+    pq_launch_pack((const uint8_t*)values->p, (uint8_t*)bits->p, nrows, stream_);
+    cv.data = bits->p;
+    out.owners.push_back(bits);
+    out.owners.push_back(values);
+  } else {
+    cv.data = values->p;
+    out.owners.push_back(values);
+    leaf_raw_values[c] = values;
+  }
+  if (any_optional) {
+    auto bm = std::make_shared<DevBuf>();
+    bm->ensure((size_t)((nrows + 7) / 8) + 16);
+    pq_launch_pack((const uint8_t*)valid_bytes->p, (uint8_t*)bm->p, nrows, stream_);
+    cv.valid = (const uint8_t*)bm->p;
+    lf_out.has_valid[c] = true;
+    out.owners.push_back(bm);
+  }
+  out.owners.push_back(valid_bytes);
+  lf_out.cols[c] = cv;
+}
+
+// everything behind a column's uploads.  A column with dictionary-encoded pages the DEVICE inflates comes here late — their run headers are
+// counted on the device or read back first (defer_behind_run_count, defer_behind_readback).
+void ParquetScan::finish_column(const ColumnUpload& u, const DeviceRuns* dr) {
+  const ColumnTables tb = send_tables(u, dr);
+  queue_decode(u, tb);
+}
+
+void ParquetScan::finish_counted(Deferred& d) {
+  int32_t total = 0;
+  memcpy(&total, (char*)d.readback->p + (((size_t)d.dr.npend * sizeof(PqPendingRuns) + 15) & ~(size_t)15) + 16, 4);
+  if (total < 0) throw CometError("parquet: too many runs in one column");
+  d.dr.total = total;
+  if (trace) trace_line(scan_id, "column %zu: %d runs counted on the device at %.2f ms\n", d.u.c, total, ms_since());
+  finish_column(d.u, &d.dr);
+  out.owners.push_back(d.dr.pend);
+  out.owners.push_back(d.dr.offsets);
+  out.owners.push_back(d.counts);
+  d.finished = true;
+}
+
+// all-NULL column: zeroed values, zeroed validity bitmap
+void ParquetScan::all_null_column(size_t c) {
+  const ColumnPlan& cp = plans[c];
+  DeviceColumnView mv;
+  auto zeros = std::make_shared<DevBuf>();
+  const size_t vb = cp.is_string ? (size_t)(total_rows + 1) * 4 : lf_out.types[c].id == TypeId::Bool ? (size_t)((total_rows + 7) / 8) : (size_t)total_rows * cp.out_width;
+  zeros->ensure(vb + 16);
+  HIP_CHECK(hipMemsetAsync(zeros->p, 0, vb + 16, stream_));
+  auto bm = std::make_shared<DevBuf>();
+  bm->ensure((size_t)((total_rows + 7) / 8) + 16);
+  HIP_CHECK(hipMemsetAsync(bm->p, 0, (size_t)((total_rows + 7) / 8) + 16, stream_));
+  mv.data = zeros->p;
+  mv.valid = (const uint8_t*)bm->p;
+  if (cp.is_string) mv.aux = zeros->p;   // no bytes are ever addressed (all offsets 0)
+  lf_out.has_valid[c] = true;
+  lf_out.cols[c] = mv;
+  out.owners.push_back(zeros);
+  out.owners.push_back(bm);
+  for (size_t si = 0; si < nsel; si++) wait_for(c * nsel + si);
+}
+
+// A copy costs ≈ 40–60 µs of submission and completion latency whatever its size (a 1 MB slice crosses in 20 µs), and one stream
+// carries them one after the other: a column of 60 small chunks spent more time between its copies than in them.  So pieces that are
+// READY and lie close together in the column's staging block cross as ONE copy — the bytes between them (a slot's unused tail) ride
+// along; a piece waits for company only while no thread would have to wait for it.
+void ParquetScan::flush_run(const ColumnUpload& u, GroupState& g, int w) {
+  if (g.pend_hi[w] > g.pend_lo[w]) upload((char*)u.cd->bytes.p + g.pend_lo[w], (char*)col_staged[u.c]->p + g.pend_lo[w], g.pend_hi[w] - g.pend_lo[w]);
+  g.pend_lo[w] = g.pend_hi[w] = 0;
+}
+void ParquetScan::push_piece(const ColumnUpload& u, GroupState& g, size_t lo, size_t hi) {
+  if (hi <= lo) return;
+  const int w = lo >= raw_base[u.c] ? 1 : 0;
+  if (g.pend_hi[w] > g.pend_lo[w] && lo >= g.pend_lo[w] && lo <= g.pend_hi[w] + kMergeGap) { g.pend_hi[w] = std::max(g.pend_hi[w], hi); return; }
+  flush_run(u, g, w);
+  g.pend_lo[w] = lo;
+  g.pend_hi[w] = hi;
+}
+
+// The decompression pipelines of the group's pages, up to chunk `si`, on the next group stream.
+// The pipelines' tables cross on the COPY stream, behind the page bytes; the group's stream is then fenced behind both and gets kernels
+// only.  (A host → device copy queued on a stream that waits for another stream's event holds the calling thread until that event has
+// happened: with the tables sent on the group's stream every launch here cost its task 7–10 ms — the time its page bytes needed to
+// cross — and eight concurrent tasks issued nothing else meanwhile: the first session of round 5, stage traces.)
+void ParquetScan::launch_group(const ColumnUpload& u, GroupState& g, size_t si) {
+  ColumnDevice* cd = u.cd.get();
+  if (g.jobs.size() >= ((size_t)1 << 23) || g.zjobs.size() >= ((size_t)1 << 23)) throw CometError("parquet: too many pages in one column");
+  const double t_launch = trace ? ms_since() : 0;
+  Snappy2Scratch* sn = nullptr;
+  Zstd2Scratch* zs = nullptr;
+  if (!g.jobs.empty()) {
+    cd->snappy2.emplace_back(new Snappy2Scratch());
+    sn = cd->snappy2.back().get();
+    sn->stage(g.jobs.data(), (int)g.jobs.size(), copy_stream);
+  }
+  if (!g.zjobs.empty()) {
+    cd->zstd2.emplace_back(new Zstd2Scratch());
+    zs = cd->zstd2.back().get();
+    zs->stage(g.zjobs.data(), (int)g.zjobs.size(), g.zblocks.data(), copy_stream);
+  }
+  hipStream_t gs = next_group_stream();
+  const double t_stream = trace ? ms_since() : 0;
+  upload_fence(gs);
+  const double t_fence = trace ? ms_since() : 0;
+  if (sn) sn->launch((uint8_t*)cd->bytes.p, (uint32_t*)inflate_err->p + u.c, gs);
+  if (zs) zs->launch((uint8_t*)cd->bytes.p, (uint32_t*)inflate_err->p + u.c, gs);
+  if (trace) trace_line(scan_id, "column %zu group of %zu snappy / %zu zstd pages (%zu blocks, %.1f MB) up to chunk %zu launched at %.2f ms\n", u.c, g.jobs.size(),
+                     g.zjobs.size(), g.zblocks.size(), (double)g.bytes / 1e6, si, ms_since());
+  if (trace && ms_since() - t_launch > 0.3)
+    trace_line(scan_id, "… that launch took %.2f ms of this thread (tables + stream %.2f, fence %.2f, kernels %.2f)\n", ms_since() - t_launch, t_stream - t_launch, t_fence - t_stream,
+               ms_since() - t_fence);
+  ctx.pages_inflated_on_device_ += (int64_t)(g.jobs.size() + g.zjobs.size());
+  g.jobs.clear();
+  g.zjobs.clear();
+  g.zblocks.clear();
+  g.bytes = 0;
+  g.zstd_chunks = 0;
+}
+
+// One column: its page bytes cross PCIe in slices as soon as their chunks are ready, on the copy stream; the pages the device decompresses are
+// launched for a GROUP of chunks as soon as their slices are across, so the pipeline runs while the column's later chunks are still being
+// read and uploaded (launched once per column it started only after the last slice: 7 ms of decompression behind 10 ms of upload, SF10 Q6).
+// Then one of three endings: the column is finished now, or behind a device run count, or behind a read-back of its index sections.
+void ParquetScan::upload_column(size_t c) {
+  const ColumnPlan& cp = plans[c];
+  if (all_missing[c]) { all_null_column(c); return; }
+  ColumnUpload u{c, std::make_shared<ColumnDevice>(), (raw_base[c] + raw_off[c][nsel] + 64 + 15) & ~(size_t)15, st.so.device_snappy && !cp.is_string && !cp.missing};
+  keep.push_back(u.cd);
+  const size_t S = u.S;
+  u.cd->bytes.ensure(u.may_inflate ? S + ((slot_off[c][nsel] + 64 + 15) & ~(size_t)15) + 64 : S);
+  GroupState g;
+  for (size_t si = 0; si < nsel; si++) {
+    {
+      bool ready;
+      { std::lock_guard<std::mutex> lk(prog->mu); ready = prog->done[c * nsel + si] != 0; }
+      // what is ready crosses while this thread waits — once it is worth a copy: a task with one scan thread gets its chunks one by one, and a
+      // hipMemcpyAsync per 0.7 MB chunk cost each of eight concurrent tasks 120 µs a call (profiles/r4_executor_hip_api.txt)
+      if (!ready && g.pending_piece_bytes() >= ((size_t)2 << 20)) { flush_run(u, g, 0); flush_run(u, g, 1); }
+    }
+    const double t_wait = trace ? ms_since() : 0;
+    (void)finish_counted_columns();
+    wait_for(c * nsel + si);
+    if (trace && ms_since() - t_wait > 0.3) trace_line(scan_id, "column %zu waited %.2f ms for chunk %zu (until %.2f ms)\n", c, ms_since() - t_wait, si, ms_since());
+    HostChunk& hc = chunks[c * nsel + si];
+    ctx.bytes_scanned_ += hc.compressed;
+    // only the bytes the chunk actually staged cross PCIe
+    if (hc.spos) push_piece(u, g, slot_off[c][si], slot_off[c][si] + std::min((hc.spos + 16 + 15) & ~(size_t)15, slot_off[c][si + 1] - slot_off[c][si]));
+    if (hc.raw_hi > hc.raw_lo) {      // page bodies read in place: from where pread() put them (+ the few bytes behind the last one the kernels' vector loads touch)
+      const size_t raw_end = raw_base[c] + raw_off[c][si + 1] - slot_off[c][si];      // slot-relative, like raw_lo / raw_hi
+      const size_t lo = hc.raw_lo & ~(size_t)15, hi = std::min((hc.raw_hi + 32 + 15) & ~(size_t)15, raw_end);
+      push_piece(u, g, slot_off[c][si] + lo, slot_off[c][si] + hi);
+    }
+    const int32_t first_block = (int32_t)g.zblocks.size();
+    g.zblocks.insert(g.zblocks.end(), hc.zblocks.begin(), hc.zblocks.end());
+    for (int z = 0; z < 2; z++)
+      for (const PqInflate& src : z ? hc.zinflate : hc.inflate) {
+        PqInflate job = src;
+        job.src_off += (int64_t)slot_off[c][si];
+        job.dst_off += (int64_t)slot_off[c][si] + (int64_t)S;
+        if (z) job.preamble += first_block;
+        (z ? g.zjobs : g.jobs).push_back(job);
+        g.bytes += (size_t)job.src_len;
+      }
+    // (a launch is a chain's latency however small it is: what is left of the column joins this group when it fits the GPU with it —
+    // judged by the blocks per chunk seen so far; kZGroupBlocks says why)
+    g.zstd_chunks += hc.zinflate.empty() ? 0 : 1;
+    const size_t zleft_est = g.zstd_chunks ? (nsel - 1 - si) * g.zblocks.size() / g.zstd_chunks : 0;
+    const bool zfull = g.zblocks.size() >= kZGroupBlocks && g.zblocks.size() + zleft_est > kZGroupBlocksHeld;
+    const size_t sgroup_bytes = few_threads ? kSGroupBytesFew : kSGroupBytesMany;
+    const bool group_full = (!g.jobs.empty() || !g.zjobs.empty()) && ((g.zjobs.empty() ? g.bytes >= sgroup_bytes : zfull) || si + 1 == nsel);
+    if (group_full || si + 1 == nsel) { flush_run(u, g, 0); flush_run(u, g, 1); }
+    if (group_full) launch_group(u, g, si);
+  }
+  // Dictionary-encoded pages the device inflates (zstd: their literals are entropy-coded, the host cannot look through the compressed stream
+  // as it does with snappy): the index sections come BACK once the device has inflated them — a few MB per column at PCIe speed — and the
+  // host reads the run headers out of them (the decoded values never come back).  Such a column is finished behind all uploads.
+  flush_run(u, g, 0);
+  flush_run(u, g, 1);
+  join_groups();
+  size_t pending_bytes = 0;
+  for (size_t si = 0; si < nsel; si++)
+    for (const HostChunk::Pending& pe : chunks[c * nsel + si].pending) pending_bytes += ((pe.end - pe.begin) + 15) & ~(size_t)15;
+  if (pending_bytes && st.so.device_runs) defer_behind_run_count(u, pending_bytes);
+  else if (pending_bytes) defer_behind_readback(u, pending_bytes);
+  else finish_column(u, nullptr);
+}
+
+// The device walks the run headers where the sections lie (device/pq_runs.hpp): one descriptor per page in the coordinates of the column's
+// byte buffer, a count pass, a prefix sum — and FOUR BYTES come back (the total, which sizes the run table) instead of the sections.
+void ParquetScan::defer_behind_run_count(const ColumnUpload& u, size_t pending_bytes) {
+  const size_t c = u.c, S = u.S;
+  Deferred d{u, std::make_shared<PinnedBuf>(), get_event(), {}, {}, nullptr};
+  size_t npend = 0, page_base = 0;
+  for (size_t si = 0; si < nsel; si++) npend += chunks[c * nsel + si].pending.size();
+  if (npend >= ((size_t)1 << 30)) throw CometError("parquet: too many pages in one column");
+  d.readback->ensure(npend * sizeof(PqPendingRuns) + 128);
+  PqPendingRuns* pd = (PqPendingRuns*)d.readback->p;
+  size_t k = 0;
+  for (size_t si = 0; si < nsel; si++) {
+    const HostChunk& hc = chunks[c * nsel + si];
+    for (const HostChunk::Pending& pe : hc.pending) {
+      PqPendingRuns& r = pd[k++];
+      r.begin = (int64_t)(slot_off[c][si] + S + pe.begin);
+      r.end = (int64_t)(slot_off[c][si] + S + pe.end);
+      r.bit_width = hc.pages[pe.page].bit_width;
+      r.max_values = pe.values;
+      r.page = (int32_t)(page_base + pe.page);      // column-global: the chunks' pages are concatenated in row-group order (send_tables)
+      r.pad = 0;
+    }
+    page_base += hc.pages.size();
+  }
+  d.dr.pend = std::make_shared<DevBuf>();
+  d.dr.offsets = std::make_shared<DevBuf>();
+  d.counts = std::make_shared<DevBuf>();
+  d.dr.pend->ensure(npend * sizeof(PqPendingRuns) + 16);
+  d.counts->ensure(npend * 4 + 16);
+  d.dr.offsets->ensure((npend + 1) * 4 + 16);
+  d.dr.npend = (int)npend;
+  // (descriptors on the copy stream, stream_ fenced behind it: no host → device copy on a stream that waits — see launch_group)
+  upload(d.dr.pend->p, pd, (npend * sizeof(PqPendingRuns) + 15) & ~(size_t)15);
+  upload_fence(stream_);
+  pq_launch_count_runs((const PqPendingRuns*)d.dr.pend->p, (int)npend, (const uint8_t*)u.cd->bytes.p, (uint32_t*)d.counts->p, (uint32_t*)inflate_err->p + c, stream_);
+  auto rtiles = std::make_shared<DevBuf>();
+  rtiles->ensure((size_t)((npend + 1023) / 1024 + 2) * 8);
+  pq_launch_u32_scan((const uint32_t*)d.counts->p, (int64_t)npend, (uint64_t*)rtiles->p, (int32_t*)d.dr.offsets->p, stream_);
+  out.owners.push_back(rtiles);
+  // the total lands behind the descriptors in the same pinned block, STORED there by a one-lane kernel (pinned host memory is device
+  // addressable): a device → host copy command on this stream would hold the calling thread until the decompression before it is done
+  pq_launch_store_u32((const uint32_t*)((char*)d.dr.offsets->p + npend * 4), (uint32_t*)((char*)d.readback->p + ((npend * sizeof(PqPendingRuns) + 15) & ~(size_t)15) + 16), stream_);
+  HIP_CHECK(hipEventRecord(d.done, stream_));
+  deferred.push_back(std::move(d));
+  if (trace) trace_line(scan_id, "column %zu: the device walks the run headers of %zu pages (%.1f MB of index sections stay where they are)\n", c, npend, (double)pending_bytes / 1e6);
+}
+
+// COMET_DEVICE_RUNS=0: the index sections come back to the host.  Where they land: the chunk's own pinned slot, between its staged bytes and
+// the page bodies read in place — a device-inflated chunk leaves that part (sized for host-inflated pages) unused; a chunk without the room
+// gets a buffer of its own
+void ParquetScan::defer_behind_readback(const ColumnUpload& u, size_t pending_bytes) {
+  const size_t c = u.c;
+  Deferred d{u, std::make_shared<PinnedBuf>(), get_event(), {}, {}, nullptr};
+  // (need: the chunk's sections, each padded to 16 bytes; in_slot: they fit behind what the chunk staged)
+  std::vector<size_t> need(nsel, 0), lo(nsel, 0);
+  std::vector<char> in_slot(nsel, 0);
+  size_t spill = 0;
+  for (size_t si = 0; si < nsel; si++) {
+    const HostChunk& hc = chunks[c * nsel + si];
+    for (const HostChunk::Pending& pe : hc.pending) need[si] += ((pe.end - pe.begin) + 15) & ~(size_t)15;
+    lo[si] = (hc.spos + 63) & ~(size_t)63;
+    in_slot[si] = lo[si] + need[si] <= slot_off[c][si + 1] - slot_off[c][si];
+    if (!in_slot[si]) spill += need[si];
+  }
+  if (spill) d.readback->ensure(spill + 64);
+  size_t at = 0;
+  for (size_t si = 0; si < nsel; si++) {
+    const HostChunk& hc = chunks[c * nsel + si];
+    uint8_t* to = in_slot[si] ? (uint8_t*)col_staged[c]->p + slot_off[c][si] + lo[si] : (uint8_t*)d.readback->p + at;
+    if (!in_slot[si]) at += need[si];
+    for (const HostChunk::Pending& pe : hc.pending) {
+      HIP_CHECK(hipMemcpyAsync(to, (char*)u.cd->bytes.p + slot_off[c][si] + u.S + pe.begin, pe.end - pe.begin, hipMemcpyDeviceToHost, stream_));
+      d.at.push_back(to);
+      to += ((pe.end - pe.begin) + 15) & ~(size_t)15;
+    }
+  }
+  HIP_CHECK(hipEventRecord(d.done, stream_));
+  deferred.push_back(std::move(d));
+  if (trace) trace_line(scan_id, "column %zu waits for %.1f MB of index sections from the device\n", c, (double)pending_bytes / 1e6);
+}
+
+// the run headers of every pending page, parsed on the scan threads (a chunk per task), positions in the coordinates of the
+// device-decompressed region — where the decode kernels will read the indices
+void ParquetScan::parse_returned_sections(Deferred& d) {
+  std::vector<std::exception_ptr> errs(nsel);
+  std::atomic<size_t> left{0};
+  std::mutex mu;
+  std::condition_variable cv;
+  size_t k = 0;
+  for (size_t si = 0; si < nsel; si++) {
+    HostChunk& hc = chunks[d.u.c * nsel + si];
+    if (hc.pending.empty()) continue;
+    const size_t first = k;
+    k += hc.pending.size();
+    left.fetch_add(1);
+    ScanPool::get().submit([&, si, first]() {
+      try {
+        HostChunk& h = chunks[d.u.c * nsel + si];
+        for (size_t j = 0; j < h.pending.size(); j++) {
+          const HostChunk::Pending& pe = h.pending[j];
+          PqPage& pg = h.pages[pe.page];
+          const uint8_t* base = d.at[first + j] - pe.begin;      // so that base + position addresses the byte
+          const size_t r0 = h.idx_runs.size();
+          parse_hybrid_runs(base, pe.begin, pe.end, pg.bit_width, pe.values, h.idx_runs);
+          for (size_t r = r0; r < h.idx_runs.size(); r++) h.idx_runs[r].byte_off |= kInflatedBit;
+          if (h.idx_runs.size() == r0) {   // page of NULLs only
+            PqRun r;
+            memset(&r, 0, sizeof r);
+            r.is_rle = 1;
+            r.count = pg.num_values;
+            h.idx_runs.push_back(r);
+          }
+          pg.idx_run_first = (int32_t)r0;
+          pg.idx_run_count = (int32_t)(h.idx_runs.size() - r0);
+        }
+      } catch (...) {
+        errs[si] = std::current_exception();
+      }
+      {
+        std::lock_guard<std::mutex> lk(mu);     // (notified under the lock: the waiter owns mu / cv and leaves their scope as soon as it sees zero)
+        left.fetch_sub(1);
+        cv.notify_all();
+      }
+    });
+  }
+  {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return left.load() == 0; });
+  }
+  for (auto& e : errs)
+    if (e) std::rethrow_exception(e);
+}
+
+void ParquetScan::finish_deferred() {
   if (trace && !deferred.empty()) trace_line(scan_id, "uploads of all columns issued at %.2f ms\n", ms_since());
-  while_waiting = nullptr;
   for (Deferred& d : deferred) {
     if (d.finished) continue;
     HIP_CHECK(hipEventSynchronize(d.done));
@@ -2987,212 +3107,180 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
       finish_counted(d);
       continue;
     }
-    if (trace) trace_line(scan_id, "column %zu index sections back at %.2f ms\n", d.c, ms_since());
-    // the run headers of every pending page, parsed on the scan threads (a chunk per task), positions in the coordinates of the
-    // device-decompressed region — where the decode kernels will read the indices
-    std::vector<std::exception_ptr> errs(nsel);
-    std::atomic<size_t> left{0};
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t k = 0;
-    for (size_t si = 0; si < nsel; si++) {
-      HostChunk& hc = chunks[d.c * nsel + si];
-      if (hc.pending.empty()) continue;
-      const size_t first = k;
-      k += hc.pending.size();
-      left.fetch_add(1);
-      ScanPool::get().submit([&, si, first]() {
-        try {
-          HostChunk& h = chunks[d.c * nsel + si];
-          for (size_t j = 0; j < h.pending.size(); j++) {
-            const HostChunk::Pending& pe = h.pending[j];
-            PqPage& pg = h.pages[pe.page];
-            const uint8_t* base = d.at[first + j] - pe.begin;      // so that base + position addresses the byte
-            const size_t r0 = h.idx_runs.size();
-            parse_hybrid_runs(base, pe.begin, pe.end, pg.bit_width, pe.values, h.idx_runs);
-            for (size_t r = r0; r < h.idx_runs.size(); r++) h.idx_runs[r].byte_off |= kInflatedBit;
-            if (h.idx_runs.size() == r0) {   // page of NULLs only
-              PqRun r;
-              memset(&r, 0, sizeof r);
-              r.is_rle = 1;
-              r.count = pg.num_values;
-              h.idx_runs.push_back(r);
-            }
-            pg.idx_run_first = (int32_t)r0;
-            pg.idx_run_count = (int32_t)(h.idx_runs.size() - r0);
-          }
-        } catch (...) {
-          errs[si] = std::current_exception();
-        }
-        {
-          std::lock_guard<std::mutex> lk(mu);     // (notified under the lock: the waiter owns mu / cv and leaves their scope as soon as it sees zero)
-          left.fetch_sub(1);
-          cv.notify_all();
-        }
-      });
-    }
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return left.load() == 0; });
-    }
-    for (auto& e : errs)
-      if (e) std::rethrow_exception(e);
-    if (trace) trace_line(scan_id, "column %zu run headers parsed at %.2f ms\n", d.c, ms_since());
-    finish_column(d.c, d.cd, d.S, d.may_inflate, nullptr);
+    if (trace) trace_line(scan_id, "column %zu index sections back at %.2f ms\n", d.u.c, ms_since());
+    parse_returned_sections(d);
+    if (trace) trace_line(scan_id, "column %zu run headers parsed at %.2f ms\n", d.u.c, ms_since());
+    finish_column(d.u, nullptr);
   }
   readback_guard.done = true;
-  // ---- the scan's columns from their leaves: a flat column is its leaf; a struct is its fields' columns under a validity of its own; a list
-  // is assembled from its element leaf's levels (rows start where the repetition level is 0, an entry holds an element slot from the
-  // repeated group's definition level on) ----
-  for (size_t t = 0; t < ntop; t++) {
-    const TopCol& tc = tops[t];
-    const size_t l0 = tc.first;
-    if (tc.kind == 0) {
-      out.cols[t] = lf_out.cols[l0];
-      out.has_valid[t] = lf_out.has_valid[l0];
-      continue;
-    }
-    DeviceColumnView nv;
-    if (tc.kind == 3) {
-      // A list of structs: its fields' leaves sit under ONE repeated group — the same repetition levels, the same element slots.  The first
-      // leaf's levels give the rows' offsets and validity and the entry of every slot; every field is then TAKEN out of its leaf's column over
-      // entries by those (exec.cpp take_column: any flat type), the element struct's validity is one more level comparison taken the same way.
-      const ColumnPlan& cp = plans[l0];
-      const int64_t n = ent_total[l0];
-      for (size_t l = l0; l < l0 + tc.count; l++)
-        if (ent_total[l] != n || !leaf_def[l] || !leaf_rep[l]) throw CometError("Parquet column '" + fields[l0].parent + "': the fields of its struct elements differ in their level entries");
-      auto starts = std::make_shared<DevBuf>(), elems = std::make_shared<DevBuf>(), start_idx = std::make_shared<DevBuf>(), elem_idx = std::make_shared<DevBuf>();
-      auto offsets = std::make_shared<DevBuf>(), lvb = std::make_shared<DevBuf>(), lbm = std::make_shared<DevBuf>(), evb = std::make_shared<DevBuf>(), entries = std::make_shared<DevBuf>();
-      starts->ensure((size_t)n * 4 + 16);
-      elems->ensure((size_t)n * 4 + 16);
-      start_idx->ensure((size_t)(n + 1) * 4 + 16);
-      elem_idx->ensure((size_t)(n + 1) * 4 + 16);
-      offsets->ensure((size_t)(total_rows + 1) * 4 + 16);
-      lvb->ensure((size_t)total_rows + 16);
-      lbm->ensure((size_t)((total_rows + 7) / 8) + 16);
-      evb->ensure((size_t)n + 16);
-      entries->ensure((size_t)n * 4 + 16);
-      const uint8_t* defp = (const uint8_t*)leaf_def[l0]->p;
-      const uint8_t* repp = (const uint8_t*)leaf_rep[l0]->p;
-      pq_launch_list_flags(defp, repp, n, cp.def_slot, (uint32_t*)starts->p, (uint32_t*)elems->p, stream_);
-      pq_launch_u32_scan((const uint32_t*)starts->p, n, (uint64_t*)tiles->p, (int32_t*)start_idx->p, stream_);
-      pq_launch_u32_scan((const uint32_t*)elems->p, n, (uint64_t*)tiles->p, (int32_t*)elem_idx->p, stream_);
-      pq_launch_list_assemble(defp, repp, n, total_rows, cp.def_parent, cp.def_slot, cp.max_def, (const int32_t*)start_idx->p, (const int32_t*)elem_idx->p, nullptr, 0,
-                              (int32_t*)offsets->p, (uint8_t*)lvb->p, (uint8_t*)evb->p, nullptr, (uint32_t*)inflate_err->p + l0, stream_);
-      pq_launch_pack((const uint8_t*)lvb->p, (uint8_t*)lbm->p, total_rows, stream_);
-      pq_launch_list_elem_entries(defp, n, cp.def_slot, (const int32_t*)elem_idx->p, (uint32_t*)entries->p, stream_);
-      int32_t nel = 0;
-      read_small(&nel, (char*)elem_idx->p + (size_t)n * 4, 4);
-      if (nel < 0 || nel > n) throw CometError("internal: list element count out of range");
-      DeviceColumnView sv;      // the element struct
-      for (size_t l = l0; l < l0 + tc.count; l++) {
-        bool khv = false;
-        sv.kids.push_back(take_column(lf_out.cols[l], lf_out.types[l], lf_out.has_valid[l], (const uint32_t*)entries->p, nullptr, nel, khv, out.owners));
-        sv.kid_has_valid.push_back(khv ? 1 : 0);
-      }
-      sv.kid_rows = nel;
-      const bool elem_nullable = cp.def_elem > cp.def_slot;
-      if (elem_nullable) {      // an optional element struct: NULL where the definition level stops short of it
-        auto sb = std::make_shared<DevBuf>(), st = std::make_shared<DevBuf>(), sbm = std::make_shared<DevBuf>();
-        sb->ensure((size_t)n + 16);
-        st->ensure((size_t)std::max(nel, 1) + 16);
-        sbm->ensure((size_t)((nel + 7) / 8) + 16);
-        pq_launch_level_ge(defp, n, cp.def_elem, (uint8_t*)sb->p, stream_);
-        if (nel > 0 && comet_launch_take(1, sb->p, (const uint32_t*)entries->p, nel, st->p, stream_) != 0) throw CometError("parquet: launch failed");
-        if (nel > 0) pq_launch_pack((const uint8_t*)st->p, (uint8_t*)sbm->p, nel, stream_);
-        sv.valid = (const uint8_t*)sbm->p;
-        for (auto& b : {sb, st, sbm}) out.owners.push_back(b);
-      }
-      HIP_CHECK(hipStreamSynchronize(stream_));      // (`entries` and the scratch arrays may go back to their pools)
-      nv.data = offsets->p;
-      nv.kids.push_back(sv);
-      nv.kid_has_valid.push_back(elem_nullable ? 1 : 0);
-      nv.kid_rows = nel;
-      if (cp.def_parent > 0) { nv.valid = (const uint8_t*)lbm->p; out.has_valid[t] = true; }
-      for (auto& b : {offsets, lbm}) out.owners.push_back(b);
-      out.cols[t] = nv;
-      continue;
-    }
-    if (tc.kind == 1) {
-      for (size_t l = l0; l < l0 + tc.count; l++) {
-        nv.kids.push_back(lf_out.cols[l]);
-        nv.kid_has_valid.push_back(lf_out.has_valid[l] ? 1 : 0);
-      }
-      nv.kid_rows = total_rows;
-      const int def_parent = plans[l0].def_parent;
-      if (def_parent > 0) {        // an optional struct: NULL where its fields' definition level stops short of it
-        auto vb = std::make_shared<DevBuf>(), bm = std::make_shared<DevBuf>();
-        vb->ensure((size_t)total_rows + 16);
-        bm->ensure((size_t)((total_rows + 7) / 8) + 16);
-        pq_launch_level_ge((const uint8_t*)leaf_def[l0]->p, total_rows, def_parent, (uint8_t*)vb->p, stream_);
-        pq_launch_pack((const uint8_t*)vb->p, (uint8_t*)bm->p, total_rows, stream_);
-        nv.valid = (const uint8_t*)bm->p;
-        out.has_valid[t] = true;
-        out.owners.push_back(vb);
-        out.owners.push_back(bm);
-      }
-    } else {
-      const ColumnPlan& cp = plans[l0];
-      const int64_t n = ent_total[l0];
-      const TypeId eid = lf_out.types[l0].id;
-      const bool by_take = eid == TypeId::String || eid == TypeId::Bytes || eid == TypeId::Bool;      // elements that are not one fixed-width value each
-      const int w = by_take ? 0 : cp.out_width;
-      if ((!by_take && !leaf_raw_values[l0]) || !leaf_def[l0] || !leaf_rep[l0]) throw CometError("internal: list column without its leaf's levels");
-      auto starts = std::make_shared<DevBuf>(), elems = std::make_shared<DevBuf>(), start_idx = std::make_shared<DevBuf>(), elem_idx = std::make_shared<DevBuf>();
-      auto offsets = std::make_shared<DevBuf>(), lvb = std::make_shared<DevBuf>(), lbm = std::make_shared<DevBuf>(), evb = std::make_shared<DevBuf>(), ebm = std::make_shared<DevBuf>(),
-           evals = std::make_shared<DevBuf>();
-      starts->ensure((size_t)n * 4 + 16);
-      elems->ensure((size_t)n * 4 + 16);
-      start_idx->ensure((size_t)(n + 1) * 4 + 16);
-      elem_idx->ensure((size_t)(n + 1) * 4 + 16);
-      offsets->ensure((size_t)(total_rows + 1) * 4 + 16);
-      lvb->ensure((size_t)total_rows + 16);
-      lbm->ensure((size_t)((total_rows + 7) / 8) + 16);
-      evb->ensure((size_t)n + 16);
-      ebm->ensure((size_t)((n + 7) / 8) + 16);
-      evals->ensure((size_t)n * (size_t)w + 16);
-      HIP_CHECK(hipMemsetAsync(evb->p, 0, (size_t)n + 16, stream_));
-      const uint8_t* defp = (const uint8_t*)leaf_def[l0]->p;
-      const uint8_t* repp = (const uint8_t*)leaf_rep[l0]->p;
-      pq_launch_list_flags(defp, repp, n, cp.def_slot, (uint32_t*)starts->p, (uint32_t*)elems->p, stream_);
-      pq_launch_u32_scan((const uint32_t*)starts->p, n, (uint64_t*)tiles->p, (int32_t*)start_idx->p, stream_);
-      pq_launch_u32_scan((const uint32_t*)elems->p, n, (uint64_t*)tiles->p, (int32_t*)elem_idx->p, stream_);
-      pq_launch_list_assemble(defp, repp, n, total_rows, cp.def_parent, cp.def_slot, cp.max_def, (const int32_t*)start_idx->p, (const int32_t*)elem_idx->p,
-                              by_take ? nullptr : (const uint8_t*)leaf_raw_values[l0]->p, w, (int32_t*)offsets->p, (uint8_t*)lvb->p, (uint8_t*)evb->p, (uint8_t*)evals->p,
-                              (uint32_t*)inflate_err->p + l0, stream_);
-      pq_launch_pack((const uint8_t*)lvb->p, (uint8_t*)lbm->p, total_rows, stream_);
-      DeviceColumnView ev;
-      nv.data = offsets->p;
-      if (by_take) {
-        // strings / booleans: the leaf's column over ENTRIES is a column like any other (offsets + bytes, or bits, + validity); the elements
-        // are its entries that hold a slot, taken in order (one small read tells how many there are)
-        auto entries = std::make_shared<DevBuf>();
-        entries->ensure((size_t)n * 4 + 16);
-        pq_launch_list_elem_entries(defp, n, cp.def_slot, (const int32_t*)elem_idx->p, (uint32_t*)entries->p, stream_);
-        int32_t nel = 0;
-        read_small(&nel, (char*)elem_idx->p + (size_t)n * 4, 4);
-        if (nel < 0 || nel > n) throw CometError("internal: list element count out of range");
-        bool ehv = false;
-        ev = take_column(lf_out.cols[l0], lf_out.types[l0], lf_out.has_valid[l0], (const uint32_t*)entries->p, nullptr, nel, ehv, out.owners);
-        HIP_CHECK(hipStreamSynchronize(stream_));      // (`entries` may go back to its pool)
-        nv.kids.push_back(ev);
-        nv.kid_has_valid.push_back(ehv ? 1 : 0);
-        nv.kid_rows = nel;
-      } else {
-        pq_launch_pack((const uint8_t*)evb->p, (uint8_t*)ebm->p, n, stream_);
-        ev.data = evals->p;
-        ev.valid = (const uint8_t*)ebm->p;
-        nv.kids.push_back(ev);
-        nv.kid_has_valid.push_back(cp.max_def > cp.def_slot ? 1 : 0);     // (elements can be NULL only if the element field is optional)
-        nv.kid_rows = n;                                                  // room for; offsets[rows] says how many there are
-      }
-      if (cp.def_parent > 0) { nv.valid = (const uint8_t*)lbm->p; out.has_valid[t] = true; }
-      for (auto& b : {starts, elems, start_idx, elem_idx, offsets, lvb, lbm, evb, ebm, evals}) out.owners.push_back(b);
-    }
-    out.cols[t] = nv;
+}
+
+// What every list column is assembled from, whatever its elements: the flags of its leaf's level entries (a row starts here / this entry
+// holds an element slot), their prefix sums, and from them the rows' offsets and validity (packed) and the elements' validity bytes.
+// `values` / `w` / `elem_values`: fixed-width elements are compacted out of the leaf's values over entries in the same pass.
+ParquetScan::ListShape ParquetScan::list_shape(size_t l0, bool clear_elem_valid, const uint8_t* values, int w, uint8_t* elem_values) {
+  const ColumnPlan& cp = plans[l0];
+  const int64_t n = ent_total[l0];
+  ListShape s{std::make_shared<DevBuf>(), std::make_shared<DevBuf>(), std::make_shared<DevBuf>(), std::make_shared<DevBuf>(),
+              std::make_shared<DevBuf>(), std::make_shared<DevBuf>(), std::make_shared<DevBuf>(), std::make_shared<DevBuf>()};
+  s.starts->ensure((size_t)n * 4 + 16);
+  s.elems->ensure((size_t)n * 4 + 16);
+  s.start_idx->ensure((size_t)(n + 1) * 4 + 16);
+  s.elem_idx->ensure((size_t)(n + 1) * 4 + 16);
+  s.offsets->ensure((size_t)(total_rows + 1) * 4 + 16);
+  s.lvb->ensure((size_t)total_rows + 16);
+  s.lbm->ensure((size_t)((total_rows + 7) / 8) + 16);
+  s.evb->ensure((size_t)n + 16);
+  if (clear_elem_valid) HIP_CHECK(hipMemsetAsync(s.evb->p, 0, (size_t)n + 16, stream_));
+  const uint8_t* defp = (const uint8_t*)leaf_def[l0]->p;
+  const uint8_t* repp = (const uint8_t*)leaf_rep[l0]->p;
+  pq_launch_list_flags(defp, repp, n, cp.def_slot, (uint32_t*)s.starts->p, (uint32_t*)s.elems->p, stream_);
+  pq_launch_u32_scan((const uint32_t*)s.starts->p, n, (uint64_t*)tiles->p, (int32_t*)s.start_idx->p, stream_);
+  pq_launch_u32_scan((const uint32_t*)s.elems->p, n, (uint64_t*)tiles->p, (int32_t*)s.elem_idx->p, stream_);
+  pq_launch_list_assemble(defp, repp, n, total_rows, cp.def_parent, cp.def_slot, cp.max_def, (const int32_t*)s.start_idx->p, (const int32_t*)s.elem_idx->p, values, w,
+                          (int32_t*)s.offsets->p, (uint8_t*)s.lvb->p, (uint8_t*)s.evb->p, elem_values, (uint32_t*)inflate_err->p + l0, stream_);
+  pq_launch_pack((const uint8_t*)s.lvb->p, (uint8_t*)s.lbm->p, total_rows, stream_);
+  return s;
+}
+
+// A list of structs: its fields' leaves sit under ONE repeated group — the same repetition levels, the same element slots.  The first
+// leaf's levels give the rows' offsets and validity and the entry of every slot; every field is then TAKEN out of its leaf's column over
+// entries by those (exec.cpp take_column: any flat type), the element struct's validity is one more level comparison taken the same way.
+// (Apart from list_column: the elements are always taken, there is a struct's validity to derive, and the scratch arrays are released
+// here — behind a stream sync — instead of travelling with the table.)
+DeviceColumnView ParquetScan::list_of_structs(size_t t) {
+  const TopCol& tc = tops[t];
+  const size_t l0 = tc.first;
+  const ColumnPlan& cp = plans[l0];
+  const int64_t n = ent_total[l0];
+  for (size_t l = l0; l < l0 + tc.count; l++)
+    if (ent_total[l] != n || !leaf_def[l] || !leaf_rep[l]) throw CometError("Parquet column '" + fields[l0].parent + "': the fields of its struct elements differ in their level entries");
+  ListShape s = list_shape(l0, false, nullptr, 0, nullptr);
+  const uint8_t* defp = (const uint8_t*)leaf_def[l0]->p;
+  auto entries = std::make_shared<DevBuf>();
+  entries->ensure((size_t)n * 4 + 16);
+  pq_launch_list_elem_entries(defp, n, cp.def_slot, (const int32_t*)s.elem_idx->p, (uint32_t*)entries->p, stream_);
+  int32_t nel = 0;
+  ctx.read_small(&nel, (char*)s.elem_idx->p + (size_t)n * 4, 4);
+  if (nel < 0 || nel > n) throw CometError("internal: list element count out of range");
+  DeviceColumnView sv;      // the element struct
+  for (size_t l = l0; l < l0 + tc.count; l++) {
+    bool khv = false;
+    sv.kids.push_back(ctx.take_column(lf_out.cols[l], lf_out.types[l], lf_out.has_valid[l], (const uint32_t*)entries->p, nullptr, nel, khv, out.owners));
+    sv.kid_has_valid.push_back(khv ? 1 : 0);
   }
-  // Hive partition columns: one constant per file (SparkPartitionedFile.partition_values, operator.proto:103-109), appended after
-  // the file columns (planner.rs:1558-1575); a NULL partition value clears the validity of its rows
+  sv.kid_rows = nel;
+  const bool elem_nullable = cp.def_elem > cp.def_slot;
+  if (elem_nullable) {      // an optional element struct: NULL where the definition level stops short of it
+    auto sb = std::make_shared<DevBuf>(), stk = std::make_shared<DevBuf>(), sbm = std::make_shared<DevBuf>();
+    sb->ensure((size_t)n + 16);
+    stk->ensure((size_t)std::max(nel, 1) + 16);
+    sbm->ensure((size_t)((nel + 7) / 8) + 16);
+    pq_launch_level_ge(defp, n, cp.def_elem, (uint8_t*)sb->p, stream_);
+    if (nel > 0 && comet_launch_take(1, sb->p, (const uint32_t*)entries->p, nel, stk->p, stream_) != 0) throw CometError("parquet: launch failed");
+    if (nel > 0) pq_launch_pack((const uint8_t*)stk->p, (uint8_t*)sbm->p, nel, stream_);
+    sv.valid = (const uint8_t*)sbm->p;
+    for (auto& b : {sb, stk, sbm}) out.owners.push_back(b);
+  }
+  HIP_CHECK(hipStreamSynchronize(stream_));      // (`entries` and the scratch arrays may go back to their pools)
+  DeviceColumnView nv;
+  nv.data = s.offsets->p;
+  nv.kids.push_back(sv);
+  nv.kid_has_valid.push_back(elem_nullable ? 1 : 0);
+  nv.kid_rows = nel;
+  if (cp.def_parent > 0) { nv.valid = (const uint8_t*)s.lbm->p; out.has_valid[t] = true; }
+  for (auto& b : {s.offsets, s.lbm}) out.owners.push_back(b);
+  return nv;
+}
+
+DeviceColumnView ParquetScan::struct_column(size_t t) {
+  const TopCol& tc = tops[t];
+  const size_t l0 = tc.first;
+  DeviceColumnView nv;
+  for (size_t l = l0; l < l0 + tc.count; l++) {
+    nv.kids.push_back(lf_out.cols[l]);
+    nv.kid_has_valid.push_back(lf_out.has_valid[l] ? 1 : 0);
+  }
+  nv.kid_rows = total_rows;
+  const int def_parent = plans[l0].def_parent;
+  if (def_parent > 0) {        // an optional struct: NULL where its fields' definition level stops short of it
+    auto vb = std::make_shared<DevBuf>(), bm = std::make_shared<DevBuf>();
+    vb->ensure((size_t)total_rows + 16);
+    bm->ensure((size_t)((total_rows + 7) / 8) + 16);
+    pq_launch_level_ge((const uint8_t*)leaf_def[l0]->p, total_rows, def_parent, (uint8_t*)vb->p, stream_);
+    pq_launch_pack((const uint8_t*)vb->p, (uint8_t*)bm->p, total_rows, stream_);
+    nv.valid = (const uint8_t*)bm->p;
+    out.has_valid[t] = true;
+    out.owners.push_back(vb);
+    out.owners.push_back(bm);
+  }
+  return nv;
+}
+
+// A list of flat elements: assembled from its element leaf's levels (rows start where the repetition level is 0, an entry holds an element
+// slot from the repeated group's definition level on).  Fixed-width elements are compacted by the assembly kernel itself (room for one per
+// entry, no host round trip, every scratch array travels with the table); strings and booleans are taken like a struct's fields.
+DeviceColumnView ParquetScan::list_column(size_t t) {
+  const size_t l0 = tops[t].first;
+  const ColumnPlan& cp = plans[l0];
+  const int64_t n = ent_total[l0];
+  const TypeId eid = lf_out.types[l0].id;
+  const bool by_take = eid == TypeId::String || eid == TypeId::Bytes || eid == TypeId::Bool;      // elements that are not one fixed-width value each
+  const int w = by_take ? 0 : cp.out_width;
+  if ((!by_take && !leaf_raw_values[l0]) || !leaf_def[l0] || !leaf_rep[l0]) throw CometError("internal: list column without its leaf's levels");
+  auto ebm = std::make_shared<DevBuf>(), evals = std::make_shared<DevBuf>();
+  ebm->ensure((size_t)((n + 7) / 8) + 16);
+  evals->ensure((size_t)n * (size_t)w + 16);
+  ListShape s = list_shape(l0, true, by_take ? nullptr : (const uint8_t*)leaf_raw_values[l0]->p, w, (uint8_t*)evals->p);
+  DeviceColumnView nv, ev;
+  nv.data = s.offsets->p;
+  if (by_take) {
+    // strings / booleans: the leaf's column over ENTRIES is a column like any other (offsets + bytes, or bits, + validity); the elements
+    // are its entries that hold a slot, taken in order (one small read tells how many there are)
+    auto entries = std::make_shared<DevBuf>();
+    entries->ensure((size_t)n * 4 + 16);
+    pq_launch_list_elem_entries((const uint8_t*)leaf_def[l0]->p, n, cp.def_slot, (const int32_t*)s.elem_idx->p, (uint32_t*)entries->p, stream_);
+    int32_t nel = 0;
+    ctx.read_small(&nel, (char*)s.elem_idx->p + (size_t)n * 4, 4);
+    if (nel < 0 || nel > n) throw CometError("internal: list element count out of range");
+    bool ehv = false;
+    ev = ctx.take_column(lf_out.cols[l0], lf_out.types[l0], lf_out.has_valid[l0], (const uint32_t*)entries->p, nullptr, nel, ehv, out.owners);
+    HIP_CHECK(hipStreamSynchronize(stream_));      // (`entries` may go back to its pool)
+    nv.kids.push_back(ev);
+    nv.kid_has_valid.push_back(ehv ? 1 : 0);
+    nv.kid_rows = nel;
+  } else {
+    pq_launch_pack((const uint8_t*)s.evb->p, (uint8_t*)ebm->p, n, stream_);
+    ev.data = evals->p;
+    ev.valid = (const uint8_t*)ebm->p;
+    nv.kids.push_back(ev);
+    nv.kid_has_valid.push_back(cp.max_def > cp.def_slot ? 1 : 0);     // (elements can be NULL only if the element field is optional)
+    nv.kid_rows = n;                                                  // room for; offsets[rows] says how many there are
+  }
+  if (cp.def_parent > 0) { nv.valid = (const uint8_t*)s.lbm->p; out.has_valid[t] = true; }
+  for (auto& b : {s.starts, s.elems, s.start_idx, s.elem_idx, s.offsets, s.lvb, s.lbm, s.evb, ebm, evals}) out.owners.push_back(b);
+  return nv;
+}
+
+// the scan's columns from their leaves: a flat column is its leaf; a struct is its fields' columns under a validity of its own; a list
+// is assembled from its leaves' levels
+void ParquetScan::assemble_nested() {
+  for (size_t t = 0; t < ntop; t++) {
+    switch (tops[t].kind) {
+      case TopKind::Flat:
+        out.cols[t] = lf_out.cols[tops[t].first];
+        out.has_valid[t] = lf_out.has_valid[tops[t].first];
+        break;
+      case TopKind::Struct: out.cols[t] = struct_column(t); break;
+      case TopKind::List: out.cols[t] = list_column(t); break;
+      case TopKind::ListOfStructs: out.cols[t] = list_of_structs(t); break;
+    }
+  }
+}
+
+// Hive partition columns: one constant per file (SparkPartitionedFile.partition_values, operator.proto:103-109), appended after
+// the file columns (planner.rs:1558-1575); a NULL partition value clears the validity of its rows
+void ParquetScan::partition_columns() {
   for (size_t p = 0; p < npart; p++) {
     const DType& t = op.partition_schema[p].dtype;
     const bool is_str = t.id == TypeId::String || t.id == TypeId::Bytes;
@@ -3229,9 +3317,9 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
         auto dv = std::make_shared<DevBuf>();
         dv->ensure((size_t)std::max(len, 1) + 16);
         if (len) {
-          small_host_.ensure(4096);
+          ctx.small_host_.ensure(4096);
           if (len > 2048) throw CometError("parquet: partition string value longer than 2048 bytes");
-          write_small(dv->p, lit.lit_bytes.data(), (size_t)len);
+          ctx.write_small(dv->p, lit.lit_bytes.data(), (size_t)len);
         }
         lit_keep.push_back(dv);
         if (comet_launch_fill_utf8((int32_t*)vals->p + sel.row_off, (uint8_t*)bytes->p, sel.rows, (int32_t)str_pos, len, (const uint8_t*)dv->p, stream_) != 0)
@@ -3241,11 +3329,11 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
         unsigned char raw[16] = {0};
         switch (t.id) {
           case TypeId::Bool: raw[0] = lit.lit_bool ? 1 : 0; break;
-          case TypeId::Int8: { int8_t x = (int8_t)lit.lit_i64; memcpy(raw, &x, 1); break; }
-          case TypeId::Int16: { int16_t x = (int16_t)lit.lit_i64; memcpy(raw, &x, 2); break; }
-          case TypeId::Int32: case TypeId::Date: { int32_t x = (int32_t)lit.lit_i64; memcpy(raw, &x, 4); break; }
+          case TypeId::Int8: { int8_t v = (int8_t)lit.lit_i64; memcpy(raw, &v, 1); break; }
+          case TypeId::Int16: { int16_t v = (int16_t)lit.lit_i64; memcpy(raw, &v, 2); break; }
+          case TypeId::Int32: case TypeId::Date: { int32_t v = (int32_t)lit.lit_i64; memcpy(raw, &v, 4); break; }
           case TypeId::Int64: case TypeId::Timestamp: case TypeId::TimestampNtz: memcpy(raw, &lit.lit_i64, 8); break;
-          case TypeId::Float: { float x = (float)lit.lit_f64; memcpy(raw, &x, 4); break; }
+          case TypeId::Float: { float v = (float)lit.lit_f64; memcpy(raw, &v, 4); break; }
           case TypeId::Double: memcpy(raw, &lit.lit_f64, 8); break;
           case TypeId::Decimal: memcpy(raw, &lit.lit_dec, 16); break;
           default: throw CometError("parquet: partition column of type " + t.str() + " is not supported by the GPU scan yet");
@@ -3278,6 +3366,23 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
     out.owners.push_back(vbytes);
     out.cols[ntop + p] = cv;
   }
+}
+
+void ParquetScan::check_device_errors() {
+  std::vector<uint32_t> ierr(ncol, 0);
+  for (size_t c0 = 0; c0 < ncol; c0 += 512) {   // read_small carries up to 4 KiB
+    const size_t n = std::min<size_t>(512, ncol - c0);
+    ctx.read_small(ierr.data() + c0, (char*)inflate_err->p + c0 * 4, n * 4);
+  }
+  for (size_t c = 0; c < ncol; c++) {
+    if (ierr[c] == 0xD1u) throw CometError("Parquet column '" + fields[c].parent + "': the list's repetition levels do not add up to the row group's rows");
+    if (ierr[c]) throw CometError("Parquet column '" + fields[c].name + "': corrupt compressed data page (device decompression, page job " +
+                                  std::to_string(ierr[c] >> 8) + ", code " + std::to_string(ierr[c] & 0xff) + ")");
+  }
+}
+
+// wait for the device, read the error words, then let go of everything in the order that is cheapest on the query's critical path
+DevTable ParquetScan::epilogue() {
   if (trace) trace_line(scan_id, "all launches issued at %.2f ms\n", ms_since());
   if (trace) trace_line(scan_id, "scan threads spent %.2f ms on chunks: %.2f reading, %.2f walking zstd frames, %.2f inflating pages\n", (double)g_ns_chunk.exchange(0) / 1e6,
                      (double)g_ns_read.exchange(0) / 1e6, (double)g_ns_walk.exchange(0) / 1e6, (double)g_ns_inflate.exchange(0) / 1e6);
@@ -3289,18 +3394,7 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
     trace_line(scan_id, "pool misses while this scan ran (process-wide): %lld hipMalloc (%.2f ms), %lld hipHostMalloc (%.2f ms)\n", (long long)(miss1[0] - miss0[0]),
                (double)(miss1[1] - miss0[1]) / 1e6, (long long)(miss1[2] - miss0[2]), (double)(miss1[3] - miss0[3]) / 1e6);
   }
-  {
-    std::vector<uint32_t> ierr(ncol, 0);
-    for (size_t c0 = 0; c0 < ncol; c0 += 512) {   // read_small carries up to 4 KiB
-      const size_t n = std::min<size_t>(512, ncol - c0);
-      read_small(ierr.data() + c0, (char*)inflate_err->p + c0 * 4, n * 4);
-    }
-    for (size_t c = 0; c < ncol; c++) {
-      if (ierr[c] == 0xD1u) throw CometError("Parquet column '" + fields[c].parent + "': the list's repetition levels do not add up to the row group's rows");
-      if (ierr[c]) throw CometError("Parquet column '" + fields[c].name + "': corrupt compressed data page (device decompression, page job " +
-                                    std::to_string(ierr[c] >> 8) + ", code " + std::to_string(ierr[c] & 0xff) + ")");
-    }
-  }
+  check_device_errors();
   out.owners.push_back(tiles);
   out.owners.push_back(vidx);
   // staging buffers can go back to the pools now that the stream is idle
@@ -3317,7 +3411,26 @@ DevTable ExecutionContext::scan_parquet(const Operator& op) {
   if (trace) trace_line(scan_id, "staging released at %.2f ms\n", ms_since());
   sels.clear();
   if (trace) trace_line(scan_id, "files closed at %.2f ms\n", ms_since());
-  return out;
+  return std::move(out);
+}
+
+DevTable ExecutionContext::scan_parquet(const Operator& op) {
+  ParquetScan s(*this, op);
+  s.collect_leaves();
+  if (op.files.empty()) return std::move(s.out);   // EmptyExec (planner.rs:1548-1556)
+  if (op.encryption_enabled) throw CometError("Parquet modular encryption is not supported by the GPU scan");
+  if (op.default_values.size() != op.default_values_indexes.size()) throw CometError("NativeScan: default_values and default_values_indexes differ in length");
+  s.st = resolve_settings(op, config_);
+  if (!s.select()) return std::move(s.out);
+  s.lay_out();
+  s.place_decompression();
+  s.start_host_stage();
+  s.open_streams();
+  for (size_t c : s.order) s.upload_column(c);
+  s.finish_deferred();
+  s.assemble_nested();
+  s.partition_columns();
+  return s.epilogue();
 }
 
 }  // namespace comet

@@ -99,13 +99,8 @@ extern "C" void pq_launch_snappy_fallback(const PqInflate* jobs, int njobs, uint
   hipLaunchKernelGGL(pq_snappy_fallback_kernel, njobs, 64, 0, (hipStream_t)st, jobs, njobs, bytes, status, err);
 }
 
-extern "C" void pq_launch_snappy(const PqInflate* jobs, int njobs, uint8_t* bytes, uint32_t* err, void* st) {
-  if (njobs <= 0) return;
-  hipLaunchKernelGGL(pq_snappy_kernel, njobs, 64, 0, (hipStream_t)st, jobs, njobs, bytes, err);
-}
-
 // Diagnostic / test entry (include/comet_amd.h): decompress `npages` raw snappy streams held in host memory with the kernel above and
-// return the pages to host memory.  Not a data path — the scan calls pq_launch_snappy on buffers that are already in HBM.  Returns 0, or
+// return the pages to host memory.  Not a data path — the scan inflates pages with the multi-kernel pipeline (snappy2_kernels.hip) on buffers that are already in HBM.  Returns 0, or
 // (page << 8 | code) of the first page that failed, or -1 for a HIP error; *kernel_ms = the kernel's time by HIP events.
 extern "C" int64_t comet_snappy_inflate_pages(const uint8_t* streams, const int64_t* stream_off, const int32_t* stream_len, const int32_t* page_len,
                                               int32_t npages, uint8_t* out, const int64_t* out_off, int32_t device_id, double* kernel_ms) {
