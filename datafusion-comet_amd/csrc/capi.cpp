@@ -494,16 +494,24 @@ static std::string json_str(const std::string& s) {
 int64_t comet_plan_codegen(const uint8_t* plan, size_t plan_len, const uint8_t* has_valid, int32_t n_valid, char* out, int64_t cap) {
   return guarded(nullptr, (int64_t)-2, [&]() -> int64_t {
     OperatorP op = decode_operator(plan, plan_len);
-    const Operator* leaf = op.get();
-    while (!leaf->children.empty()) leaf = leaf->children[0].get();
-    if (leaf->kind != OpKind::Scan) throw CometError("comet_plan_codegen: a Filter / Projection / HashAggregate chain over ONE Scan leaf is expected");
-    // (a source with struct / list columns: the chain sees their fields and elements as columns behind the real ones, like over a materialised source)
-    bool nested = false;
-    for (auto& t : leaf->scan_fields) nested = nested || t.is_nested();
-    const std::vector<DType> types = nested ? extend_struct_field_types(leaf->scan_fields) : leaf->scan_fields;
-    std::vector<bool> hv(types.size(), false);
-    for (int32_t k = 0; k < n_valid && (size_t)k < hv.size(); k++) hv[(size_t)k] = has_valid && has_valid[k] != 0;
-    PipelineDesc d = nested ? generate_pipeline(*op, hv, &types) : generate_pipeline(*op, hv);
+    PipelineDesc d;
+    if (op->kind == OpKind::HashJoin) {
+      // a join over two Scan leaves (or chains over them): fused as createPlan decides, has_valid over the left source's columns, then the right source's
+      std::vector<bool> hv((size_t)std::max(n_valid, 0), false);
+      for (size_t k = 0; k < hv.size(); k++) hv[k] = has_valid && has_valid[k] != 0;
+      d = ExecutionContext::join_codegen(op, plan_bytes_hash(plan, plan_len), hv);
+    } else {
+      const Operator* leaf = op.get();
+      while (!leaf->children.empty()) leaf = leaf->children[0].get();
+      if (leaf->kind != OpKind::Scan) throw CometError("comet_plan_codegen: a Filter / Projection / HashAggregate chain over ONE Scan leaf is expected");
+      // (a source with struct / list columns: the chain sees their fields and elements as columns behind the real ones, like over a materialised source)
+      bool nested = false;
+      for (auto& t : leaf->scan_fields) nested = nested || t.is_nested();
+      const std::vector<DType> types = nested ? extend_struct_field_types(leaf->scan_fields) : leaf->scan_fields;
+      std::vector<bool> hv(types.size(), false);
+      for (int32_t k = 0; k < n_valid && (size_t)k < hv.size(); k++) hv[(size_t)k] = has_valid && has_valid[k] != 0;
+      d = nested ? generate_pipeline(*op, hv, &types) : generate_pipeline(*op, hv);
+    }
     std::string j = "{\"sink\":" + std::to_string((int)d.sink) + ",\"has_filter\":" + (d.has_filter ? "true" : "false") + ",\"R\":" + std::to_string(d.R) + ",\"derived\":" + std::to_string(d.derived.size()) +
                     ",\"kernels\":[";
     for (size_t k = 0; k < d.kernels.size(); k++) j += (k ? "," : "") + json_str(d.kernels[k]);

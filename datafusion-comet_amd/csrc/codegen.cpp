@@ -3235,15 +3235,7 @@ std::vector<const Operator*> collect_chain(const Operator& root, bool has_source
 
 std::vector<ExprP> bound_columns(const std::vector<DType>& types) {
   std::vector<ExprP> cols;
-  for (size_t i = 0; i < types.size(); i++) {
-    auto b = std::make_shared<Expr>();
-    b->kind = ExprKind::Bound;
-    b->proto_tag = 3;
-    b->bound_index = (int)i;
-    b->dtype = types[i];
-    b->has_dtype = true;
-    cols.push_back(b);
-  }
+  for (size_t i = 0; i < types.size(); i++) cols.push_back(bound((int)i, types[i]));
   return cols;
 }
 
@@ -4330,23 +4322,37 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
 // generate_join: key hashing / equality / residual condition / output gather functor for the hash-join templates
 // (join_build_body, join_count_body, join_emit_body).  Reference: planner.rs:2192-2266, :2415-2555.
 // ---------------------------------------------------------------------------------------------
+ExprP bound(int idx, const DType& t) {
+  auto b = std::make_shared<Expr>();
+  b->kind = ExprKind::Bound;
+  b->proto_tag = 3;
+  b->bound_index = idx;
+  b->dtype = t;
+  b->has_dtype = true;
+  return b;
+}
+
+ExprP shift_bound(const ExprP& e, int by, int from) {
+  if (e->kind == ExprKind::Bound) {
+    if (e->bound_index < from) return e;
+    auto n = std::make_shared<Expr>(*e);
+    n->bound_index = e->bound_index + by;
+    return n;
+  }
+  if (e->children.empty()) return e;
+  auto n = std::make_shared<Expr>(*e);
+  for (auto& c : n->children) c = shift_bound(c, by, from);
+  return n;
+}
+
 void fold_chain(const Operator& top, const Operator& source, const std::vector<DType>& source_types, std::vector<ExprP>& cols, std::vector<ExprP>& preds) {
   std::vector<const Operator*> chain;
   for (const Operator* cur = &top; cur != &source; cur = cur->children[0].get()) {
     if ((cur->kind != OpKind::Filter && cur->kind != OpKind::Projection) || cur->children.size() != 1) throw CometError("internal: fold_chain over a non-chain");
     chain.push_back(cur);
   }
-  cols.clear();
+  cols = bound_columns(source_types);
   preds.clear();
-  for (size_t i = 0; i < source_types.size(); i++) {
-    auto b = std::make_shared<Expr>();
-    b->kind = ExprKind::Bound;
-    b->proto_tag = 3;
-    b->bound_index = (int)i;
-    b->dtype = source_types[i];
-    b->has_dtype = true;
-    cols.push_back(b);
-  }
   for (int i = (int)chain.size() - 1; i >= 0; i--) {
     const Operator& op = *chain[(size_t)i];
     std::map<const Expr*, ExprP> memo;
@@ -4361,132 +4367,99 @@ void fold_chain(const Operator& top, const Operator& source, const std::vector<D
   }
 }
 
-PipelineDesc generate_join(const Operator& j, const std::vector<DType>& lt_in, const std::vector<DType>& rt_in, const std::vector<bool>& lvalid_in,
-                           const std::vector<bool>& rvalid_in, const JoinFusion* fu, const JoinFusion* fub) {
-  if (j.kind != OpKind::HashJoin) throw CometError("internal: generate_join on a non-join");
-  if (j.left_keys.size() != j.right_keys.size() || j.left_keys.empty()) throw CometError("HashJoin needs matching, non-empty key lists");
-  int mode = 0;
+namespace {
+// the functors of R = 1 kernels (joins, sort keys) address row 0 of the per-thread row arrays
+std::string row0(std::string text) {
+  for (size_t p0 = text.find("[r]"); p0 != std::string::npos; p0 = text.find("[r]")) text.replace(p0, 3, "[0]");
+  return text;
+}
+
+// one functor of P: the statements `g` gathered, then `tail` (a return statement, stores)
+void write_fn(std::ostream& src, const std::string& signature, const Gen& g, const std::string& tail) {
+  src << "  static __device__ __forceinline__ " << signature << " {\n    bool k[R] = {true};\n" << g.decls << g.body() << tail << "  }\n";
+}
+
+// What the join type and the build side make of the kernel templates' switches
+struct JoinShape {
+  int mode = 0;                                 // P::MODE: 0 all pairs, 1 semi, 2 anti
   bool keep_left = false, keep_right = false;   // outer joins: which side's unmatched rows survive
-  switch (j.join_type) {
-    case JoinType::Inner: break;
-    case JoinType::LeftSemi: mode = 1; break;
-    case JoinType::LeftAnti: mode = 2; break;
-    case JoinType::LeftOuter: keep_left = true; break;
-    case JoinType::RightOuter: keep_right = true; break;
-    case JoinType::FullOuter: keep_left = keep_right = true; break;
-    default: throw CometError("HashJoin type " + std::to_string((int)j.join_type) + " is not supported by the MI355X native engine yet");
-  }
-  if (j.null_aware_anti) throw CometError("null-aware anti join is not supported by the MI355X native engine yet");
-  const bool build_left = j.build_side == BuildSide::Left;
-  // LeftSemi / LeftAnti built on the LEFT: the output is a subset of the BUILD rows — the probe pass only marks the build rows
-  // it matched (all of them: MODE 0 walks the whole chain), the tail pass then emits the marked (semi) or unmarked (anti) ones
-  const bool build_only = mode != 0 && build_left;
-  const bool keep_matched = build_only && mode == 1;
-  if (build_only) mode = 0;
-  const bool outer_probe = !build_only && (build_left ? keep_right : keep_left);    // the probe side is the preserved one
-  const bool outer_build = build_only || (build_left ? keep_left : keep_right);
-  // The build side: the materialised child — or (round 6), with a fused BUILD chain (fub), the chain's SOURCE table: build rows are source rows, the chain's
-  // Filters are part of P::bvalid (a row that fails them is in no table, no bitmap and no outer join's tail: P::bkeep), its columns expressions over the source.
-  const std::vector<DType>& bt = fub ? fub->src_types : (build_left ? lt_in : rt_in);
-  const std::vector<bool>& bv_src = fub ? fub->src_valid : (build_left ? lvalid_in : rvalid_in);
-  if (fub && bt.size() != bv_src.size()) throw CometError("internal: fused build source validity arity mismatch");
-  std::vector<bool> bv(bv_src);
-  if (fub)
-    for (auto& p : fub->preds)
-      if (p->kind == ExprKind::IsNotNull && p->children.size() == 1 && p->children[0]->kind == ExprKind::Bound && p->children[0]->bound_index >= 0 &&
-          (size_t)p->children[0]->bound_index < bv.size())
-        bv[(size_t)p->children[0]->bound_index] = false;
-  // The probe side: the materialised child — or, with a fused probe chain (JoinFusion), the chain's SOURCE table; the child's columns
-  // are then expressions over the source columns (fu->cols), its Filters conjuncts over them (fu->preds, P::pkeep).
-  const std::vector<DType>& pt = fu ? fu->src_types : (build_left ? rt_in : lt_in);      // PHYSICAL probe columns
-  const std::vector<bool>& pv_src = fu ? fu->src_valid : (build_left ? rvalid_in : lvalid_in);
-  if (fu && pt.size() != pv_src.size()) throw CometError("internal: fused probe source validity arity mismatch");
-  // a fused chain's isnotnull(<source column>) conjuncts: every probe row that passes P::pkeep holds a value there — keys, condition and output read
-  // no validity bit of such a column (P::pkeep itself still does)
-  std::vector<bool> pv(pv_src);
-  if (fu)
-    for (auto& p : fu->preds)
-      if (p->kind == ExprKind::IsNotNull && p->children.size() == 1 && p->children[0]->kind == ExprKind::Bound && p->children[0]->bound_index >= 0 &&
-          (size_t)p->children[0]->bound_index < pv.size())
-        pv[(size_t)p->children[0]->bound_index] = false;
-  const int nb = (int)bt.size(), np = (int)pt.size();
-  const int nprobe_logical = fu ? (int)fu->cols.size() : np;
-  const int nbuild_logical = fub ? (int)fub->cols.size() : nb;
-  const int nl = build_left ? nbuild_logical : nprobe_logical, nr = build_left ? nprobe_logical : nbuild_logical;
-  if (nb + np > COMET_MAX_IN) throw CometError("too many columns for one GPU hash join");
-  const std::vector<ExprP>& bkeys_logical = build_left ? j.left_keys : j.right_keys;
-  const std::vector<ExprP>& pkeys_logical = build_left ? j.right_keys : j.left_keys;
-  std::vector<ExprP> pkeys, bkeys;
-  {
-    std::map<const Expr*, ExprP> memo;
-    for (auto& k : pkeys_logical) pkeys.push_back(fu ? substitute(k, fu->cols, memo) : k);
-  }
-  {
-    std::map<const Expr*, ExprP> memo;
-    for (auto& k : bkeys_logical) bkeys.push_back(fub ? substitute(k, fub->cols, memo) : k);
-  }
-  // physical combined schema = kernel argument order: build columns (row i), then probe columns (row j)
-  std::vector<DType> ct(bt);
-  ct.insert(ct.end(), pt.begin(), pt.end());
-  std::vector<bool> cv(bv);
-  cv.insert(cv.end(), pv.begin(), pv.end());
-  auto locate_combined = [=](int c) { return std::make_pair(c, std::string(c < nb ? "i" : "j")); };
-  auto mk_bound = [](int idx, const DType& t) {
-    auto b = std::make_shared<Expr>();
-    b->kind = ExprKind::Bound;
-    b->proto_tag = 3;
-    b->bound_index = idx;
-    b->dtype = t;
-    b->has_dtype = true;
-    return ExprP(b);
-  };
-  std::function<ExprP(const ExprP&, int)> shift_bound = [&](const ExprP& e, int by) -> ExprP {
-    if (e->kind == ExprKind::Bound) {
-      auto n = std::make_shared<Expr>(*e);
-      n->bound_index = e->bound_index + by;
-      return n;
+  bool build_left, build_only, keep_matched, outer_probe, outer_build, dedup_build;
+  const char* name;                             // in the explain text
+
+  explicit JoinShape(const Operator& j) {
+    switch (j.join_type) {
+      case JoinType::Inner: break;
+      case JoinType::LeftSemi: mode = 1; break;
+      case JoinType::LeftAnti: mode = 2; break;
+      case JoinType::LeftOuter: keep_left = true; break;
+      case JoinType::RightOuter: keep_right = true; break;
+      case JoinType::FullOuter: keep_left = keep_right = true; break;
+      default: throw CometError("HashJoin type " + std::to_string((int)j.join_type) + " is not supported by the MI355X native engine yet");
     }
-    if (e->children.empty()) return e;
-    auto n = std::make_shared<Expr>(*e);
-    for (auto& c : n->children) c = shift_bound(c, by);
-    return n;
-  };
-  // logical column c of left ++ right (what keys, condition and output refer to) as an expression over the physical schema
-  std::vector<ExprP> phys;
-  for (int c = 0; c < nl + nr; c++) {
-    const bool is_left = c < nl;
-    const int local = is_left ? c : c - nl;
-    if (is_left == build_left) phys.push_back(fub ? fub->cols[(size_t)local] : mk_bound(local, bt[(size_t)local]));
-    else if (!fu) phys.push_back(mk_bound(nb + local, pt[(size_t)local]));
-    else phys.push_back(shift_bound(fu->cols[(size_t)local], nb));
+    if (j.null_aware_anti) throw CometError("null-aware anti join is not supported by the MI355X native engine yet");
+    build_left = j.build_side == BuildSide::Left;
+    name = keep_left && keep_right ? "FullOuter" : keep_left ? "LeftOuter" : keep_right ? "RightOuter" : mode == 0 ? "Inner" : mode == 1 ? "LeftSemi" : "LeftAnti";
+    // LeftSemi / LeftAnti built on the LEFT: the output is a subset of the BUILD rows — the probe pass only marks the build rows
+    // it matched (all of them: MODE 0 walks the whole chain), the tail pass then emits the marked (semi) or unmarked (anti) ones
+    build_only = mode != 0 && build_left;
+    keep_matched = build_only && mode == 1;
+    if (build_only) mode = 0;
+    outer_probe = !build_only && (build_left ? keep_right : keep_left);    // the probe side is the preserved one
+    outer_build = build_only || (build_left ? keep_left : keep_right);
+    // semi / anti joins that keep PROBE rows and have no residual condition only ask whether a key exists on the build side: one build row
+    // per run of equal keys is enough (comet_device.hpp "Runs of equal keys")
+    dedup_build = mode != 0 && !j.join_condition;
   }
+};
 
-  PipelineDesc d;
-  SiteScope site_scope(d);
-  d.sink = SinkKind::Output;
-  d.R = 1;
-  d.op_names.push_back("HashJoin");
-  std::ostringstream src, ex;
-  src << "// generated by datafusion-comet_amd codegen — hash join\n#include \"comet_device.hpp\"\nusing namespace comet;\n";
-  src << "struct P {\n  static constexpr int R = 1;\n  static constexpr int MODE = " << mode << ";\n";
-  src << "  static constexpr bool OUTER_PROBE = " << (outer_probe ? "true" : "false") << ", OUTER_BUILD = " << (outer_build ? "true" : "false")
-      << ", BUILD_KEEP_MATCHED = " << (keep_matched ? "true" : "false") << ", BUILD_ONLY = " << (build_only ? "true" : "false") << ";\n";
-  // semi / anti joins that keep PROBE rows and have no residual condition only ask whether a key exists on the build side: one build row
-  // per run of equal keys is enough (comet_device.hpp "Runs of equal keys")
-  const bool dedup_build = mode != 0 && !j.join_condition;
-  src << "  static constexpr bool DEDUP_BUILD = " << (dedup_build ? "true" : "false") << ";\n";
-  src << "  static constexpr bool HAS_COND = " << (j.join_condition ? "true" : "false") << ";\n";      // a residual condition beside the keys
+// One side of the join as the kernels see it: the materialised child — or, with a fused chain (JoinFusion), the chain's SOURCE table: rows are source rows, the
+// child's columns expressions over the source columns (fu->cols), its Filters conjuncts over them (fu->preds: P::bkeep / P::pkeep; a build row that fails them is in
+// no table, no bitmap and no outer join's tail, a probe row that fails them is not part of the probe side at all).
+struct JoinSide {
+  const JoinFusion* fu;
+  const std::vector<DType>& types;      // PHYSICAL columns
+  const std::vector<bool>& valid_src;   // their validity as the table has it (what the chain's own predicates read)
+  // … and for keys, condition and output: every row that passes a fused chain's isnotnull(<source column>) conjunct holds a value there, no validity bit is read
+  std::vector<bool> valid;
+  const std::vector<ExprP>& logical_keys;   // bound to the child's own schema
+  std::vector<ExprP> keys;              // … and over the physical columns (bind_keys)
+  int base = 0;                         // first kernel argument: build columns, then probe columns
+  const char* row;                      // "i" (build) / "j" (probe)
 
-  // key words of one side
-  auto key_fn = [&](const char* name, const char* rowvar, const std::vector<DType>& types, const std::vector<bool>& valid, int base,
-                    const std::vector<ExprP>& keys, bool want_hash) {
-    Gen g(types, valid);
-    g.locate = [base, rowvar](int idx) { return std::make_pair(base + idx, std::string(rowvar)); };
-    std::string okall;
-    std::vector<std::string> words;
-    for (auto& ke : keys) {
+  JoinSide(const JoinFusion* fu, const std::vector<DType>& child_types, const std::vector<bool>& child_valid, const std::vector<ExprP>& logical_keys, const char* row, const char* what)
+      : fu(fu), types(fu ? fu->src_types : child_types), valid_src(fu ? fu->src_valid : child_valid), valid(valid_src), logical_keys(logical_keys), row(row) {
+    if (fu && types.size() != valid_src.size()) throw CometError(std::string("internal: fused ") + what + " source validity arity mismatch");
+    if (fu)
+      for (auto& p : fu->preds)
+        if (p->kind == ExprKind::IsNotNull && p->children.size() == 1 && p->children[0]->kind == ExprKind::Bound && p->children[0]->bound_index >= 0 &&
+            (size_t)p->children[0]->bound_index < valid.size())
+          valid[(size_t)p->children[0]->bound_index] = false;
+  }
+  void bind_keys() {
+    std::map<const Expr*, ExprP> memo;
+    for (auto& k : logical_keys) keys.push_back(fu ? substitute(k, fu->cols, memo) : k);
+  }
+  int ncols() const { return (int)types.size(); }
+  int nlogical() const { return fu ? (int)fu->cols.size() : ncols(); }
+  bool filters() const { return fu && !fu->preds.empty(); }
+  std::function<std::pair<int, std::string>(int)> locate() const {
+    const int b = base;
+    const std::string r = row;
+    return [b, r](int idx) { return std::make_pair(b + idx, r); };
+  }
+};
+
+// the keys of one side lowered into their validity and their 64-bit words.  (Every functor that needs them lowers them again in a Gen of its own, as the text
+// always had it: a shared Gen would number the keys' raise sites once instead of once per functor.)
+struct LoweredKeys {
+  Gen g;
+  std::string ok;
+  std::vector<std::string> words;
+  explicit LoweredKeys(const JoinSide& s) : g(s.types, s.valid) {
+    g.locate = s.locate();
+    for (auto& ke : s.keys) {
       Val v = g.named(g.gen(ke));
-      okall = Gen::and_ok(okall, v.ok);
+      ok = Gen::and_ok(ok, v.ok);
       switch (v.rep) {
         case Rep::B: words.push_back("(u64)(" + v.v + " ? 1 : 0)"); break;
         case Rep::I32: case Rep::I64: words.push_back("(u64)(i64)" + v.v); break;
@@ -4496,263 +4469,320 @@ PipelineDesc generate_join(const Operator& j, const std::vector<DType>& lt_in, c
         case Rep::STR: words.push_back(v.v + ".a"); words.push_back(v.v + ".b"); break;
       }
     }
-    src << "  static __device__ __forceinline__ " << (want_hash ? "u64 " : "bool ") << name << "(const CometKParams& prm, i64 " << rowvar << ") {\n"
-        << "    bool k[R] = {true};\n" << g.decls << g.body();
-    if (want_hash) {
-      src << "    u64 kw[" << words.size() << "];\n";
-      for (size_t w = 0; w < words.size(); w++) {
-        std::string e = words[w];
-        for (size_t p0 = e.find("[r]"); p0 != std::string::npos; p0 = e.find("[r]")) e.replace(p0, 3, "[0]");
-        src << "    kw[" << w << "] = " << e << ";\n";
-      }
-      src << "    return comet::hash_key<" << words.size() << ">(kw);\n  }\n";
-      if (std::string(name) == "phash") {
-        // a single integer key: its value handed out too — the probe asks the build side's key bitmap before it touches the table
-        const bool one_int = keys.size() == 1 && words.size() == 1 && (words[0].rfind("(u64)(i64)", 0) == 0);
-        src << "  static constexpr bool KEYMAP = " << (one_int ? "true" : "false") << ";\n";
-        src << "  static __device__ __forceinline__ u64 pkey0(const CometKParams& prm, i64 " << rowvar << ") {\n";
-        if (one_int) {
-          std::string e = words[0];
-          for (size_t p0 = e.find("[r]"); p0 != std::string::npos; p0 = e.find("[r]")) e.replace(p0, 3, "[0]");
-          src << "    bool k[R] = {true};\n" << g.decls << g.body() << "    return " << e << ";\n  }\n";
-        } else {
-          src << "    (void)prm; (void)" << rowvar << "; return 0;\n  }\n";
-        }
-      }
-      if (std::string(name) == "bhash") {
-        // the same key words handed out (run detection compares neighbouring build rows word by word: exact, unlike their hashes)
-        src << "  static constexpr int NKW = " << words.size() << ";\n";
-        src << "  static __device__ __forceinline__ void bkeys(const CometKParams& prm, i64 " << rowvar << ", u64* kw) {\n"
-            << "    bool k[R] = {true};\n" << g.decls << g.body();
-        for (size_t w = 0; w < words.size(); w++) {
-          std::string e = words[w];
-          for (size_t p0 = e.find("[r]"); p0 != std::string::npos; p0 = e.find("[r]")) e.replace(p0, 3, "[0]");
-          src << "    kw[" << w << "] = " << e << ";\n";
-        }
-        src << "  }\n";
-      }
-    } else {
-      std::string e = okall.empty() ? "true" : okall;
-      for (size_t p0 = e.find("[r]"); p0 != std::string::npos; p0 = e.find("[r]")) e.replace(p0, 3, "[0]");
-      src << "    return " << e << ";\n  }\n";
-    }
-    return (int)words.size();
-  };
-  if (fub && !fub->preds.empty()) {
-    // P::bvalid = the fused chain's Filters (every predicate column loaded up front, as in P::pkeep) AND the keys' validity
-    Gen g(bt, bv_src);
-    g.eager_loads = true;
-    g.locate = [](int idx) { return std::make_pair(idx, std::string("i")); };
-    for (auto& p : fub->preds) {
-      g.add_predicate(p);
-      ex << "  build filter (fused into the build passes): " << explain_expr(p) << "\n";
-    }
-    src << "  static __device__ __forceinline__ bool bkeep(const CometKParams& prm, i64 i) {\n    bool k[R] = {true};\n" << g.decls << g.body() << "    return k[0];\n  }\n";
-    key_fn("bkeysvalid", "i", bt, bv, 0, bkeys, false);
-    src << "  static __device__ __forceinline__ bool bvalid(const CometKParams& prm, i64 i) { return bkeep(prm, i) && bkeysvalid(prm, i); }\n";
-  } else {
-    src << "  static __device__ __forceinline__ bool bkeep(const CometKParams&, i64) { return true; }\n";
-    key_fn("bvalid", "i", bt, bv, 0, bkeys, false);
   }
-  int nwb = key_fn("bhash", "i", bt, bv, 0, bkeys, true);
-  key_fn("pvalid", "j", pt, pv, nb, pkeys, false);
-  int nwp = key_fn("phash", "j", pt, pv, nb, pkeys, true);
-  if (nwb != nwp) throw CometError("HashJoin key types differ between the two sides");
+  std::string store_words() const {      // kw[w] = …;
+    std::string t;
+    for (size_t w = 0; w < words.size(); w++) t += "    kw[" + std::to_string(w) + "] = " + row0(words[w]) + ";\n";
+    return t;
+  }
+  std::string hash_tail() const { return "    u64 kw[" + std::to_string(words.size()) + "];\n" + store_words() + "    return comet::hash_key<" + std::to_string(words.size()) + ">(kw);\n"; }
+};
 
-  // P::pkeep(j): the Filters of a fused probe chain, conjunct by conjunct (columns load only for rows still alive); a row that fails is
-  // not part of the probe side at all (outer / anti joins do not emit it either)
-  if (fu && !fu->preds.empty()) {
-    Gen g(pt, pv_src);
-    // every load of the chain's predicates up front, no "only for rows still alive" staging: a staged load sits in a lane-dependent branch and is waited for
-    // inside it, so the probe tile's sixteen rows per thread became sixteen CHAINS of dependent latencies; straight-line loads of sixteen rows are in flight together
-    static const bool eager_keep = getenv("COMET_JOIN_EAGER_KEEP") == nullptr || atoi(getenv("COMET_JOIN_EAGER_KEEP")) != 0;
-    g.eager_loads = eager_keep;
-    g.locate = [nb](int idx) { return std::make_pair(nb + idx, std::string("j")); };
-    for (auto& p : fu->preds) {
-      g.add_predicate(p);
-      ex << "  probe filter (fused into the probe kernel): " << explain_expr(p) << "\n";
+// The functor P of the hash-join templates, written piece by piece into `src`; `d` and `ex` gather what the executor and EXPLAIN need
+struct JoinGen {
+  const Operator& j;
+  const JoinShape& shape;
+  JoinSide &build, &probe;
+  PipelineDesc& d;
+  std::ostream &src, &ex;
+  int nl, nr;                     // logical columns of the left / right child
+  std::vector<DType> ct;          // physical combined schema = kernel argument order: build columns (row i), then probe columns (row j)
+  std::vector<bool> cv;
+  std::vector<ExprP> phys;        // logical column c of left ++ right (what keys, condition and output refer to) as an expression over the physical schema
+
+  JoinGen(const Operator& j, const JoinShape& shape, JoinSide& build, JoinSide& probe, PipelineDesc& d, std::ostream& src, std::ostream& ex)
+      : j(j), shape(shape), build(build), probe(probe), d(d), src(src), ex(ex), ct(build.types), cv(build.valid) {
+    const int nb = build.ncols();
+    nl = shape.build_left ? build.nlogical() : probe.nlogical();
+    nr = shape.build_left ? probe.nlogical() : build.nlogical();
+    ct.insert(ct.end(), probe.types.begin(), probe.types.end());
+    cv.insert(cv.end(), probe.valid.begin(), probe.valid.end());
+    for (int c = 0; c < nl + nr; c++) {
+      const bool is_left = c < nl;
+      const int local = is_left ? c : c - nl;
+      if (is_left == shape.build_left) phys.push_back(build.fu ? build.fu->cols[(size_t)local] : bound(local, build.types[(size_t)local]));
+      else if (!probe.fu) phys.push_back(bound(nb + local, probe.types[(size_t)local]));
+      else phys.push_back(shift_bound(probe.fu->cols[(size_t)local], nb));
     }
-    src << "  static __device__ __forceinline__ bool pkeep(const CometKParams& prm, i64 j) {\n    bool k[R] = {true};\n" << g.decls << g.body() << "    return k[0];\n  }\n";
-  } else {
-    src << "  static __device__ __forceinline__ bool pkeep(const CometKParams&, i64) { return true; }\n";
   }
-  {
-    // match(i, j): every key pair equal (NULL never equals) and the residual condition TRUE
+
+  std::function<std::pair<int, std::string>(int)> locate_combined() const {
+    const int nb = build.ncols();
+    return [nb](int c) { return std::make_pair(c, std::string(c < nb ? "i" : "j")); };
+  }
+  std::string fn(const char* ret, const std::string& name, const JoinSide& s, const char* more = "") const {
+    return std::string(ret) + " " + name + "(const CometKParams& prm, i64 " + s.row + more + ")";
+  }
+
+  void write_switches() {
+    const auto tf = [](bool b) { return b ? "true" : "false"; };
+    src << "struct P {\n  static constexpr int R = 1;\n  static constexpr int MODE = " << shape.mode << ";\n";
+    src << "  static constexpr bool OUTER_PROBE = " << tf(shape.outer_probe) << ", OUTER_BUILD = " << tf(shape.outer_build) << ", BUILD_KEEP_MATCHED = " << tf(shape.keep_matched)
+        << ", BUILD_ONLY = " << tf(shape.build_only) << ";\n";
+    src << "  static constexpr bool DEDUP_BUILD = " << tf(shape.dedup_build) << ";\n";
+    src << "  static constexpr bool HAS_COND = " << tf((bool)j.join_condition) << ";\n";      // a residual condition beside the keys
+  }
+
+  // P::bkeep / P::pkeep: the Filters of a fused chain.  Every load of the chain's predicates up front, no "only for rows still alive" staging: a staged load sits in a
+  // lane-dependent branch and is waited for inside it, so the probe tile's sixteen rows per thread became sixteen CHAINS of dependent latencies; straight-line loads
+  // of sixteen rows are in flight together
+  void write_keep(const JoinSide& s, const char* name, const char* explain_label) {
+    if (!s.filters()) {
+      src << "  static __device__ __forceinline__ bool " << name << "(const CometKParams&, i64) { return true; }\n";
+      return;
+    }
+    Gen g(s.types, s.valid_src);
+    g.eager_loads = true;
+    g.locate = s.locate();
+    for (auto& p : s.fu->preds) {
+      g.add_predicate(p);
+      ex << explain_label << explain_expr(p) << "\n";
+    }
+    write_fn(src, fn("bool", name, s), g, "    return k[0];\n");
+  }
+
+  // P::bvalid / P::pvalid (or, beside a fused build chain's Filters, P::bkeysvalid): every key of the row holds a value
+  void write_keys_valid(const JoinSide& s, const char* name) {
+    LoweredKeys k(s);
+    write_fn(src, fn("bool", name, s), k.g, "    return " + row0(k.ok.empty() ? "true" : k.ok) + ";\n");
+  }
+
+  // P::bhash, and the same key words handed out (run detection compares neighbouring build rows word by word: exact, unlike their hashes)
+  int write_build_hash() {
+    LoweredKeys k(build);
+    write_fn(src, fn("u64", "bhash", build), k.g, k.hash_tail());
+    src << "  static constexpr int NKW = " << k.words.size() << ";\n";
+    write_fn(src, fn("void", "bkeys", build, ", u64* kw"), k.g, k.store_words());
+    return (int)k.words.size();
+  }
+
+  // P::phash; a single integer key: its value handed out too — the probe asks the build side's key bitmap before it touches the table
+  int write_probe_hash() {
+    LoweredKeys k(probe);
+    write_fn(src, fn("u64", "phash", probe), k.g, k.hash_tail());
+    const bool one_int = probe.keys.size() == 1 && k.words.size() == 1 && (k.words[0].rfind("(u64)(i64)", 0) == 0);
+    src << "  static constexpr bool KEYMAP = " << (one_int ? "true" : "false") << ";\n";
+    if (one_int) write_fn(src, fn("u64", "pkey0", probe), k.g, "    return " + row0(k.words[0]) + ";\n");
+    else src << "  static __device__ __forceinline__ " << fn("u64", "pkey0", probe) << " {\n    (void)prm; (void)" << probe.row << "; return 0;\n  }\n";
+    return (int)k.words.size();
+  }
+
+  void write_key_functors() {
+    write_keep(build, "bkeep", "  build filter (fused into the build passes): ");
+    if (build.filters()) {
+      // P::bvalid = the fused chain's Filters AND the keys' validity
+      write_keys_valid(build, "bkeysvalid");
+      src << "  static __device__ __forceinline__ bool bvalid(const CometKParams& prm, i64 i) { return bkeep(prm, i) && bkeysvalid(prm, i); }\n";
+    } else {
+      write_keys_valid(build, "bvalid");
+    }
+    const int nwb = write_build_hash();
+    write_keys_valid(probe, "pvalid");
+    const int nwp = write_probe_hash();
+    if (nwb != nwp) throw CometError("HashJoin key types differ between the two sides");
+    write_keep(probe, "pkeep", "  probe filter (fused into the probe kernel): ");
+  }
+
+  // the residual condition over the physical schema, NULL = false
+  std::string lower_condition(Gen& g) const {
+    std::map<const Expr*, ExprP> m2;
+    Val c = g.gen(substitute(j.join_condition, phys, m2));
+    if (c.rep != Rep::B) throw CometError("join condition must be boolean");
+    return Gen::and_ok(c.ok, c.v);
+  }
+  void write_pair_fn(const char* name, Gen& g, const std::string& value) {
+    Val r;
+    r.rep = Rep::B;
+    r.v = value;
+    r = g.named(r);
+    write_fn(src, std::string("bool ") + name + "(const CometKParams& prm, i64 i, i64 j)", g, "    return " + row0(r.v) + ";\n");
+  }
+
+  // match(i, j): every key pair equal (NULL never equals) and the residual condition TRUE
+  void write_match() {
     Gen g(ct, cv);
-    g.locate = locate_combined;
+    g.locate = locate_combined();
     std::string cond;
     for (size_t k = 0; k < j.left_keys.size(); k++) {
-      std::map<const Expr*, ExprP> memo;
-      // right keys are bound to the right child's schema: shift their column indices by nl
-      std::function<ExprP(const ExprP&)> shift = [&](const ExprP& e) -> ExprP {
-        if (e->kind == ExprKind::Bound) {
-          auto n = std::make_shared<Expr>(*e);
-          n->bound_index = e->bound_index + nl;
-          return n;
-        }
-        if (e->children.empty()) return e;
-        auto n = std::make_shared<Expr>(*e);
-        for (auto& c : n->children) c = shift(c);
-        return n;
-      };
       std::map<const Expr*, ExprP> m2;
       Val a = g.gen(substitute(j.left_keys[k], phys, m2));
-      Val b = g.gen(substitute(shift(j.right_keys[k]), phys, m2));
+      Val b = g.gen(substitute(shift_bound(j.right_keys[k], nl), phys, m2));      // right keys are bound to the right child's schema
       Val c = g.compare(ExprKind::Eq, a, b);
       cond = Gen::and_ok(cond, Gen::and_ok(c.ok, c.v));
     }
     if (j.join_condition) {
-      std::map<const Expr*, ExprP> m2;
-      Val c = g.gen(substitute(j.join_condition, phys, m2));
-      if (c.rep != Rep::B) throw CometError("join condition must be boolean");
-      cond = Gen::and_ok(cond, Gen::and_ok(c.ok, c.v));
+      cond = Gen::and_ok(cond, lower_condition(g));
       ex << "  condition: " << explain_expr(j.join_condition) << "\n";
     }
-    Val r;
-    r.rep = Rep::B;
-    r.v = cond;
-    r = g.named(r);
-    std::string e = r.v;
-    for (size_t p0 = e.find("[r]"); p0 != std::string::npos; p0 = e.find("[r]")) e.replace(p0, 3, "[0]");
-    src << "  static __device__ __forceinline__ bool match(const CometKParams& prm, i64 i, i64 j) {\n    bool k[R] = {true};\n"
-        << g.decls << g.body() << "    return " << e << ";\n  }\n";
+    write_pair_fn("match", g, cond);
   }
-  {
-    // cond(i, j): the residual condition ALONE — what the bucket table still has to ask of a build row whose one-word key its entry settled
-    if (j.join_condition) {
-      Gen g(ct, cv);
-      g.locate = locate_combined;
-      std::map<const Expr*, ExprP> m2;
-      Val c = g.gen(substitute(j.join_condition, phys, m2));
-      Val r;
-      r.rep = Rep::B;
-      r.v = Gen::and_ok(c.ok, c.v);
-      r = g.named(r);
-      std::string e = r.v;
-      for (size_t p0 = e.find("[r]"); p0 != std::string::npos; p0 = e.find("[r]")) e.replace(p0, 3, "[0]");
-      src << "  static __device__ __forceinline__ bool cond(const CometKParams& prm, i64 i, i64 j) {\n    bool k[R] = {true};\n"
-          << g.decls << g.body() << "    return " << e << ";\n  }\n";
-    } else {
+
+  // cond(i, j): the residual condition ALONE — what the bucket table still has to ask of a build row whose one-word key its entry settled.
+  // (lowered in a Gen of its own, not taken from match's: the temporaries' names would change)
+  void write_cond() {
+    if (!j.join_condition) {
       src << "  static __device__ __forceinline__ bool cond(const CometKParams&, i64, i64) { return true; }\n";
+      return;
+    }
+    Gen g(ct, cv);
+    g.locate = locate_combined();
+    write_pair_fn("cond", g, lower_condition(g));
+  }
+
+  // output = left columns then right columns (Inner / outer); left columns only (Semi / Anti): types and nullability (a fused column is a computed expression)
+  void describe_outputs() {
+    const int nout = (shape.mode == 0 && !shape.build_only) ? nl + nr : nl;
+    if (nout * 2 + kOutFirstCol > 44) throw CometError("too many output columns for one GPU hash join");
+    Gen g0(ct, cv);
+    g0.locate = locate_combined();
+    for (int c = 0; c < nout; c++) {
+      const bool null_extended = c < nl ? shape.keep_right : shape.keep_left;      // the non-preserved side is NULL-extended
+      const ExprP& e = phys[(size_t)c];
+      OutCol oc;
+      if (e->kind == ExprKind::Bound && e->bound_index >= 0 && (size_t)e->bound_index < ct.size() &&
+          (ct[(size_t)e->bound_index].id == TypeId::String || ct[(size_t)e->bound_index].id == TypeId::Bytes)) {
+        oc.type = ct[(size_t)e->bound_index];
+        oc.nullable = cv[(size_t)e->bound_index] || null_extended;
+        oc.gather_src = e->bound_index;     // Utf8 payload: row index now, gathered after the emit (index into build ++ probe columns)
+      } else {
+        Val v = g0.gen(e);
+        if (v.rep == Rep::STR) throw CometError("a computed Utf8 column below a fused join probe is not supported");
+        oc.type = v.t;
+        oc.nullable = !v.ok.empty() || null_extended;
+      }
+      d.out_cols.push_back(oc);
     }
   }
-  {
-    // emit(i, j, pos): output = left columns then right columns (Inner / outer); left columns only (Semi/Anti).
-    // Outer joins add emit_probe_only(j, pos) / emit_build_only(i, pos): the other side's columns are NULL.
-    const int nout = (mode == 0 && !build_only) ? nl + nr : nl;
-    if (nout * 2 + kOutFirstCol > 44) throw CometError("too many output columns for one GPU hash join");
-    auto is_str_bound = [&](const ExprP& e) {
-      return e->kind == ExprKind::Bound && e->bound_index >= 0 && (size_t)e->bound_index < ct.size() &&
-             (ct[(size_t)e->bound_index].id == TypeId::String || ct[(size_t)e->bound_index].id == TypeId::Bytes);
-    };
-    {
-      Gen g0(ct, cv);             // types and nullability of the output columns (a fused probe column is a computed expression)
-      g0.locate = locate_combined;
-      for (int c = 0; c < nout; c++) {
-        const bool is_left = c < nl;
-        const ExprP& e = phys[(size_t)c];
-        OutCol oc;
-        if (is_str_bound(e)) {
-          oc.type = ct[(size_t)e->bound_index];
-          oc.nullable = cv[(size_t)e->bound_index] || (is_left ? keep_right : keep_left);
-          oc.gather_src = e->bound_index;     // Utf8 payload: row index now, gathered after the emit (index into build ++ probe columns)
-        } else {
-          Val v = g0.gen(e);
-          if (v.rep == Rep::STR) throw CometError("a computed Utf8 column below a fused join probe is not supported");
-          oc.type = v.t;
-          oc.nullable = !v.ok.empty() || (is_left ? keep_right : keep_left);   // the non-preserved side is NULL-extended
-        }
-        d.out_cols.push_back(oc);
-      }
+
+  // the stores of output column c at `pos`; absent: its side has no row (an outer join's other side), the column is NULL
+  void store_column(Gen& g, int c, bool absent) {
+    const ExprP& e = phys[(size_t)c];
+    const OutCol& oc = d.out_cols[(size_t)c];
+    const std::string vb = "prm.out[" + std::to_string(kOutFirstCol + 2 * c) + "]", ob = "prm.out[" + std::to_string(kOutFirstCol + 2 * c + 1) + "]";
+    const std::string st = oc.gather_src >= 0 ? "u32" : store_ctype(oc.type);
+    if (absent) {
+      g.stmt("((" + st + "*)" + vb + ")[pos] = " + (oc.gather_src >= 0 ? std::string("0u") : "(" + st + ")0") + ";");
+      g.stmt("((u8*)" + ob + ")[pos] = 0;");
+      return;
     }
+    if (oc.gather_src >= 0) {
+      // Utf8 payload: the source row (build row i or probe row j); NULL when the value is NULL
+      const int pc = e->bound_index;
+      const std::string row = pc < build.ncols() ? "i" : "j";
+      g.in_used[(size_t)pc] = true;
+      g.stmt("((u32*)" + vb + ")[pos] = (u32)" + row + ";");
+      if (oc.nullable) g.stmt("((u8*)" + ob + ")[pos] = " + (cv[(size_t)pc] ? "comet::ld_valid(prm.in[" + std::to_string(pc) + "], " + row + ") ? 1 : 0" : std::string("1")) + ";");
+      return;
+    }
+    Val v = g.gen(e);
+    std::string val = v.v;
+    if (v.t.id == TypeId::Decimal) val = v.rep == Rep::I128 ? v.v : "(i128)" + v.v;
+    else if (v.t.id == TypeId::Bool) val = "(u8)(" + v.v + " ? 1 : 0)";
+    else val = "(" + st + ")" + v.v;
+    if (!v.ok.empty()) {
+      g.stmt("((" + st + "*)" + vb + ")[pos] = " + v.ok + " ? " + val + " : (" + st + ")0;");
+      g.stmt("((u8*)" + ob + ")[pos] = " + v.ok + " ? 1 : 0;");
+    } else {
+      g.stmt("((" + st + "*)" + vb + ")[pos] = " + val + ";");
+      if (oc.nullable) g.stmt("((u8*)" + ob + ")[pos] = 1;");
+    }
+  }
+
+  // emit(i, j, pos); outer joins add emit_probe_only(j, pos) / emit_build_only(i, pos): the other side's columns are NULL
+  void write_emits() {
+    const char* sig[3] = {"void emit(const CometKParams& prm, i64 i, i64 j, i64 pos)", "void emit_probe_only(const CometKParams& prm, i64 j, i64 pos)",
+                          "void emit_build_only(const CometKParams& prm, i64 i, i64 pos)"};
     // variant 0 = both rows, 1 = probe row only, 2 = build row only
     for (int variant = 0; variant < 3; variant++) {
-      if (variant == 1 && !outer_probe) continue;
-      if (variant == 2 && !outer_build) continue;
+      if ((variant == 1 && !shape.outer_probe) || (variant == 2 && !shape.outer_build)) continue;
       Gen g(ct, cv);
-      g.locate = locate_combined;
-      for (int c = 0; c < nout; c++) {
-        const bool in_build = ((c < nl) == build_left);
-        const bool absent = (variant == 1 && in_build) || (variant == 2 && !in_build);
-        const ExprP& e = phys[(size_t)c];
-        std::string vb = "prm.out[" + std::to_string(kOutFirstCol + 2 * c) + "]", ob = "prm.out[" + std::to_string(kOutFirstCol + 2 * c + 1) + "]";
-        if (d.out_cols[c].gather_src >= 0) {
-          // Utf8 payload: the source row (build row i or probe row j); NULL when the side is absent or the value is NULL
-          const int pc = e->bound_index;
-          auto loc = locate_combined(pc);
-          if (absent) {
-            g.stmt("((u32*)" + vb + ")[pos] = 0u;");
-            g.stmt("((u8*)" + ob + ")[pos] = 0;");
-          } else {
-            g.in_used[(size_t)pc] = true;
-            g.stmt("((u32*)" + vb + ")[pos] = (u32)" + loc.second + ";");
-            if (d.out_cols[c].nullable)
-              g.stmt("((u8*)" + ob + ")[pos] = " + (cv[(size_t)pc] ? "comet::ld_valid(prm.in[" + std::to_string(loc.first) + "], " + loc.second + ") ? 1 : 0" : std::string("1")) + ";");
-          }
-          continue;
-        }
-        const char* st = store_ctype(d.out_cols[c].type);
-        if (absent) {
-          g.stmt("((" + std::string(st) + "*)" + vb + ")[pos] = (" + st + ")0;");
-          g.stmt("((u8*)" + ob + ")[pos] = 0;");
-          continue;
-        }
-        Val v = g.gen(e);
-        std::string val = v.v;
-        if (v.t.id == TypeId::Decimal) val = v.rep == Rep::I128 ? v.v : "(i128)" + v.v;
-        else if (v.t.id == TypeId::Bool) val = "(u8)(" + v.v + " ? 1 : 0)";
-        else val = std::string("(") + st + ")" + v.v;
-        if (!v.ok.empty()) {
-          g.stmt("((" + std::string(st) + "*)" + vb + ")[pos] = " + v.ok + " ? " + val + " : (" + st + ")0;");
-          g.stmt("((u8*)" + ob + ")[pos] = " + v.ok + " ? 1 : 0;");
-        } else {
-          g.stmt("((" + std::string(st) + "*)" + vb + ")[pos] = " + val + ";");
-          if (d.out_cols[c].nullable) g.stmt("((u8*)" + ob + ")[pos] = 1;");
-        }
+      g.locate = locate_combined();
+      for (int c = 0; c < (int)d.out_cols.size(); c++) {
+        const bool in_build = ((c < nl) == shape.build_left);
+        store_column(g, c, (variant == 1 && in_build) || (variant == 2 && !in_build));
       }
-      const char* sig = variant == 0 ? "emit(const CometKParams& prm, i64 i, i64 j, i64 pos)"
-                        : variant == 1 ? "emit_probe_only(const CometKParams& prm, i64 j, i64 pos)"
-                                       : "emit_build_only(const CometKParams& prm, i64 i, i64 pos)";
-      src << "  static __device__ __forceinline__ void " << sig << " {\n    bool k[R] = {true};\n" << g.decls << g.body() << "  }\n";
+      write_fn(src, sig[variant], g, "");
     }
-    if (!outer_probe) src << "  static __device__ __forceinline__ void emit_probe_only(const CometKParams&, i64, i64) {}\n";
-    if (!outer_build) src << "  static __device__ __forceinline__ void emit_build_only(const CometKParams&, i64, i64) {}\n";
+    if (!shape.outer_probe) src << "  static __device__ __forceinline__ void emit_probe_only(const CometKParams&, i64, i64) {}\n";
+    if (!shape.outer_build) src << "  static __device__ __forceinline__ void emit_build_only(const CometKParams&, i64, i64) {}\n";
   }
+
+  // the kernels: the extern "C" lines and PipelineDesc::kernels, both from one table
+  void write_kernels() {
+    struct K { const char* name; const char* bounds; const char* body; };
+    static const K table[] = {
+        {"k_jbuild", "256", "comet::join_build_body<P>(prm);"},
+        {"k_jbcnt", "256", "comet::join_build_count_body<P>(prm);"},
+        {"k_pack", "256", "comet::pack_validity_body((const u8*)prm.out[0], (u8*)prm.out[1], prm.n);"},
+        {"k_jbcount", "256", "comet::join_build_unmatched_count_body<P>(prm);"},
+        {"k_jbscan", "256", "comet::tile_scan_body((u64*)prm.out[comet::kJoinBuildTiles], prm.iarg[3]);"},
+        {"k_jbemit", "256", "comet::join_build_unmatched_emit_body<P>(prm);"},
+        // single-pass probes (comet_device.hpp template D'): the chained global table, or an LDS table for small build sides
+        {"k_jprobe", "256", "comet::join_probe_fused_body<P>(prm);"},
+        {"k_jprobe_km", "256", "comet::join_probe_fused_body<P, true>(prm);"},
+        {"k_jlds", "256, COMET_WAVES_JLDS", "comet::join_probe_lds_body<P>(prm);"},
+        // the key bitmap's two helpers: a sample of the probe side through the finished table (does it pay?), and (below) the bitmap's own build pass
+        {"k_jsample", "256", "comet::join_sample_body<P>(prm);"},
+        // the direct map of a unique integer key (no hash table): build rows in key order, and the probe over it
+        {"k_jdrows", "256", "comet::join_direct_rows_body<P>(prm);"},
+        {"k_jdprobe", "256, COMET_WAVES_JDPROBE", "comet::join_probe_direct_body<P>(prm);"},
+        {"k_jbmap", "256", "comet::join_keymap_build_body<P>(prm);"},
+        // the bucket table (comet_device.hpp template D''): partition passes, the LDS build, the probes; and the bitmap-only semi / anti join
+        {"k_jphist", "1024", "comet::join_part_hist_body<P>(prm);"},
+        {"k_jpscat", "1024", "comet::join_part_scatter_body<P>(prm);"},
+        {"k_jtbuild", "256", "comet::join_table_build_body<P>(prm);"},
+        {"k_jprobe_b", "256, COMET_WAVES_JPROBE_B", "comet::join_probe_bucket_body<P>(prm);"},
+        {"k_jprobe_bkm", "256, COMET_WAVES_JPROBE_BKM", "comet::join_probe_bucket_body<P, true>(prm);"},
+        {"k_jsample_b", "256", "comet::join_sample_bucket_body<P>(prm);"},
+        {"k_jprobe_bm", "256", "comet::join_probe_bitmap_body<P>(prm);"},      // only where the build side is deduplicated
+    };
+    for (const K& k : table) {
+      if (std::string(k.name) == "k_jprobe_bm" && !shape.dedup_build) continue;
+      src << "extern \"C\" __global__ __launch_bounds__(" << k.bounds << ") void " << k.name << "(const CometKParams prm) { " << k.body << " }\n";
+      d.kernels.push_back(k.name);
+    }
+    // (the descriptor has always listed k_jbmap ahead of the direct map's two kernels)
+    auto bmap = std::find(d.kernels.begin(), d.kernels.end(), "k_jbmap");
+    std::rotate(bmap - 2, bmap, bmap + 1);
+  }
+};
+}  // namespace
+
+PipelineDesc generate_join(const Operator& j, const std::vector<DType>& lt_in, const std::vector<DType>& rt_in, const std::vector<bool>& lvalid_in,
+                           const std::vector<bool>& rvalid_in, const JoinFusion* fu, const JoinFusion* fub) {
+  if (j.kind != OpKind::HashJoin) throw CometError("internal: generate_join on a non-join");
+  if (j.left_keys.size() != j.right_keys.size() || j.left_keys.empty()) throw CometError("HashJoin needs matching, non-empty key lists");
+  const JoinShape shape(j);
+  const bool bl = shape.build_left;
+  JoinSide build(fub, bl ? lt_in : rt_in, bl ? lvalid_in : rvalid_in, bl ? j.left_keys : j.right_keys, "i", "build");
+  JoinSide probe(fu, bl ? rt_in : lt_in, bl ? rvalid_in : lvalid_in, bl ? j.right_keys : j.left_keys, "j", "probe");
+  if (build.ncols() + probe.ncols() > COMET_MAX_IN) throw CometError("too many columns for one GPU hash join");
+  probe.base = build.ncols();
+  probe.bind_keys();
+  build.bind_keys();
+
+  PipelineDesc d;
+  SiteScope site_scope(d);
+  d.sink = SinkKind::Output;
+  d.R = 1;
+  d.op_names.push_back("HashJoin");
+  std::ostringstream src, ex;
+  src << "// generated by datafusion-comet_amd codegen — hash join\n#include \"comet_device.hpp\"\nusing namespace comet;\n";
+  JoinGen g(j, shape, build, probe, d, src, ex);
+  g.write_switches();
+  g.write_key_functors();
+  g.write_match();
+  g.write_cond();
+  g.describe_outputs();
+  g.write_emits();
   src << "};\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jbuild(const CometKParams prm) { comet::join_build_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jbcnt(const CometKParams prm) { comet::join_build_count_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_pack(const CometKParams prm) { comet::pack_validity_body((const u8*)prm.out[0], (u8*)prm.out[1], prm.n); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jbcount(const CometKParams prm) { comet::join_build_unmatched_count_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jbscan(const CometKParams prm) { comet::tile_scan_body((u64*)prm.out[comet::kJoinBuildTiles], prm.iarg[3]); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jbemit(const CometKParams prm) { comet::join_build_unmatched_emit_body<P>(prm); }\n";
-  // single-pass probes (comet_device.hpp template D'): the chained global table, or an LDS table for small build sides
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jprobe(const CometKParams prm) { comet::join_probe_fused_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jprobe_km(const CometKParams prm) { comet::join_probe_fused_body<P, true>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256, COMET_WAVES_JLDS) void k_jlds(const CometKParams prm) { comet::join_probe_lds_body<P>(prm); }\n";
-  // the key bitmap's two helpers: a sample of the probe side through the finished table (does it pay?), and the bitmap's own build pass
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jsample(const CometKParams prm) { comet::join_sample_body<P>(prm); }\n";
-  // the direct map of a unique integer key (no hash table): build rows in key order, and the probe over it
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jdrows(const CometKParams prm) { comet::join_direct_rows_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256, COMET_WAVES_JDPROBE) void k_jdprobe(const CometKParams prm) { comet::join_probe_direct_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jbmap(const CometKParams prm) { comet::join_keymap_build_body<P>(prm); }\n";
-  // the bucket table (comet_device.hpp template D''): partition passes, the LDS build, the probes; and the bitmap-only semi / anti join
-  src << "extern \"C\" __global__ __launch_bounds__(1024) void k_jphist(const CometKParams prm) { comet::join_part_hist_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(1024) void k_jpscat(const CometKParams prm) { comet::join_part_scatter_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jtbuild(const CometKParams prm) { comet::join_table_build_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256, COMET_WAVES_JPROBE_B) void k_jprobe_b(const CometKParams prm) { comet::join_probe_bucket_body<P>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256, COMET_WAVES_JPROBE_BKM) void k_jprobe_bkm(const CometKParams prm) { comet::join_probe_bucket_body<P, true>(prm); }\n";
-  src << "extern \"C\" __global__ __launch_bounds__(256) void k_jsample_b(const CometKParams prm) { comet::join_sample_bucket_body<P>(prm); }\n";
-  if (dedup_build) src << "extern \"C\" __global__ __launch_bounds__(256) void k_jprobe_bm(const CometKParams prm) { comet::join_probe_bitmap_body<P>(prm); }\n";
-  d.kernels = {"k_jbuild", "k_jbcnt", "k_pack", "k_jbcount", "k_jbscan", "k_jbemit", "k_jprobe", "k_jprobe_km", "k_jlds", "k_jsample", "k_jbmap", "k_jdrows", "k_jdprobe",
-               "k_jphist", "k_jpscat", "k_jtbuild", "k_jprobe_b", "k_jprobe_bkm", "k_jsample_b"};
-  if (dedup_build) d.kernels.push_back("k_jprobe_bm");
-  d.join_dedup_build = dedup_build;
-  d.join_outer_build = outer_build;
-  d.join_build_only = build_only;
-  const char* jt_name = build_only ? (keep_matched ? "LeftSemi" : "LeftAnti") : keep_left && keep_right ? "FullOuter" : keep_left ? "LeftOuter" : keep_right ? "RightOuter" : mode == 0 ? "Inner" : mode == 1 ? "LeftSemi" : "LeftAnti";
-  ex << "  hash join: " << jt_name << ", build " << (build_left ? "left" : "right") << ", "
-     << j.left_keys.size() << " key(s)" << (fu ? ", probe side fused with its Filter / Projection chain" : "") << (fub ? ", build side fused with its chain" : "") << "\n";
-  d.in_types = ct;
+  g.write_kernels();
+  d.join_dedup_build = shape.dedup_build;
+  d.join_outer_build = shape.outer_build;
+  d.join_build_only = shape.build_only;
+  ex << "  hash join: " << shape.name << ", build " << (bl ? "left" : "right") << ", " << j.left_keys.size() << " key(s)"
+     << (fu ? ", probe side fused with its Filter / Projection chain" : "") << (fub ? ", build side fused with its chain" : "") << "\n";
+  d.in_types = g.ct;
   d.source = with_optional_headers(src.str());
   d.explain = ex.str();
   return d;
@@ -4850,8 +4880,7 @@ PipelineDesc generate_sort_keys(const Operator& sort, const std::vector<DType>& 
   }
   if (W > 255) throw CometError("Sort key wider than 255 bytes");
   for (auto& st : stores) g.stmt(st);
-  std::string body = g.decls + g.body();
-  for (size_t p0 = body.find("[r]"); p0 != std::string::npos; p0 = body.find("[r]")) body.replace(p0, 3, "[0]");
+  const std::string body = row0(g.decls + g.body());
   src << "  static __device__ __forceinline__ void keys(const CometKParams& prm, i64 i) {\n    u8* K = (u8*)prm.out[0];\n    const i64 n = prm.n;\n"
       << "    bool k[R] = {true};\n" << body << "  }\n};\n";
   src << "extern \"C\" __global__ __launch_bounds__(256) void k_sortkey(const CometKParams prm) {\n"

@@ -119,6 +119,9 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
 // Hash join of two materialised tables (left/right = the join's children in plan order).
 // Sort: the kernel that writes every row's order-preserving key bytes (byte planes)
 PipelineDesc generate_sort_keys(const Operator& sort, const std::vector<DType>& types, const std::vector<bool>& has_validity);
+// a Bound expression (column `idx` of type `t`); and `e` with every bound index >= `from` moved up by `by`
+ExprP bound(int idx, const DType& t);
+ExprP shift_bound(const ExprP& e, int by, int from = 0);
 // Probe-side fusion (DataFusion's HashJoinExec STREAMS its probe side, planner.rs:2192-2266; materialising the probe child first costs a
 // write and a read of every surviving row): when the probe child is a chain of Filters / Projections over a source, the join kernel
 // reads the SOURCE table — the child's columns are expressions over the source columns, its Filters run inside the probe kernel.

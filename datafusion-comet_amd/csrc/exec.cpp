@@ -702,15 +702,7 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
     if (sp != shuffle_projs_.end()) {
       Operator& pr = *sp->second;
       pr.project_list.clear();
-      for (size_t i = 0; i < st.size(); i++) {
-        auto b = std::make_shared<Expr>();
-        b->kind = ExprKind::Bound;
-        b->proto_tag = 3;
-        b->bound_index = (int)i;
-        b->dtype = st[i];
-        b->has_dtype = true;
-        pr.project_list.push_back(b);
-      }
+      for (size_t i = 0; i < st.size(); i++) pr.project_list.push_back(bound((int)i, st[i]));
       for (auto& e : op.shuffle_hash_exprs)
         if (e->kind != ExprKind::Bound) pr.project_list.push_back(e);
       for (auto& k : op.shuffle_sort_orders)
@@ -740,18 +732,9 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
         const Operator::SortKey& k = op.shuffle_sort_orders[i];
         const int col = k.child->kind == ExprKind::Bound ? k.child->bound_index : (int)computed_at++;
         if (col < 0 || (size_t)col >= st.size()) throw CometError("ShuffleWriter: range sort order references column " + std::to_string(col));
-        auto mk = [&](int idx, const DType& t) {
-          auto b = std::make_shared<Expr>();
-          b->kind = ExprKind::Bound;
-          b->proto_tag = 3;
-          b->bound_index = idx;
-          b->dtype = t;
-          b->has_dtype = true;
-          return b;
-        };
         Operator::SortKey a = k, b = k;
-        a.child = mk(col, st[(size_t)col]);
-        b.child = mk((int)i, st[(size_t)col]);
+        a.child = bound(col, st[(size_t)col]);
+        b.child = bound((int)i, st[(size_t)col]);
         so.sort_orders.push_back(a);
         sb.sort_orders.push_back(b);
         btypes.push_back(st[(size_t)col]);
@@ -899,6 +882,47 @@ std::string ExecutionContext::check_only(OperatorP plan, uint64_t plan_hash) {
   return ctx.explain_;
 }
 
+PipelineDesc ExecutionContext::join_codegen(OperatorP plan, uint64_t plan_hash, const std::vector<bool>& has_valid) {
+  const Operator& op = *plan;
+  const Operator* leaf[2] = {nullptr, nullptr};
+  for (size_t s = 0; s < 2 && op.kind == OpKind::HashJoin && op.children.size() == 2; s++) {
+    const Operator* c = op.children[s].get();
+    while ((c->kind == OpKind::Filter || c->kind == OpKind::Projection) && c->children.size() == 1) c = c->children[0].get();
+    if (c->kind == OpKind::Scan) leaf[s] = c;
+  }
+  if (!leaf[0] || !leaf[1]) throw CometError("comet_plan_codegen: a HashJoin over two Scan leaves, or Filter / Projection chains over them, is expected");
+  std::vector<InputSource> ins(2);
+  ExecutionContext ctx(plan, plan_hash, {}, ins, 8192, 0);      // createPlan: infer_schema decides probe and build fusion
+  auto fit = ctx.fused_probe_.find(&op);
+  auto fbit = ctx.fused_build_.find(&op);
+  const bool build_left = op.build_side == BuildSide::Left;
+  // the two tables as materialize hands them to hash_join_impl: a fused side's is its chain's source, an unfused chain's is the chain's output
+  std::vector<DType> types[2];
+  std::vector<bool> valid[2];
+  size_t first = 0;
+  for (size_t s = 0; s < 2; s++) {
+    std::vector<bool> hv(leaf[s]->scan_fields.size(), false);
+    for (size_t k = 0; k < hv.size(); k++) hv[k] = first + k < has_valid.size() && has_valid[first + k];
+    first += hv.size();
+    const bool is_build = (s == 0) == build_left;
+    const bool fused = is_build ? fbit != ctx.fused_build_.end() : fit != ctx.fused_probe_.end();
+    if (fused || op.children[s].get() == leaf[s]) {
+      types[s] = leaf[s]->scan_fields;
+      valid[s] = hv;
+    } else {
+      const PipelineDesc cd = generate_pipeline(*op.children[s], hv);
+      for (auto& oc : cd.out_cols) {
+        types[s].push_back(oc.type);
+        valid[s].push_back(oc.nullable);
+      }
+    }
+  }
+  JoinFusion fu, fub;
+  if (fit != ctx.fused_probe_.end()) { fu = fit->second.fu; fu.src_valid = valid[build_left ? 1 : 0]; }
+  if (fbit != ctx.fused_build_.end()) { fub = fbit->second.fu; fub.src_valid = valid[build_left ? 0 : 1]; }
+  return generate_join(op, types[0], types[1], valid[0], valid[1], fit != ctx.fused_probe_.end() ? &fu : nullptr, fbit != ctx.fused_build_.end() ? &fub : nullptr);
+}
+
 std::string ExecutionContext::compile_only(OperatorP plan, uint64_t plan_hash) {
   // count Scan leaves to fabricate the (never used) input list
   size_t nscan = 0;
@@ -922,6 +946,28 @@ std::string ExecutionContext::compile_only(OperatorP plan, uint64_t plan_hash) {
     planned_variant(*ctx.plan_, ctx.plan_hash_, none, true);
   }
   return ctx.explain_;
+}
+
+Variant ExecutionContext::node_variant(const Operator& node, const char* tag, const std::string& validity, const std::function<PipelineDesc()>& generate) {
+  const std::string key = std::to_string(plan_hash_ ^ (0x9E3779B97F4A7C15ull * (uint64_t)(node_id_[&node] + 1))) + tag + validity;
+  std::shared_ptr<PlannedVariant> pv;
+  {
+    std::lock_guard<std::mutex> lk(g_plan_mu);
+    auto it = g_plan_cache.find(key);
+    if (it != g_plan_cache.end()) pv = it->second;
+  }
+  if (!pv) {
+    pv = std::make_shared<PlannedVariant>();
+    pv->desc = generate();
+    pv->code = jit_compile(pv->desc.source);
+    std::lock_guard<std::mutex> lk(g_plan_mu);
+    g_plan_cache[key] = pv;
+  }
+  Variant v;
+  v.desc = pv->desc;
+  note_sites(v.desc);
+  v.mod = jit_load(pv->code);
+  return v;
 }
 
 Variant& ExecutionContext::variant_for(const std::vector<bool>& has_valid, const std::vector<int>& str_fixed_len) {
@@ -1477,12 +1523,7 @@ DevTable ExecutionContext::run_chain_to_device(const Operator& top, const DevTab
   CometKParams prm;
   memset(&prm, 0, sizeof prm);
   prm.n = n;
-  for (size_t i = 0; i < in.cols.size(); i++) {
-    prm.in[i].data = in.cols[i].data;
-    prm.in[i].valid = in.has_valid[i] ? in.cols[i].valid : nullptr;
-    prm.in[i].aux = in.cols[i].aux;
-    prm.in[i].offset = in.cols[i].offset;
-  }
+  bind_inputs(prm, in.cols, in.has_valid);
   prm.out[kOutErr] = err_flags_.p;
   const size_t ncol = d.out_cols.size();
   std::vector<std::shared_ptr<DevBuf>> vals(ncol), vbytes(ncol);

@@ -173,6 +173,9 @@ class ExecutionContext {
   // CPU-only: plan + generate + hiprtc-compile the all-valid variant (used by build()/tests w/o GPU)
   static std::string compile_only(OperatorP plan, uint64_t plan_hash);
   static std::string check_only(OperatorP plan, uint64_t plan_hash);
+  // CPU-only (comet_plan_codegen): what a plan whose root is a HashJoin over two Scan leaves, or Filter / Projection chains over them, generates for the join —
+  // fused as createPlan decides; has_valid covers the left source's columns, then the right source's
+  static PipelineDesc join_codegen(OperatorP plan, uint64_t plan_hash, const std::vector<bool>& has_valid);
 
   std::string last_error;
   int last_error_kind = 0;
@@ -200,6 +203,7 @@ class ExecutionContext {
   DevTable materialize(const Operator& op);
   DevTable scan_parquet(const Operator& native_scan);
   friend struct ParquetScan;         // parquet_scan.cpp: the stages of scan_parquet
+  friend struct HashJoinRun;         // exec_join.cpp: the steps of hash_join_impl
   int64_t launch_fused_filter(Variant& v, CometKParams& prm, int64_t n);
   DevTable run_chain_to_device(const Operator& top, const DevTable& in);
   void extend_derived(DevTable& in, const std::vector<DerivedCol>& derived);
@@ -212,6 +216,8 @@ class ExecutionContext {
   bool plan_fused_probe(const Operator& join, const std::vector<DType>& build_types, PipelineDesc& desc);
   bool plan_fused_build(const Operator& join, FusedProbe& fb);
   DevTable sort_table(const Operator& s, const DevTable& in);
+  // the kernels of a plan node that is no fused chain (a join ":J:", a sort's key kernel ":S:"), generated and compiled once per node and validity pattern, loaded
+  Variant node_variant(const Operator& node, const char* tag, const std::string& validity, const std::function<PipelineDesc()>& generate);
   std::shared_ptr<DevBuf> sort_key_planes(const Operator& s, const DevTable& in, int& W, std::vector<int64_t>* str_len = nullptr, bool measure_only = false);
   DevTable literal_table(const std::vector<std::vector<ExprP>>& rows, const std::vector<DType>& types);
   DevTable take_rows(const DevTable& in, const uint32_t* dev_perm, int64_t first, int64_t rows, std::shared_ptr<DevBuf> perm_owner);
@@ -354,7 +360,6 @@ class ExecutionContext {
   DevPending dev_pending_;
   bool dev_stream_done_ = false;
   int64_t dev_chunks_seen_ = 0;
-  bool join_no_bucket_ = false;      // set while a join whose bucket table overflowed re-runs over the chained table
   int64_t bytes_scanned_ = 0;
   int64_t row_groups_pruned_ = 0;
   int64_t row_groups_pruned_bloom_ = 0;    // … of them, by a column chunk's Bloom filter (the statistics had not ruled them out)

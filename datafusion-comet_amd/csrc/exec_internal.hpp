@@ -145,6 +145,8 @@ bool scan_cast_supported(const SrcFmt& f, const DType& t);
 bool scan_cast_value(const SrcFmt& f, const char* src, int64_t i, const DType& t, char* dst);
 const Operator* find_scan(const Operator* op);
 std::string validity_key(const std::vector<bool>& v);
+// columns → prm.in[first_slot …] (a column without validity passes no bitmap)
+void bind_inputs(CometKParams& prm, const std::vector<DeviceColumnView>& cols, const std::vector<bool>& has_valid, size_t first_slot = 0);
 u128 pow10_u128_host(int p);
 struct Timer {
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

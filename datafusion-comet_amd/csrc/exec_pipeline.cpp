@@ -14,12 +14,7 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
   CometKParams prm;
   memset(&prm, 0, sizeof prm);
   prm.n = n;
-  for (size_t i = 0; i < cols.size(); i++) {
-    prm.in[i].data = cols[i].data;
-    prm.in[i].valid = has_valid[i] ? cols[i].valid : nullptr;
-    prm.in[i].aux = cols[i].aux;
-    prm.in[i].offset = cols[i].offset;
-  }
+  bind_inputs(prm, cols, has_valid);
   err_flags_.ensure(kErrBytes);
   prm.out[kOutErr] = err_flags_.p;
   if (!has_join_) input_rows += n;

@@ -143,24 +143,7 @@ DevTable ExecutionContext::explode(const Operator& ex, const DevTable& in) {
 // order-preserving key bytes of every row of `in` under sop.sort_orders, as W byte planes of n rows (plane p of row i at p·n + i)
 std::shared_ptr<DevBuf> ExecutionContext::sort_key_planes(const Operator& sop, const DevTable& in, int& W, std::vector<int64_t>* str_len, bool measure_only) {
   const int64_t n = in.rows;
-  std::string key = std::to_string(plan_hash_ ^ (0x9E3779B97F4A7C15ull * (uint64_t)(node_id_[&sop] + 1))) + ":S:" + validity_key(in.has_valid);
-  std::shared_ptr<PlannedVariant> pv;
-  {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto it = g_plan_cache.find(key);
-    if (it != g_plan_cache.end()) pv = it->second;
-  }
-  if (!pv) {
-    pv = std::make_shared<PlannedVariant>();
-    pv->desc = generate_sort_keys(sop, in.types, in.has_valid);
-    pv->code = jit_compile(pv->desc.source);
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    g_plan_cache[key] = pv;
-  }
-  Variant v;
-  v.desc = pv->desc;
-  note_sites(v.desc);
-  v.mod = jit_load(pv->code);
+  Variant v = node_variant(sop, ":S:", validity_key(in.has_valid), [&] { return generate_sort_keys(sop, in.types, in.has_valid); });
   W = v.desc.sort_key_bytes;
   CometKParams prm;
   memset(&prm, 0, sizeof prm);
@@ -191,12 +174,7 @@ std::shared_ptr<DevBuf> ExecutionContext::sort_key_planes(const Operator& sop, c
   planes->ensure((size_t)W * (size_t)std::max<int64_t>(n, 1) + 16);
   if (n == 0) return planes;
   prm.n = n;
-  for (size_t i = 0; i < in.cols.size(); i++) {
-    prm.in[i].data = in.cols[i].data;
-    prm.in[i].valid = in.has_valid[i] ? in.cols[i].valid : nullptr;
-    prm.in[i].aux = in.cols[i].aux;
-    prm.in[i].offset = in.cols[i].offset;
-  }
+  bind_inputs(prm, in.cols, in.has_valid);
   prm.out[0] = planes->p;
   prm.out[kOutErr] = err_flags_.p;
   launch(v, "k_sortkey", (int)std::min<int64_t>((n + 255) / 256, 256 * 8), prm);

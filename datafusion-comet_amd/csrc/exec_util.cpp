@@ -283,6 +283,16 @@ std::string validity_key(const std::vector<bool>& v) {
   return k;
 }
 
+void bind_inputs(CometKParams& prm, const std::vector<DeviceColumnView>& cols, const std::vector<bool>& has_valid, size_t first_slot) {
+  for (size_t i = 0; i < cols.size(); i++) {
+    CometCol& c = prm.in[first_slot + i];
+    c.data = cols[i].data;
+    c.valid = has_valid[i] ? cols[i].valid : nullptr;
+    c.aux = cols[i].aux;
+    c.offset = cols[i].offset;
+  }
+}
+
 
 
 }  // namespace detail

@@ -355,12 +355,7 @@ DevTable ExecutionContext::expand(const Operator& ex, const DevTable& in) {
       CometKParams prm;
       memset(&prm, 0, sizeof prm);
       prm.n = n;
-      for (size_t i = 0; i < in.cols.size(); i++) {
-        prm.in[i].data = in.cols[i].data;
-        prm.in[i].valid = in.has_valid[i] ? in.cols[i].valid : nullptr;
-        prm.in[i].aux = in.cols[i].aux;
-        prm.in[i].offset = in.cols[i].offset;
-      }
+      bind_inputs(prm, in.cols, in.has_valid);
       prm.out[kOutErr] = err_flags_.p;
       for (size_t k = 0; k < part.out_col.size(); k++) {
         const size_t c = (size_t)part.out_col[k];

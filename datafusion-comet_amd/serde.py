@@ -564,6 +564,7 @@ class Operator:
     join_type: int = 0
     build_side: int = 0
     condition: Optional[Expr] = None
+    null_aware_anti: bool = False                             # hash_join (HashJoin.null_aware_anti = 6)
 
     # native_scan
     field_names: List[str] = field(default_factory=list)
@@ -770,6 +771,8 @@ class Operator:
                 body += _f_msg(4, self.condition.encode())
             if self.build_side:
                 body += _f_varint(5, self.build_side)
+            if self.null_aware_anti:
+                body += _f_varint(6, 1)
         elif self.kind == "raw":
             return out + _f_msg(self.raw_tag, b"")
         else:

@@ -216,7 +216,8 @@ int32_t comet_regexp_extract_host(const char* pattern, int32_t group, const uint
 /* ==== TEST ABI: exported for the repo's own tests and tools, NOT part of the product boundary — an integrator does not bind these (define COMET_TEST_ABI to see them) ====
  * ---- what the generator writes — diagnostic entries (tests/emu: the generated per-row code compiled and run on the HOST against the oracle) --------------------
  * comet_plan_codegen: the HIP source generated for a Filter / Projection / HashAggregate chain over one Scan leaf (has_valid[k]: column k arrives with a validity
- * bitmap) and what the executor needs to read its outputs, as JSON {"sink", "has_filter", "R", "kernels": [...], "out": [{"type", "precision", "scale", "nullable",
+ * bitmap), or for a HashJoin over two Scan leaves or Filter / Projection chains over them (fused as createPlan decides; has_valid: the left source's columns, then the
+ * right source's), and what the executor needs to read its outputs, as JSON {"sink", "has_filter", "R", "kernels": [...], "out": [{"type", "precision", "scale", "nullable",
  * "gather_src", "view_src", "fmt_kind", "packed_string", "concat", "case_mode", "pad", "pad_left"}], "source"}: the length, the text written when it fits `cap`.
  * comet_embedded_header: the text of a header hiprtc compiles that source against ("comet_device.hpp", "kparams.h", "comet_ryu.hpp", "comet_strtod.hpp",
  * "comet_strts.hpp", "comet_regex_vm.hpp").  -2 and comet_last_error(0) on failure.  Neither needs a GPU. */

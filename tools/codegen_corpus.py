@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A fixed corpus of plans and what the pipeline generator makes of each, without a GPU: per plan, the SHA-256 of the whole comet_plan_codegen JSON (kernel
+"""A fixed corpus of plans and what the pipeline and join generators make of each, without a GPU: per plan, the SHA-256 of the whole comet_plan_codegen JSON (kernel
 source, kernels, output descriptors, fix_sums, R) with every input column's validity off and on, and comet_check_plan's text.  A refused plan is recorded with its
 refusal.  tests/golden/codegen_corpus.json is this tool's output at the commit before the generator was restructured; tests/test_codegen_corpus_cpu.py compares.
 
@@ -208,9 +208,78 @@ def tpch_plans():
     yield "tpch/grouped_min_max", mm
 
 
+JOIN_TYPES = {"inner": S.INNER, "left_outer": S.LEFT_OUTER, "right_outer": S.RIGHT_OUTER, "full_outer": S.FULL_OUTER, "left_semi": S.LEFT_SEMI, "left_anti": S.LEFT_ANTI}
+SIDES = {"build_left": S.BUILD_LEFT, "build_right": S.BUILD_RIGHT}
+# the two tables every join plan reads: key, second key, one column of each key type, a Utf8 column, a payload
+JL = [I64, I32, F64, D38, B, STR, I64]
+JR = [I64, I32, F64, D38, B, STR, I32]
+
+
+def join_plans():
+    """comet_plan_codegen over a HashJoin root: the join's own kernels, probe and build fusion decided as createPlan decides them"""
+    lc = [S.col(i, t) for i, t in enumerate(JL)]
+    rc = [S.col(i, t) for i, t in enumerate(JR)]
+    cond = S.lt(S.col(2, F64), S.col(len(JL) + 2, F64))      # bound to left ++ right
+    for tn, jt in JOIN_TYPES.items():
+        for sn, side in SIDES.items():
+            yield f"join/type/{tn}/{sn}", S.hash_join(S.scan(JL), S.scan(JR), [lc[0]], [rc[0]], jt, side)
+            yield f"join/type/{tn}/{sn}/cond", S.hash_join(S.scan(JL), S.scan(JR), [lc[0]], [rc[0]], jt, side, cond)
+    short = lambda c: S.scalar_func("substring", [c, S.lit(1, I32), S.lit(2, I32)], STR)
+    keys = {"int32_int64": ([lc[1], lc[0]], [rc[1], rc[0]]), "float64": ([lc[2]], [rc[2]]), "decimal_38": ([lc[3]], [rc[3]]), "bool": ([lc[4]], [rc[4]]),
+            "computed_short_string": ([short(lc[5])], [short(rc[5])])}
+    for kn, (lk, rk) in keys.items():
+        for tn in ("inner", "left_semi"):
+            for sn, side in SIDES.items():
+                yield f"join/key/{kn}/{tn}/{sn}", S.hash_join(S.scan(JL), S.scan(JR), lk, rk, JOIN_TYPES[tn], side)
+    # fusion: a chain with a Filter and a computed key fuses into the probe kernel, a chain whose Filters are isnotnull only into the build passes
+    def probe_chain(fields):
+        c = [S.col(i, t) for i, t in enumerate(fields)]
+        src = S.filter_(S.scan(fields), S.and_(S.is_not_null(c[0]), S.gt(c[6], S.lit(3, fields[6]))))
+        return S.project(src, [S.math("add", c[0], S.lit(1, I64), I64), c[2], c[5], c[6]]), [I64, F64, STR, fields[6]]
+
+    def build_chain(fields):
+        c = [S.col(i, t) for i, t in enumerate(fields)]
+        return S.project(S.filter_(S.scan(fields), S.is_not_null(c[0])), [c[0], c[2], c[5], c[6]]), [I64, F64, STR, fields[6]]
+
+    for fn in ("none", "probe", "build", "both"):
+        for tn in ("inner", "left_outer", "full_outer", "left_semi", "left_anti"):
+            for sn, side in SIDES.items():
+                for with_cond in (False, True):
+                    sides = []
+                    for is_left, fields in ((True, JL), (False, JR)):
+                        is_build = is_left == (side == S.BUILD_LEFT)
+                        if fn == "both" or fn == ("build" if is_build else "probe"):
+                            sides.append(build_chain(fields) if is_build else probe_chain(fields))
+                        else:
+                            sides.append((S.scan(fields), fields))
+                    (l, lt_), (r, rt_) = sides
+                    if fn == "none" and not with_cond:
+                        continue      # (join/type/… above)
+                    c = S.lt(S.col(lt_.index(F64), F64), S.col(len(lt_) + rt_.index(F64), F64)) if with_cond else None
+                    yield f"join/fused_{fn}/{tn}/{sn}" + ("/cond" if with_cond else ""), S.hash_join(l, r, [S.col(0, I64)], [S.col(0, I64)], JOIN_TYPES[tn], side, c)
+    # a Utf8 payload column on one side only (gathered after the emit)
+    for sn, side in SIDES.items():
+        yield f"join/utf8_payload/left/{sn}", S.hash_join(S.scan([I64, STR]), S.scan([I64, F64]), [S.col(0, I64)], [S.col(0, I64)], S.LEFT_OUTER, side)
+        yield f"join/utf8_payload/right/{sn}", S.hash_join(S.scan([I64, F64]), S.scan([I64, STR]), [S.col(0, I64)], [S.col(0, I64)], S.LEFT_OUTER, side)
+    # (the root is the Projection: comet_check_plan's text is what this entry pins)
+    yield "join/outer_under_projection", S.project(S.hash_join(S.scan(JL), S.scan(JR), [lc[0]], [rc[0]], S.FULL_OUTER, S.BUILD_RIGHT),
+                                                     [S.col(0, I64), S.math("add", S.col(6, I64), S.cast(S.col(len(JL) + 6, I32), I64), I64)])
+    # refusals
+    na = S.hash_join(S.scan(JL), S.scan(JR), [lc[0]], [rc[0]], S.LEFT_ANTI, S.BUILD_RIGHT)
+    na.null_aware_anti = True
+    yield "join/refuse/null_aware_anti", na
+    yield "join/refuse/key_types_differ", S.hash_join(S.scan(JL), S.scan(JR), [lc[0]], [rc[3]], S.INNER, S.BUILD_RIGHT)
+    yield "join/refuse/key_counts_differ", S.hash_join(S.scan(JL), S.scan(JR), [lc[0], lc[1]], [rc[0]], S.INNER, S.BUILD_RIGHT)
+    yield "join/refuse/too_many_output_columns", S.hash_join(S.scan([I64] * 11), S.scan([I64] * 11), [S.col(0, I64)], [S.col(0, I64)], S.INNER, S.BUILD_RIGHT)
+    yield "join/refuse/too_many_input_columns", S.hash_join(S.scan([I64] * 13), S.scan([I64] * 12), [S.col(0, I64)], [S.col(0, I64)], S.LEFT_SEMI, S.BUILD_RIGHT)
+    # (the fused functor refuses a computed Utf8 column; the join then runs over the materialised chain)
+    pc = S.project(S.filter_(S.scan(JL), S.gt(lc[6], S.lit(3, I64))), [lc[0], short(lc[5])])
+    yield "join/refuse/computed_utf8_under_fused_probe", S.hash_join(pc, S.scan(JR), [S.col(0, I64)], [rc[0]], S.INNER, S.BUILD_RIGHT)
+
+
 def all_plans():
     seen = set()
-    for gen in (aggregate_plans, shared_and_mixed_plans, group_key_plans, refusal_plans, output_plans, tpch_plans):
+    for gen in (aggregate_plans, shared_and_mixed_plans, group_key_plans, refusal_plans, output_plans, tpch_plans, join_plans):
         for name, plan in gen():
             assert name not in seen, name
             seen.add(name)
@@ -218,10 +287,8 @@ def all_plans():
 
 
 def n_inputs(plan):
-    leaf = plan
-    while leaf.children:
-        leaf = leaf.children[0]
-    return len(leaf.fields)
+    """the columns of every Scan leaf (a join's has_valid covers the left source, then the right source)"""
+    return len(plan.fields) if not plan.children else sum(n_inputs(c) for c in plan.children)
 
 
 def record(plan) -> dict:

@@ -234,7 +234,7 @@ print(f'{d[\"sec_per_run\"]*1e3:7.3f} ms  $E  stages {d[\"stage_ms_rank0\"]}  ' 
 q95_bisect() {     # TPC-DS Q95 stage A with the libraries of earlier commits (bisect/<tag>/, built from git worktrees) and with HEAD's join switches, on ONE box
   for v in $(ls bisect 2>/dev/null); do timeout 200 python tools/q95_variant.py --root bisect/$v --tag $v 2> $OUT/q95_$v.err | tee -a $OUT/q95_bisect.jsonl | cut -c1-300; done
   timeout 200 python tools/q95_variant.py --root . --tag head 2> $OUT/q95_head.err | tee -a $OUT/q95_bisect.jsonl | cut -c1-300
-  for E in ${Q95_ENVS:-COMET_JOIN_KEYMAP=0 COMET_JOIN_DIRECT=0 COMET_JOIN_COUNT_RUNS=0}; do
+  for E in ${Q95_ENVS:-COMET_JOIN_KEYMAP=0 COMET_JOIN_DIRECT=0}; do
     env $E timeout 200 python tools/q95_variant.py --root . --tag "head $E" 2> $OUT/q95_env.err | tee -a $OUT/q95_bisect.jsonl | cut -c1-300
   done
   for v in ${Q95_STATS:-r3 head}; do
