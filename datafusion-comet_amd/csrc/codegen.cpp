@@ -2338,6 +2338,40 @@ struct Gen {
       } else throw CometError("seconds_to_timestamp expects Int32, Int64, Float32 or Float64 input, got " + a.t.str());
       return r;
     }
+    if (f == "unscaled_value") {
+      // spark_unscaled_value (math_funcs/internal/unscaled_value.rs): the stored integer of a Decimal128 of at most 18 digits, as Int64.  Spark's DecimalAggregates
+      // rule puts it under sum / avg of short decimals; the bound 10^p − 1 goes with the value (an ANSI sum above it proves from it that it cannot overflow)
+      if (e.children.size() != 1) throw CometError("unscaled_value expects one argument");
+      Val a = arg(0);
+      if (a.t.id != TypeId::Decimal || a.t.precision > 18)
+        throw CometError("unscaled_value over " + a.t.str() + " is not supported by the MI355X native engine (a Decimal128 of at most 18 digits is)");
+      r.t = DType::of(TypeId::Int64);
+      r.rep = Rep::I64;
+      r.ok = a.ok;
+      r.v = a.rep == Rep::I128 ? "(i64)" + a.v : a.v;
+      r.maxabs = std::min(a.maxabs, pow10_u128(a.t.precision) - 1);
+      return r;
+    }
+    if (f == "make_decimal") {
+      // spark_make_decimal (math_funcs/internal/make_decimal.rs:46-78): the Int64 becomes the unscaled value of Decimal128(p, s), no rescale; |v| > 10^p − 1 is NULL,
+      // or under fail_on_error decimal_overflow_error(v, p, s).  NULL slots are skipped (:55-61); a value whose static bound fits gets no check at all
+      if (e.children.size() != 1) throw CometError("make_decimal expects one argument");
+      if (!e.has_dtype || e.dtype.id != TypeId::Decimal) throw CometError("make_decimal: expected a Decimal128 return type");
+      Val a = arg(0);
+      if (a.t.id != TypeId::Int64) throw CometError("make_decimal over " + a.t.str() + " is not supported by the MI355X native engine (Int64 is)");
+      r.t = e.dtype;
+      r.ok = a.ok;
+      r.maxabs = a.maxabs;
+      if (e.dtype.precision <= 18) {
+        r.rep = Rep::I64;
+        r.v = a.v;
+      } else {
+        r.rep = Rep::I128;
+        r.v = "(i128)" + a.v;
+      }
+      const ErrSite site = out_of_range_site(e.dtype);
+      return bound_check(r, e.dtype.precision, e.fail_on_error, 3, &site);
+    }
     throw CometError("Scalar function '" + f + "' is not supported by the MI355X native engine");
   }
 
@@ -3243,7 +3277,7 @@ std::vector<ExprP> bound_columns(const std::vector<DType>& types) {
 int state_arity(const AggExpr& a) {
   switch (a.kind) {
     case AggKind::Avg: return 2;
-    case AggKind::Sum: return a.dtype.id == TypeId::Decimal ? 2 : 1;
+    case AggKind::Sum: return a.dtype.id == TypeId::Decimal || (a.dtype.is_integer() && a.eval_mode == EvalMode::Try) ? 2 : 1;      // try_sum: (sum, has_all_nulls)
     case AggKind::Variance: case AggKind::Stddev: return 3;     // (count, mean, m2)
     case AggKind::Covariance: return 4;                         // (count, mean1, mean2, algo_const)
     case AggKind::Correlation: return 6;                        // … + (m2_1, m2_2)
@@ -3857,8 +3891,8 @@ struct AggSink {
     if (!c.merging) {
       // SumInteger LEGACY (sum_int.rs:117-160, :403-475): wrapping i64, NULL until a non-null value arrives
       if (!v.t.is_integer()) throw CometError("integer sum over " + v.t.str());
-      if (c.a.eval_mode != EvalMode::Legacy) throw CometError("ANSI/TRY integer sum is not supported in the GPU pipeline yet");
     }
+    if (c.a.eval_mode != EvalMode::Legacy) return checked_int_sum(c, v);
     // … and its merge (sum_int.rs:494-530): wrapping sum of the non-null partial sums, NULL if none
     const std::string vkey = c.vkey(g), cond = c.guarded(v.ok);
     PrimSlot cnt = al.get(Prim::Cnt, vkey, c.fkey, cond, "");
@@ -3867,6 +3901,71 @@ struct AggSink {
     put(j, "i64", acc(cnt) + " ? (i64)" + acc(sum) + " : 0");
     put_ok(j, acc(cnt) + " ? 1 : 0");
     explain(c.merge_label(), "sum_int -> Int64");
+  }
+
+  // SumInteger ANSI (sum_int.rs:178-248, :537-686) and TRY (:251-391, :688-890): the reference adds in row order with add_checked; ANSI fails the task at the
+  // first overflowing step, TRY keeps (sum, has_all_nulls) where (NULL, false) means "overflowed" and stays so.  Decided from order-independent facts:
+  // P, the exact sum of the positive addends, and N, of the negative ones.  P ≤ 2^63−1 and N ≥ −2^63: no prefix of any order overflows, the answer is P + N.
+  // P + N outside Int64: every order overflows.  Otherwise the reference's answer depends on the row order: the task fails by name (error flag 16).
+  // Where rows × max|v| cannot reach 2^63 (Int8, Int16, unscaled_value of a short decimal) nothing is tracked: LEGACY's own two words.  A merge sums the
+  // incoming partial sums the same way; TRY's overflowed incoming states are counted, like decimal_merge's that_ovf.
+  void checked_int_sum(const Call& c, const Val& v) {
+    const bool ansi = c.a.eval_mode == EvalMode::Ansi;
+    const char* name = ansi ? "sum_int(ansi)" : "sum_int(try)";
+    if (c.merging && v.t.id != TypeId::Int64) throw CometError(std::string("Final ") + name + " expects an Int64 sum state column");
+    const std::string vkey = c.vkey(g);
+    std::string cond = c.guarded(v.ok), fkey = c.fkey;
+    PrimSlot that_ovf{};
+    const bool try_merge = c.merging && !ansi;
+    if (try_merge) {
+      Val s2 = g.named(g.gen(c.children.at(1)));
+      if (s2.rep != Rep::B) throw CometError("Final sum_int(try) expects (sum, has_all_nulls) state columns");
+      const std::string seen = "!(" + s2.v + ")";      // has_all_nulls is non-null
+      that_ovf = al.get(Prim::Cnt, vkey, "ovf", "(" + seen + " && !" + okx(v) + ")", "");
+      cond = "(" + seen + " && " + okx(v) + ")";
+      fkey = "ne";
+    }
+    const u128 kI64Max = ((u128)1 << 63) - 1;
+    const u128 bound = c.merging || v.maxabs == kUnbounded || v.maxabs > ((u128)1 << 63) ? (u128)1 << 63 : v.maxabs;
+    const u128 safe_rows = kI64Max / (bound == 0 ? 1 : bound);
+    const bool dynamic = safe_rows < ((u128)1 << 33);
+    PrimSlot cnt = al.get(Prim::Cnt, vkey, fkey, cond, "");
+    fin += "    {\n";
+    if (!dynamic) {
+      const long long sr = (long long)safe_rows;
+      if (max_rows_exact == 0 || sr < max_rows_exact) max_rows_exact = sr;
+      PrimSlot sum = al.get(Prim::SumI64, vkey, fkey, cond, v.v, bound);
+      fin += "      i64 total = (i64)" + acc(sum) + ";\n";
+      if (!ansi) fin += "      bool ovf = false;\n";
+    } else {
+      const std::string x = "(i64)(" + v.v + ")";
+      PrimSlot pos = al.get(Prim::Sum128, vkey + "#pos", fkey, cond, "(i128)comet::i64_pos_part(" + x + ")", bound);
+      PrimSlot neg = al.get(Prim::Sum128, vkey + "#neg", fkey, cond, "(i128)comet::i64_neg_part(" + x + ")", bound);
+      fin += "      i64 total = 0;\n      bool ovf = false;\n";
+      fin += "      comet::int_sum_decide(acc + " + std::to_string(pos.word) + ", acc + " + std::to_string(neg.word) + ", total, ovf, " + err_word() + ");\n";
+      g.uses_err = true;
+    }
+    if (try_merge) fin += "      ovf = ovf || " + acc(that_ovf) + " != 0;\n";
+    const std::string C = acc(cnt);
+    const int j = add_out(DType::of(TypeId::Int64), true);
+    if (ansi) {
+      if (dynamic) fin += "      if (ovf) atomicOr(" + err_word() + ", 2u);\n";
+      put(j, "i64", C + " ? total : 0", IN2);
+      put_ok(j, C + " ? 1 : 0", IN2);
+      explain(c.merge_label(), std::string(name) + " -> Int64");
+    } else if (c.as_state) {
+      // an untouched state is (0, true), an overflowed one (NULL, false)
+      const int j1 = add_out(DType::of(TypeId::Bool), false);
+      put(j, "i64", "(ovf || " + C + " == 0) ? 0 : total", IN2);
+      put_ok(j, "ovf ? 0 : 1", IN2);
+      put(j1, "u8", "(" + C + " == 0 && !ovf) ? 1 : 0", IN2);
+      explain(c.label(), std::string(name) + " -> (Int64, has_all_nulls)");
+    } else {
+      put(j, "i64", "(ovf || " + C + " == 0) ? 0 : total", IN2);
+      put_ok(j, "(ovf || " + C + " == 0) ? 0 : 1", IN2);
+      explain(c.label(), std::string(name) + " -> Int64");
+    }
+    fin += "    }\n";
   }
 
   void float_sum_avg(const Call& c) {

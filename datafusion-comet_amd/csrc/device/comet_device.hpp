@@ -1417,6 +1417,25 @@ CDEV void sum_overflow_decide(const u64* sum192, u64 amax_word, u64 signflags, u
 }
 
 // ---------------------------------------------------------------------------------------------
+// SumInteger under ANSI / TRY adds in row order with add_checked (sum_int.rs:178-391, :537-890): whether a prefix overflows depends on that order.  The
+// positive and the negative addends are summed apart, exactly (128 bits each): pos = P ≥ 0, neg = N ≤ 0, T = P + N.
+//   1. P ≤ 2^63−1 and N ≥ −2^63  → every prefix of every order lies in [N, P]: no overflow, the answer is T
+//   2. T outside Int64           → the last prefix of every order overflows: ovf
+//   3. otherwise                 → some orders overflow and some do not: err bit 4, the task fails by name
+CDEV i64 i64_pos_part(i64 v) { return v > 0 ? v : 0; }
+CDEV i64 i64_neg_part(i64 v) { return v < 0 ? v : 0; }
+CDEV void int_sum_decide(const u64* pos, const u64* neg, i64& total, bool& ovf, unsigned int* err) {
+  const i128 P = mk128(pos[1], pos[0]), N = mk128(neg[1], neg[0]), T = P + N;
+  const i128 hi = (i128)0x7fffffffffffffffll, lo = -hi - 1;
+  total = (i64)(u64)(u128)T;
+  ovf = false;
+  if (P <= hi && N >= lo) return;
+  total = 0;
+  if (T > hi || T < lo) { ovf = true; return; }
+  atomicOr(err, 16u);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Kernel template A — ungrouped aggregate over a fused scan→filter→project pipeline.
 //   P::R            rows per thread per tile (tile = 256·R rows)
 //   P::NW           accumulator words

@@ -518,7 +518,11 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
         else if (lit) throw CometError("Window: SUM / AVG / MIN / MAX of a literal is not supported");
         else if (minmax && (at.is_integer() || at.id == TypeId::Decimal || at.id == TypeId::Date || at.id == TypeId::Timestamp || at.id == TypeId::TimestampNtz)) out.push_back(at);
         else if (a.kind == AggKind::Sum && at.id == TypeId::Decimal && a.dtype.id == TypeId::Decimal) out.push_back(a.dtype);
-        else if (a.kind == AggKind::Sum && at.is_integer()) out.push_back(DType::of(TypeId::Int64));
+        else if (a.kind == AggKind::Sum && at.is_integer()) {
+          // the frame sums wrap like SumInteger's LEGACY accumulator: an ANSI / TRY sum would wrap silently where the reference raises / yields NULL
+          if (a.eval_mode != EvalMode::Legacy) throw CometError("Window: ANSI/TRY integer SUM over a window frame is not supported by the MI355X native engine yet (LEGACY is)");
+          out.push_back(DType::of(TypeId::Int64));
+        }
         else if (a.kind == AggKind::Avg && at.id == TypeId::Decimal && a.dtype.id == TypeId::Decimal) out.push_back(a.dtype);
         else throw CometError("Window: aggregate (tag " + std::to_string(a.proto_tag) + ") over " + at.str() + " is not supported yet (SUM / AVG of decimals, SUM of integers, COUNT, MIN / MAX of integers, decimals, dates and timestamps are)");
         continue;

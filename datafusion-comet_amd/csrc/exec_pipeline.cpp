@@ -10,7 +10,7 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
   Variant& v = variant_for(has_valid, fixed_lens);
   const PipelineDesc& d = v.desc;
   if (d.max_rows_exact && input_rows + n > d.max_rows_exact)
-    throw CometError("decimal sum over more rows than the exactness bound allows (" + std::to_string(d.max_rows_exact) + ")");
+    throw CometError("decimal or integer sum over more rows than its static no-overflow proof allows (" + std::to_string(d.max_rows_exact) + ")");
   CometKParams prm;
   memset(&prm, 0, sizeof prm);
   prm.n = n;
@@ -354,7 +354,7 @@ void ExecutionContext::raise_device_errors(uint32_t f) {
   if (f & 32768u) throw CometError("{\"errorType\":\"RemainderByZero\",\"errorClass\":\"REMAINDER_BY_ZERO\",\"params\":{}}", 1);      // (common/src/error.rs:81-82, 684)
   if (f & 64u) throw CometError("Utf8 group keys longer than 15 bytes are not supported by the GPU hash aggregate yet");
   if (f & 16u)
-    throw CometError("decimal sum overflow cannot be decided order-independently for this input (mixed signs beyond the precision bound); "
+    throw CometError("decimal or ANSI/TRY integer sum overflow cannot be decided order-independently for this input (mixed signs beyond the type's bound); "
                      "exact sequential evaluation is not implemented");
   throw CometError("device error flags " + std::to_string(f));
 }

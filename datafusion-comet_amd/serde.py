@@ -414,6 +414,26 @@ def scalar_func(name: str, args: Sequence[Expr], return_type: Optional[DataType]
     return Expr("scalar_func", list(args), dtype=return_type, value=name, fail_on_error=fail_on_error)
 
 
+def unscaled_value(child: Expr) -> Expr:
+    """UnscaledValue(decimal(p <= 18, s)) -> Long, what Spark's DecimalAggregates rule puts under sum / avg of short decimals (decimalExpressions.scala:27-45)."""
+    return scalar_func("unscaled_value", [child], T_INT64)
+
+
+def make_decimal(child: Expr, precision: int, scale: int, null_on_overflow: bool = True) -> Expr:
+    """MakeDecimal(long, p, s): the Long as the unscaled value of decimal(p, s); out of range is NULL, or an error when null_on_overflow is off
+    (decimalExpressions.scala:47-75: fail_on_error = !nullOnOverflow)."""
+    return scalar_func("make_decimal", [child], decimal(precision, scale), fail_on_error=not null_on_overflow)
+
+
+def sum_state_types(agg: "AggExpr") -> List[DataType]:
+    """The Partial state columns of a sum: decimals keep (sum, is_empty), try_sum of integers (sum, has_all_nulls), every other sum one column."""
+    if agg.dtype.type_id == DECIMAL:
+        return [agg.dtype, T_BOOL]
+    if agg.eval_mode == TRY and agg.dtype.type_id in (INT8, INT16, INT32, INT64):
+        return [T_INT64, T_BOOL]
+    return [agg.dtype]
+
+
 def date_part(field_name: str, date_expr: Expr) -> Expr:
     """What CometGetDateField emits for year()/month()/…: Cast(datepart(<field>, date) AS int) (serde/datetime.scala:36-80)."""
     return cast(scalar_func("datepart", [lit(field_name, T_STRING), date_expr]), T_INT32)

@@ -2,8 +2,11 @@
 """A fixed corpus of plans and what the pipeline and join generators make of each, without a GPU: per plan, the SHA-256 of the whole comet_plan_codegen JSON (kernel
 source, kernels, output descriptors, fix_sums, R) with every input column's validity off and on, and comet_check_plan's text.  A refused plan is recorded with its
 refusal.  tests/golden/codegen_corpus.json is this tool's output at the commit before the generator was restructured; tests/test_codegen_corpus_cpu.py compares.
+That file is a record of the past and is not rewritten: plans for what the generator has learnt since go into a corpus of their own (--ansi-try-sum →
+tests/golden/ansi_try_sum_codegen.json, compared by tests/test_ansi_try_sum_cpu.py), and an entry whose recorded refusal has been lifted since is RETIRED below:
+it is no longer generated, its record is carried over as it stands, and the plan moves into the newer corpus under its new behaviour.
 
-  python tools/codegen_corpus.py [--out f.json]      (no COMET_* generator variable set)"""
+  python tools/codegen_corpus.py [--ansi-try-sum] [--out f.json]      (no COMET_* generator variable set)"""
 import argparse
 import hashlib
 import json
@@ -90,8 +93,8 @@ def state_plan(agg, state, grouped, mode):
     return S.hash_agg(S.scan(sf), [S.col(0, I32)] if grouped else [], [agg], mode)
 
 
-def aggregate_plans():
-    for name, (mk, state, with_filter) in aggregate_kinds().items():
+def aggregate_plans(kinds=None):
+    for name, (mk, state, with_filter) in (kinds if kinds is not None else aggregate_kinds()).items():
         for grouped in (False, True):
             g = "grouped" if grouped else "ungrouped"
             keys = [K] if grouped else []
@@ -158,7 +161,6 @@ def refusal_plans():
     yield "refuse/unknown_statistics_type", S.hash_agg(S.scan([F64]), [], [S.variance(S.col(0, F64), 7)])
     yield "refuse/state_column_out_of_bound", S.hash_agg(S.scan([F64, F64]), [], [S.variance(S.col(0, F64))], S.FINAL)
     yield "refuse/project_above_aggregate", S.project(S.hash_agg(S.scan([I32, I64]), [S.col(0, I32)], [S.count(S.col(1, I64))]), [S.col(0, I32)])
-    yield "refuse/ansi_integer_sum", S.hash_agg(S.scan([I64]), [], [S.sum_(S.col(0, I64), I64, S.ANSI)])
 
 
 def output_plans():
@@ -277,6 +279,41 @@ def join_plans():
     yield "join/refuse/computed_utf8_under_fused_probe", S.hash_join(pc, S.scan(JR), [S.col(0, I64)], [rc[0]], S.INNER, S.BUILD_RIGHT)
 
 
+# entries of tests/golden/codegen_corpus.json whose refusal has been lifted: name → (what was recorded, where the plan is held now)
+RETIRED = {
+    "refuse/ansi_integer_sum": ("refused: ANSI/TRY integer sum is not supported in the GPU pipeline yet", "ansi_try_sum_plans: lifted/ansi_integer_sum"),
+}
+
+
+def ansi_try_sum_plans():
+    """ANSI / TRY integer sums in every mode, grouped and not, and unscaled_value / make_decimal: the corpus of tests/golden/ansi_try_sum_codegen.json"""
+    kinds = {
+        "sum_i8_ansi": (lambda: S.sum_(BY, I64, S.ANSI), [I64], False),              # proven by the input's bound: LEGACY's words
+        "sum_i32_ansi": (lambda: S.sum_(XI, I64, S.ANSI), [I64], False),             # dynamic: the positive and the negative sum
+        "sum_i64_ansi": (lambda: S.sum_(X, I64, S.ANSI), [I64], True),
+        "sum_i16_try": (lambda: S.sum_(SH, I64, S.TRY), [I64, B], False),
+        "sum_i64_try": (lambda: S.sum_(X, I64, S.TRY), [I64, B], True),
+        "sum_unscaled_d12_ansi": (lambda: S.sum_(S.unscaled_value(DD12), I64, S.ANSI), [I64], False),
+    }
+    yield from aggregate_plans(kinds)
+    yield "lifted/ansi_integer_sum", S.hash_agg(S.scan([I64]), [], [S.sum_(S.col(0, I64), I64, S.ANSI)])      # (RETIRED["refuse/ansi_integer_sum"])
+    for grouped in (False, True):
+        g = "grouped" if grouped else "ungrouped"
+        keys = [K] if grouped else []
+        yield f"shared/legacy_ansi_try_same_value/{g}", S.hash_agg(S.scan(FIELDS), keys, [S.sum_(X, I64), S.sum_(X, I64, S.ANSI), S.sum_(X, I64, S.TRY), S.count(X)])
+        nk = 1 if grouped else 0
+        child = S.scan([I32] * nk + [I64, I64, B, I64])
+        c = lambda i, t: S.col(nk + i, t)
+        aggs = [S.sum_(c(0, I64), I64, S.TRY), S.sum_(c(0, I64), I64, S.ANSI), S.count(c(0, I64))]
+        yield f"mixed/try_ansi_count/{g}", S.hash_agg(child, [S.col(0, I32)] * nk, aggs, S.PARTIAL, expr_modes=[S.PARTIAL_MERGE, S.PARTIAL_MERGE, S.PARTIAL], initial_input_buffer_offset=nk + 1)
+    scan = S.scan([D12, I64])
+    yield "out/unscaled_value_make_decimal", S.project(scan, [S.unscaled_value(S.col(0, D12)), S.make_decimal(S.col(1, I64), 17, 2), S.make_decimal(S.col(1, I64), 17, 2, null_on_overflow=False),
+                                                             S.make_decimal(S.unscaled_value(S.col(0, D12)), 22, 2, null_on_overflow=False)])
+    yield "refuse/unscaled_value_of_a_wide_decimal", S.hash_agg(S.scan([D38]), [], [S.sum_(S.unscaled_value(S.col(0, D38)), I64, S.ANSI)])
+    yield "refuse/make_decimal_of_an_int", S.project(S.scan([I32]), [S.make_decimal(S.col(0, I32), 17, 2)])
+    yield "refuse/final_try_sum_without_its_flag", S.hash_agg(S.scan([I64, I64]), [], [S.sum_(S.col(0, I64), I64, S.TRY)], S.FINAL)
+
+
 def all_plans():
     seen = set()
     for gen in (aggregate_plans, shared_and_mixed_plans, group_key_plans, refusal_plans, output_plans, tpch_plans, join_plans):
@@ -307,14 +344,23 @@ def record(plan) -> dict:
 def corpus() -> dict:
     switches = sorted(v for v in os.environ if v.startswith("COMET_") and v != "COMET_JIT_CACHE_DIR")
     assert not switches, f"{switches} set: the corpus records what the generator makes by default"
-    return {name: record(plan) for name, plan in all_plans()}
+    out = {name: record(plan) for name, plan in all_plans()}
+    for name, (recorded, _) in RETIRED.items():
+        assert name not in out, name
+        out[name] = {"check": recorded, "valid_off": recorded, "valid_on": recorded}
+    return out
+
+
+def ansi_try_sum_corpus() -> dict:
+    return {name: record(plan) for name, plan in ansi_try_sum_plans()}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--ansi-try-sum", action="store_true", help="the corpus of tests/golden/ansi_try_sum_codegen.json instead")
     a = ap.parse_args()
-    text = json.dumps(corpus(), indent=0, sort_keys=True) + "\n"
+    text = json.dumps(ansi_try_sum_corpus() if a.ansi_try_sum else corpus(), indent=0, sort_keys=True) + "\n"
     if a.out:
         with open(a.out, "w") as f:
             f.write(text)

@@ -80,6 +80,9 @@ def probes():
     f = S.scalar_func
     P = {
         "Literal": (L(1, S.T_INT32), ""), "AttributeReference": (i32, "BoundReference"), "Alias": (i32, "serialized as its child"),
+        "KnownNotNull": (i32, "serialized as its child"), "KnownNullable": (i32, "serialized as its child"),
+        "UnscaledValue": (S.unscaled_value(dec), "of a decimal of at most 18 digits (what DecimalAggregates puts under sum / avg of short decimals); its bound 10^p − 1 lets an ANSI sum above it run without overflow tracking"),
+        "MakeDecimal": (S.make_decimal(i64, 17, 2), "of a Long; beyond 10^p − 1 NULL, or NUMERIC_VALUE_OUT_OF_RANGE when nullOnOverflow is off"),
         "Add": (S.math("add", i64, L(1, S.T_INT64), S.T_INT64), "integers, floats, decimals (narrow and 256-bit wide path)"),
         "Subtract": (S.math("subtract", dec, dec, S.decimal(13, 2)), ""), "Multiply": (S.math("multiply", dec, dec, S.decimal(25, 4)), ""),
         "Divide": (S.math("divide", f64, L(2.0, S.T_DOUBLE), S.T_DOUBLE), "floats and decimals"),
@@ -177,7 +180,7 @@ def probes():
     return P
 
 
-ACCEPTED_AGGREGATES = {"Sum": "integers, decimals, Float64 (exact, order independent)", "Average": "decimals and Float64", "Count": "", "Min": "not decimal(>18) in grouped aggregates",
+ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64 (exact, order independent)", "Average": "decimals and Float64", "Count": "", "Min": "not decimal(>18) in grouped aggregates",
                        "Max": "not decimal(>18) in grouped aggregates", "First": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
                        "Last": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
                        "BitAndAgg": "Byte / Short / Int / Long, not over window frames", "BitOrAgg": "Byte / Short / Int / Long, not over window frames",
@@ -259,6 +262,9 @@ def render() -> str:
     w("  device-resident input ANY type mismatch with the declared Scan fields.  Time zones come from the system's database ($TZDIR, /usr/share/zoneinfo).")
     w("* `Min` / `Max` of decimal(> 18) in grouped aggregates; more than eight Float64 sums / averages in one aggregate (a variance or stddev takes two,")
     w("  a covariance three, a corr five; in a Partial aggregate functions over the same columns share theirs); statistical aggregates over window frames.")
+    w("* `Sum` of integers under ANSI / TRY (`try_sum`): where the positive addends of a group sum beyond 2^63 − 1 or the negative ones below −2^63 while the total fits,")
+    w("  the reference's answer depends on the row order; the task fails with \"… sum overflow cannot be decided order-independently …\" (as a decimal sum with mixed")
+    w("  signs beyond its precision does).  Over window frames an ANSI / TRY integer sum is refused at `createPlan` (the frame sums wrap like LEGACY's).")
     w("* `First` / `Last` of Utf8, Binary and nested values in a HashAggregate (their state is fixed-width; over window frames any flat type runs); `BitAndAgg` /")
     w("  `BitOrAgg` / `BitXorAgg` over anything but Byte / Short / Int / Long, and over window frames.")
     w("* `RLike`: patterns outside the byte-exact subset (`\\\\p{..}`, scoped flags, look-around, `\\\\b` under `(?m)`) are refused by name.")
@@ -289,6 +295,11 @@ def render() -> str:
     w("  they were rounded; variance, stddev and covariance results are within 2 ulp of exact, corr within 4 (`tests/test_stat_agg_gpu.py`).  A group with a")
     w("  NaN or ±inf input has NaN results on both sides, but its state's `mean` differs: here it is the IEEE outcome of the exact sum divided by the count,")
     w("  in the reference it depends on the row order (inf or NaN).")
+    w("* ANSI / TRY integer `sum`: the reference adds in row order with a checked add, so whether it overflows moves with row order, batch boundaries and")
+    w("  partitioning.  Here the positive and the negative addends are summed apart, exactly: if neither sum leaves Int64 no order overflows and the total is the")
+    w("  answer; if the total leaves Int64 every order overflows (ANSI: ARITHMETIC_OVERFLOW, TRY: NULL); in between the task fails by name rather than guess")
+    w("  (`tests/test_ansi_try_sum_gpu.py`).  Where the input's bound proves that 2^33 rows cannot reach 2^63 — Byte, Short, `UnscaledValue` of a short decimal —")
+    w("  the sum is LEGACY's, word for word.")
     w("* `first` / `last` in a HashAggregate: the reference marks both not deterministic (`aggregates.scala:240,275`) because its answer moves with partitioning.")
     w("  Within one native plan the input order is defined — batches in the order `executePlan` pulls them, rows in batch order, behind the chain's Filters and the")
     w("  aggregate's own FILTER — and this implementation is a pure function of that order: the same bits for every batch size, chunking, grid size and table path")
