@@ -524,7 +524,10 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
           out.push_back(DType::of(TypeId::Int64));
         }
         else if (a.kind == AggKind::Avg && at.id == TypeId::Decimal && a.dtype.id == TypeId::Decimal) out.push_back(a.dtype);
-        else throw CometError("Window: aggregate (tag " + std::to_string(a.proto_tag) + ") over " + at.str() + " is not supported yet (SUM / AVG of decimals, SUM of integers, COUNT, MIN / MAX of integers, decimals, dates and timestamps are)");
+        // float SUM / AVG: the frame's exact sum in 192-bit fixed point, rounded once (window_kernels.hip "Float sums over frames"); Float32
+        // is widened exactly and the result is Float64, as the grouped aggregate reports it
+        else if ((a.kind == AggKind::Sum || a.kind == AggKind::Avg) && at.is_float()) out.push_back(DType::of(TypeId::Double));
+        else throw CometError("Window: aggregate (tag " + std::to_string(a.proto_tag) + ") over " + at.str() + " is not supported yet (SUM / AVG of decimals and floats, SUM of integers, COUNT, MIN / MAX of integers, decimals, dates and timestamps are)");
         continue;
       }
       const std::string& f = fn.func;

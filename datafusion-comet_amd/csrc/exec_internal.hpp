@@ -3,6 +3,7 @@
 #pragma once
 #include "exec.hpp"
 #include "shuffle_format.hpp"
+#include "fix_scale.hpp"
 
 #include <cerrno>
 #include <fcntl.h>
@@ -41,6 +42,12 @@ extern "C" int comet_launch_window_pick(int mode, int64_t nth, int lo_kind, int6
 extern "C" int comet_launch_window_agg(int fn, int lo_kind, int64_t lo_off, int hi_kind, int64_t hi_off, const void* S128, const void* SH128, const int32_t* C, const int32_t* sp, const int32_t* sg, const uint32_t* first_part,
                                        const uint32_t* first_peer, int64_t n, const void* bound16, const void* scaler16, const void* avg_bound16, void* out, uint8_t* out_ok,
                                        void* stream);
+// float SUM / AVG over frames (window_kernels.hip "Float sums over frames"): width 4 / 8 = Float32 / Float64 argument
+extern "C" int comet_launch_window_fexp(int width, const void* src, const uint8_t* valid_bits, int64_t n, uint64_t* hi_lo, void* stream);
+extern "C" int comet_launch_scan192_f64(int width, const void* src, const uint8_t* valid_bits, int64_t n, int scale, int slice, void* tiles, void* out192, void* stream);
+extern "C" int comet_launch_scan128_fclass(int width, const void* src, const uint8_t* valid_bits, int64_t n, void* tiles, void* out128, void* stream);
+extern "C" int comet_launch_window_fagg(int fn, int lo_kind, int64_t lo_off, int hi_kind, int64_t hi_off, const void* S192, int windows, const void* K128, int scale, const int32_t* sp, const int32_t* sg,
+                                        const uint32_t* first_part, const uint32_t* first_peer, int64_t n, double* out, uint8_t* out_ok, void* stream);
 extern "C" int comet_launch_window_flags(const uint8_t* part_planes, int Wp, const uint8_t* order_planes, int Wo, int64_t n, uint32_t* fpart, uint32_t* fpeer, void* stream);
 extern "C" int comet_launch_window_first(const uint32_t* fpart, const int32_t* sp, const uint32_t* fpeer, const int32_t* sg, int64_t n, uint32_t* first_part,
                                          uint32_t* first_peer, void* stream);

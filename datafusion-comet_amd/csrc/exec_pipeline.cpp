@@ -706,8 +706,8 @@ bool ExecutionContext::adjust_fix_scales(const PipelineDesc& d, const uint64_t* 
     const int top = (int)hi - 1200, low = 1200 - (int)lo, s = fix_scales_[f];
     int target = s;
     if (top > s + kFixW) target = top + 10 - kFixW;
-    else if (low < s && !fix_has_state_) target = (top - low <= kFixW - 10) ? low : top + 2 - kFixW;
-    if (target < -1300) target = -1300;
+    else if (low < s && !fix_has_state_) target = fix_scale_for_range(top, low, kFixW);
+    if (target < kFixScaleFloor) target = kFixScaleFloor;
     if (target == s) continue;
     if (target > s && fix_has_state_) shift_right[f] = target - s;
     fix_scales_[f] = target;

@@ -31,7 +31,9 @@ DevTable ExecutionContext::window(const Operator& w, const DevTable& in) {
       if (w.window_fns[k].is_agg) {
         const AggExpr& a = w.window_fns[k].agg;
         const bool dec = a.dtype.id == TypeId::Decimal && a.kind != AggKind::Count;
-        if (a.kind == AggKind::Min || a.kind == AggKind::Max || a.kind == AggKind::First || a.kind == AggKind::Last) add_col(in.types[(size_t)a.children[0]->bound_index], nullptr, nullptr);
+        const bool flt = (a.kind == AggKind::Sum || a.kind == AggKind::Avg) && a.children[0]->kind == ExprKind::Bound && in.types[(size_t)a.children[0]->bound_index].is_float();
+        if (flt) add_col(DType::of(TypeId::Double), nullptr, nullptr);
+        else if (a.kind == AggKind::Min || a.kind == AggKind::Max || a.kind == AggKind::First || a.kind == AggKind::Last) add_col(in.types[(size_t)a.children[0]->bound_index], nullptr, nullptr);
         else add_col(dec ? a.dtype : DType::of(TypeId::Int64), nullptr, nullptr);
         continue;
       }
@@ -159,6 +161,10 @@ DevTable ExecutionContext::window(const Operator& w, const DevTable& in) {
   };
   struct Prefix { std::shared_ptr<DevBuf> S, SH, C; };   // 128-bit inclusive sums (low part), sums of the high 64 bits (wide decimals only), non-NULL prefix counts
   std::map<int, Prefix> prefix;                           // by argument column
+  // float SUM / AVG: 192-bit fixed-point inclusive sums at the column's scale, and the prefix sums of its packed class words (non-NULL / +inf /
+  // −inf / NaN counters) — window_kernels.hip "Float sums over frames"
+  struct FloatPrefix { std::shared_ptr<DevBuf> S, K; int scale, windows; };   // S: `windows` arrays of n × 24 bytes, window j at scale + kFixW · j
+  std::map<int, FloatPrefix> fprefix;                     // by argument column
   for (auto& fn : w.window_fns) {
     if (fn.is_agg) {
       const AggExpr& a = fn.agg;
@@ -205,6 +211,53 @@ DevTable ExecutionContext::window(const Operator& w, const DevTable& in) {
         pq_launch_pack((const uint8_t*)okb->p, (uint8_t*)bits->p, n, stream_);
         HIP_CHECK(hipStreamSynchronize(stream_));   // scratch goes back to the pool
         add_col(at, data, bits);
+        out.owners.push_back(okb);
+        continue;
+      }
+      if ((a.kind == AggKind::Sum || a.kind == AggKind::Avg) && arg->kind == ExprKind::Bound && in.types[(size_t)arg->bound_index].is_float()) {
+        const int fc = arg->bound_index;
+        auto it = fprefix.find(fc);
+        if (it == fprefix.end()) {
+          const DeviceColumnView& sc = in.cols[(size_t)fc];
+          if (sc.offset != 0) throw CometError("Window: aggregate over a column with a non-zero Arrow offset is not supported yet");
+          const uint8_t* vb = in.has_valid[(size_t)fc] ? sc.valid : nullptr;
+          const int width = fixed_width(in.types[(size_t)fc]);
+          // one scale for the column from the exponent range of its values: the whole column is resident, so no pass is ever run again
+          DevBuf range, t192, t128;
+          range.ensure(64);
+          HIP_CHECK(hipMemsetAsync(range.p, 0, 16, stream_));
+          if (comet_launch_window_fexp(width, sc.data, vb, n, (uint64_t*)range.p, stream_) != 0) throw CometError("window: launch failed");
+          uint64_t hi_lo[2];
+          read_small(hi_lo, range.p, 16);
+          const int top = (int)hi_lo[0] - 1200, low = 1200 - (int)hi_lo[1];
+          int scale = hi_lo[0] ? fix_scale_for_range(top, low, kFixW) : 0;   // no finite non-zero value: every sum is 0
+          int windows = 1;
+          if (hi_lo[0] && scale != low) {
+            // the rule would truncate: cut the values into windows kFixW bits apart from the lowest bit up instead, one scan each — exact for any range
+            scale = low;
+            windows = (top - low + kFixW - 1) / kFixW;
+          }
+          auto S = std::make_shared<DevBuf>(), K = std::make_shared<DevBuf>();
+          S->ensure((size_t)n * 24 * (size_t)windows + 16);
+          K->ensure((size_t)n * 16 + 16);
+          t192.ensure((size_t)((n + 2047) / 2048 + 2) * 24);
+          t128.ensure((size_t)((n + 2047) / 2048 + 2) * 16);
+          for (int j = 0; j < windows; j++)
+            if (comet_launch_scan192_f64(width, sc.data, vb, n, scale + kFixW * j, windows > 1, t192.p, (char*)S->p + (size_t)j * (size_t)n * 24, stream_) != 0)
+              throw CometError("window: launch failed");
+          if (comet_launch_scan128_fclass(width, sc.data, vb, n, t128.p, K->p, stream_) != 0) throw CometError("window: launch failed");
+          HIP_CHECK(hipStreamSynchronize(stream_));   // scratch goes back to the pool
+          it = fprefix.emplace(fc, FloatPrefix{S, K, scale, windows}).first;
+        }
+        auto data = std::make_shared<DevBuf>(), okb = std::make_shared<DevBuf>(), bits = std::make_shared<DevBuf>();
+        data->ensure((size_t)n * 8 + 16);
+        okb->ensure((size_t)n + 16);
+        bits->ensure((size_t)((n + 7) / 8) + 16);
+        if (comet_launch_window_fagg(a.kind == AggKind::Avg ? 1 : 0, lo_kind, lo_off, hi_kind, hi_off, it->second.S->p, it->second.windows, it->second.K->p, it->second.scale, (const int32_t*)sp->p,
+                                     (const int32_t*)sg->p, (const uint32_t*)first_part->p, (const uint32_t*)first_peer->p, n, (double*)data->p, (uint8_t*)okb->p, stream_) != 0)
+          throw CometError("window: launch failed");
+        pq_launch_pack((const uint8_t*)okb->p, (uint8_t*)bits->p, n, stream_);
+        add_col(DType::of(TypeId::Double), data, bits);
         out.owners.push_back(okb);
         continue;
       }

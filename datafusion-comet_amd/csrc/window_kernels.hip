@@ -8,11 +8,15 @@
 //   row_number = i − ps + 1        rank = peer_start − ps + 1        dense_rank = g − g(ps) + 1
 //   percent_rank = (rank − 1) / (rows − 1)      cume_dist = (peer_end − ps) / rows      ntile(k): Spark's bucket formula
 // and lag / lead are a gather with index i ∓ k when that row lies inside the partition (otherwise NULL).
+// Aggregates over frames difference prefix sums at the frame's ends: 128-bit integers for exact types, 192-bit FIXED POINT for
+// Float64 / Float32 SUM and AVG ("Float sums over frames" below; device/window_fsum.hpp) — each frame's float sum is its exact real sum
+// rounded once; MIN / MAX come from running extremes per partition or a walk of the frame.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "device/comet_device.hpp"
+#include "device/window_fsum.hpp"
 
 using namespace comet;
 
@@ -123,15 +127,23 @@ __global__ __launch_bounds__(256) void window_widen_kernel(int width, const void
   }
 }
 
-constexpr int kScanTile = 2048;   // rows per block in the 128-bit scan (256 threads × 8)
+constexpr int kScanTile = 2048;   // rows per block in the wide scans (256 threads × 8)
 
-__global__ __launch_bounds__(256) void scan128_tile_sum_kernel(const i128* __restrict__ in, i64 n, u128* __restrict__ tiles) {
-  __shared__ u128 part[256];
+// Inclusive wrapping prefix sums of wide integers in three launches — per-tile totals, one block scanning the tile totals, then every tile
+// again with its carry-in.  T is the running word (u128, or the three limbs of U192); load(i) yields row i's addend, so an argument that is
+// CONVERTED on the way in (double → fixed point) is read at its own width and no widened copy of it exists.
+struct Load128 {
+  const i128* in;
+  __device__ u128 operator()(i64 i) const { return (u128)in[i]; }
+};
+template <class T, class L>
+__global__ __launch_bounds__(256) void scan_tile_sum_kernel(L load, i64 n, T* __restrict__ tiles) {
+  __shared__ T part[256];
   const i64 base = (i64)blockIdx.x * kScanTile;
-  u128 s = 0;
+  T s{};
   for (int k = 0; k < kScanTile / 256; k++) {
     const i64 i = base + (i64)threadIdx.x * (kScanTile / 256) + k;
-    if (i < n) s += (u128)in[i];
+    if (i < n) s += load(i);
   }
   part[threadIdx.x] = s;
   __syncthreads();
@@ -141,52 +153,125 @@ __global__ __launch_bounds__(256) void scan128_tile_sum_kernel(const i128* __res
   }
   if (threadIdx.x == 0) tiles[blockIdx.x] = part[0];
 }
-__global__ __launch_bounds__(256) void scan128_tiles_kernel(u128* tiles, i64 ntiles) {   // one block: exclusive scan of the tile sums
-  __shared__ u128 part[256];
+template <class T>
+__global__ __launch_bounds__(256) void scan_tiles_kernel(T* tiles, i64 ntiles) {   // one block: exclusive scan of the tile sums
+  __shared__ T part[256];
   const i64 per = (ntiles + 255) / 256, lo = (i64)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
-  u128 s = 0;
+  T s{};
   for (i64 t = lo; t < hi; t++) s += tiles[t];
   part[threadIdx.x] = s;
   __syncthreads();
   for (int st = 1; st < 256; st <<= 1) {
-    u128 add = (int)threadIdx.x >= st ? part[threadIdx.x - st] : (u128)0;
+    T add{};
+    if ((int)threadIdx.x >= st) add = part[threadIdx.x - st];
     __syncthreads();
     part[threadIdx.x] += add;
     __syncthreads();
   }
-  u128 run = threadIdx.x ? part[threadIdx.x - 1] : (u128)0;
+  T run{};
+  if (threadIdx.x) run = part[threadIdx.x - 1];
   for (i64 t = lo; t < hi; t++) {
-    const u128 v = tiles[t];
+    const T v = tiles[t];
     tiles[t] = run;
     run += v;
   }
 }
-__global__ __launch_bounds__(256) void scan128_apply_kernel(const i128* __restrict__ in, i64 n, const u128* __restrict__ tiles, i128* __restrict__ out) {
-  __shared__ u128 part[256];
+template <class T, class L>
+__global__ __launch_bounds__(256) void scan_apply_kernel(L load, i64 n, const T* __restrict__ tiles, T* __restrict__ out) {
+  __shared__ T part[256];
   const int per = kScanTile / 256;
   const i64 base = (i64)blockIdx.x * kScanTile + (i64)threadIdx.x * per;
-  u128 loc[kScanTile / 256];
-  u128 s = 0;
+  T loc[kScanTile / 256];
+  T s{};
   for (int k = 0; k < per; k++) {
     const i64 i = base + k;
-    s += i < n ? (u128)in[i] : (u128)0;
+    if (i < n) s += load(i);
     loc[k] = s;
   }
   part[threadIdx.x] = s;
   __syncthreads();
   // exclusive scan of the 256 per-thread sums (Hillis–Steele on LDS)
   for (int st = 1; st < 256; st <<= 1) {
-    u128 add = (int)threadIdx.x >= st ? part[threadIdx.x - st] : (u128)0;
+    T add{};
+    if ((int)threadIdx.x >= st) add = part[threadIdx.x - st];
     __syncthreads();
     part[threadIdx.x] += add;
     __syncthreads();
   }
-  const u128 before = tiles[blockIdx.x] + (threadIdx.x ? part[threadIdx.x - 1] : (u128)0);
+  T before = tiles[blockIdx.x];
+  if (threadIdx.x) before += part[threadIdx.x - 1];
   for (int k = 0; k < per; k++) {
     const i64 i = base + k;
-    if (i < n) out[i] = (i128)(before + loc[k]);
+    if (i < n) {
+      T o = before;
+      o += loc[k];
+      out[i] = o;
+    }
   }
 }
+// tiles: (n / 2048 + 2) words of scratch
+template <class T, class L>
+int launch_scan(L load, i64 n, T* tiles, T* out, hipStream_t st) {
+  if (n <= 0) return 0;
+  const i64 nt = (n + kScanTile - 1) / kScanTile;
+  hipLaunchKernelGGL((scan_tile_sum_kernel<T, L>), (int)nt, 256, 0, st, load, n, tiles);
+  hipLaunchKernelGGL((scan_tiles_kernel<T>), 1, 256, 0, st, tiles, nt);
+  hipLaunchKernelGGL((scan_apply_kernel<T, L>), (int)nt, 256, 0, st, load, n, (const T*)tiles, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- Float sums over frames (device/window_fsum.hpp holds the per-row math and the argument for exactness) ------------------------------
+// SUM / AVG of a Float64 / Float32 column over any frame, from three passes over the argument column (8 or 4 bytes per row each):
+//   1. the exponent range of its finite non-zero values (unsigned maxima of f64_exp_hi / f64_exp_lo) — the host picks ONE fixed-point
+//      scale s for the column from it (fix_scale.hpp; the whole column is resident, so nothing is ever re-run);
+//   2. scan192: inclusive 192-bit prefix sums of trunc(x / 2^s), converted in the scan's load (24 bytes per row written) — once per
+//      window when the column's values span more than one (then nothing is truncated: window_fsum.hpp);
+//   3. a 128-bit scan of the packed class words (non-NULL / +inf / −inf / NaN counters), converted in the load as well.
+// The frame kernel then differences both at the frame's ends: window_fagg_kernel.
+__global__ __launch_bounds__(256) void window_fexp_kernel(int width, const void* __restrict__ src, const u8* __restrict__ valid_bits, i64 n, u64* __restrict__ hi_lo) {
+  __shared__ u64 ph[256], pl[256];
+  u64 h = 0, l = 0;
+  for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+    if (!wf_valid(valid_bits, i)) continue;
+    const double x = wf_value(src, width, i);
+    const u64 xh = f64_exp_hi(x), xl = f64_exp_lo(x);
+    h = xh > h ? xh : h;
+    l = xl > l ? xl : l;
+  }
+  ph[threadIdx.x] = h;
+  pl[threadIdx.x] = l;
+  __syncthreads();
+  for (int st = 128; st >= 1; st >>= 1) {
+    if ((int)threadIdx.x < st) {
+      const u64 oh = ph[threadIdx.x + st], ol = pl[threadIdx.x + st];
+      if (oh > ph[threadIdx.x]) ph[threadIdx.x] = oh;
+      if (ol > pl[threadIdx.x]) pl[threadIdx.x] = ol;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (ph[0]) atomicMax(&hi_lo[0], ph[0]);
+    if (pl[0]) atomicMax(&hi_lo[1], pl[0]);
+  }
+}
+struct LoadFix192 {
+  const void* src;
+  const u8* valid_bits;
+  int width, scale;
+  __device__ U192 operator()(i64 i) const { return wf_fix(wf_valid(valid_bits, i), wf_value(src, width, i), scale); }
+};
+struct LoadFixSlice {   // one of several windows of a column too wide for one (wf_fix_slice)
+  const void* src;
+  const u8* valid_bits;
+  int width, scale;
+  __device__ U192 operator()(i64 i) const { return wf_fix_slice(wf_valid(valid_bits, i), wf_value(src, width, i), scale); }
+};
+struct LoadFClass {
+  const void* src;
+  const u8* valid_bits;
+  int width;
+  __device__ u128 operator()(i64 i) const { return wf_class_word(wf_valid(valid_bits, i), wf_value(src, width, i)); }
+};
 
 enum { WA_SUM_DEC = 0, WA_SUM_INT = 1, WA_COUNT = 2, WA_AVG_DEC = 3 };
 // A frame bound: the partition's edge, the current row (ROWS) or its peer group (RANGE), or the current row ± a literal number of rows
@@ -251,6 +336,37 @@ __global__ __launch_bounds__(256) void window_agg_kernel(int fn, WFrame frame, c
         break;
       }
     }
+  }
+}
+
+// S: inclusive 192-bit fixed-point prefix sums (scale s), K: inclusive prefix sums of the class words
+__global__ __launch_bounds__(256) void window_fagg_kernel(int fn, WFrame frame, const U192* __restrict__ S, const u128* __restrict__ K, int s, const i32* __restrict__ sp,
+                                                          const i32* __restrict__ sg, const u32* __restrict__ first_part, const u32* __restrict__ first_peer, i64 n,
+                                                          double* __restrict__ out, u8* __restrict__ out_ok) {
+  for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+    const i32 p = sp[i + 1] - 1, g = sg[i + 1] - 1;
+    i64 start, end;
+    frame_bounds(frame, i, (i64)first_part[p], (i64)first_part[p + 1], (i64)first_peer[g], (i64)first_peer[g + 1], start, end);
+    double v;
+    const bool ok = wf_frame(fn, S, K, start, end, s, v);
+    out[i] = v;
+    out_ok[i] = ok ? 1 : 0;
+  }
+}
+
+// the same over `windows` > 1 prefix arrays n rows apart (a column whose values span more than one fixed-point window): the frame's
+// differences are put together into one wide integer — a per-thread array, which is why the one-window kernel above stays apart
+__global__ __launch_bounds__(256) void window_fagg_wide_kernel(int fn, WFrame frame, const U192* __restrict__ S, int windows, const u128* __restrict__ K, int s,
+                                                               const i32* __restrict__ sp, const i32* __restrict__ sg, const u32* __restrict__ first_part,
+                                                               const u32* __restrict__ first_peer, i64 n, double* __restrict__ out, u8* __restrict__ out_ok) {
+  for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+    const i32 p = sp[i + 1] - 1, g = sg[i + 1] - 1;
+    i64 start, end;
+    frame_bounds(frame, i, (i64)first_part[p], (i64)first_part[p + 1], (i64)first_peer[g], (i64)first_peer[g + 1], start, end);
+    double v;
+    const bool ok = wf_frame_wide(fn, S, n, windows, K, start, end, s, v);
+    out[i] = v;
+    out_ok[i] = ok ? 1 : 0;
   }
 }
 
@@ -493,11 +609,32 @@ int comet_launch_window_widen(int width, const void* src, const uint8_t* valid_b
 }
 // inclusive prefix sums of n 128-bit integers (wrapping); tiles: (n / 2048 + 2) × 16 bytes of scratch
 int comet_launch_scan128(const void* in128, int64_t n, void* tiles, void* out128, void* stream) {
-  if (n <= 0) return 0;
-  const int64_t nt = (n + kScanTile - 1) / kScanTile;
-  hipLaunchKernelGGL(scan128_tile_sum_kernel, (int)nt, 256, 0, (hipStream_t)stream, (const i128*)in128, (i64)n, (u128*)tiles);
-  hipLaunchKernelGGL(scan128_tiles_kernel, 1, 256, 0, (hipStream_t)stream, (u128*)tiles, (i64)nt);
-  hipLaunchKernelGGL(scan128_apply_kernel, (int)nt, 256, 0, (hipStream_t)stream, (const i128*)in128, (i64)n, (const u128*)tiles, (i128*)out128);
+  return launch_scan<u128>(Load128{(const i128*)in128}, (i64)n, (u128*)tiles, (u128*)out128, (hipStream_t)stream);
+}
+// hi_lo[0] / [1] (zeroed by the caller): unsigned maxima of f64_exp_hi / f64_exp_lo over the column's non-NULL rows
+int comet_launch_window_fexp(int width, const void* src, const uint8_t* valid_bits, int64_t n, uint64_t* hi_lo, void* stream) {
+  if (n > 0) hipLaunchKernelGGL(window_fexp_kernel, grid_for(n), 256, 0, (hipStream_t)stream, width, src, valid_bits, (i64)n, (u64*)hi_lo);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// inclusive 192-bit prefix sums of trunc(x / 2^scale) over a Float64 / Float32 column; tiles: (n / 2048 + 2) × 24 bytes, out192: n × 24 bytes
+// (slice: only the value bits of weight 2^scale … 2^(scale + 157) — one window of several)
+int comet_launch_scan192_f64(int width, const void* src, const uint8_t* valid_bits, int64_t n, int scale, int slice, void* tiles, void* out192, void* stream) {
+  if (slice) return launch_scan<U192>(LoadFixSlice{src, valid_bits, width, scale}, (i64)n, (U192*)tiles, (U192*)out192, (hipStream_t)stream);
+  return launch_scan<U192>(LoadFix192{src, valid_bits, width, scale}, (i64)n, (U192*)tiles, (U192*)out192, (hipStream_t)stream);
+}
+// inclusive 128-bit prefix sums of the column's class words; tiles: (n / 2048 + 2) × 16 bytes, out128: n × 16 bytes
+int comet_launch_scan128_fclass(int width, const void* src, const uint8_t* valid_bits, int64_t n, void* tiles, void* out128, void* stream) {
+  return launch_scan<u128>(LoadFClass{src, valid_bits, width}, (i64)n, (u128*)tiles, (u128*)out128, (hipStream_t)stream);
+}
+int comet_launch_window_fagg(int fn, int lo_kind, int64_t lo_off, int hi_kind, int64_t hi_off, const void* S192, int windows, const void* K128, int scale, const int32_t* sp,
+                             const int32_t* sg, const uint32_t* first_part, const uint32_t* first_peer, int64_t n, double* out, uint8_t* out_ok, void* stream) {
+  if (windows < 1 || windows > kWfMaxWindows) return -1;
+  if (n > 0 && windows > 1)
+    hipLaunchKernelGGL(window_fagg_wide_kernel, grid_for(n), 256, 0, (hipStream_t)stream, fn, WFrame{lo_kind, hi_kind, (i64)lo_off, (i64)hi_off}, (const U192*)S192, windows,
+                       (const u128*)K128, scale, sp, sg, first_part, first_peer, (i64)n, out, out_ok);
+  else if (n > 0)
+    hipLaunchKernelGGL(window_fagg_kernel, grid_for(n), 256, 0, (hipStream_t)stream, fn, WFrame{lo_kind, hi_kind, (i64)lo_off, (i64)hi_off}, (const U192*)S192, (const u128*)K128, scale, sp, sg,
+                       first_part, first_peer, (i64)n, out, out_ok);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // one direction of the running extremes: scratch `local` n × 32 bytes, `tiles` 2 × (n / 1024 + 1) × 32 bytes

@@ -180,8 +180,10 @@ def probes():
     return P
 
 
-ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64 (exact, order independent)", "Average": "decimals and Float64", "Count": "", "Min": "not decimal(>18) in grouped aggregates",
-                       "Max": "not decimal(>18) in grouped aggregates", "First": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
+ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64 / Float32 (exact, order independent; over window frames too)",
+                       "Average": "decimals and Float64 / Float32, in aggregates and over window frames", "Count": "",
+                       "Min": "not decimal(>18) in grouped aggregates; over window frames integers, decimals, dates and timestamps (not floats)",
+                       "Max": "not decimal(>18) in grouped aggregates; over window frames integers, decimals, dates and timestamps (not floats)", "First": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
                        "Last": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
                        "BitAndAgg": "Byte / Short / Int / Long, not over window frames", "BitOrAgg": "Byte / Short / Int / Long, not over window frames",
                        "BitXorAgg": "Byte / Short / Int / Long, not over window frames",
@@ -270,7 +272,7 @@ def render() -> str:
     w("* `RLike`: patterns outside the byte-exact subset (`\\\\p{..}`, scoped flags, look-around, `\\\\b` under `(?m)`) are refused by name.")
     w("* `Concat`: of Utf8 columns and literals (at most eight), as an output column.")
     w("* Computed Utf8 values used as operands of further expressions must fit 15 bytes (literals, substring, CASE over those).")
-    w("* Window: RANGE frames with value offsets over non-integer keys, floating-point aggregates over frames, MIN / MAX over sliding frames wider")
+    w("* Window: RANGE frames with value offsets over non-integer keys, MIN / MAX of floats over frames, MIN / MAX over sliding frames wider")
     w("  than 4096 rows, lag / lead defaults of Utf8 / Boolean type.")
     w("* Nested types: struct-of-flat, list-of-flat, list-of-flat-struct and map columns are read from Parquet, passed through Filter / Projection / Sort /")
     w("  Limit / ShuffleWriter, taken apart by `GetStructField` and exported; struct / list columns of any depth arrive through Scan / ShuffleScan inputs;")
@@ -288,6 +290,14 @@ def render() -> str:
     w("* Float64 / Float32 `sum` and `avg`: the reference adds in row order (its result moves with batch and partition boundaries); here the sum is the EXACT real sum")
     w("  rounded once — the same bits for every order, chunking and grid, at most half an ulp from the truth, within the reference's own a-priori error bound of its")
     w("  sequential sum and bit-equal to it wherever that one is exact (`tests/test_float_agg_gpu.py`).  Up to eight such sums per aggregate.")
+    w("* Float64 / Float32 `sum` and `avg` over a window frame: each row's result is its frame's EXACT real sum rounded once (`avg`: divided by the frame's non-NULL")
+    w("  count in one IEEE division) — the same bits for every scan tiling and input batching, and independent of what earlier frames held")
+    w("  (`tests/test_window_float_gpu.py`).  The reference's sliding frames use a retracting accumulator (add the entering row, subtract the leaving one), whose")
+    w("  rounding errors drift along the partition and which stays NaN for the rest of the partition once an inf has entered and left; here a frame that no longer")
+    w("  holds an inf or NaN is finite again, which is Spark's own answer.  One fixed-point scale serves a whole argument column; where the grouped sums' rule would")
+    w("  truncate — the column's finite non-zero values span more than 148 binary orders of magnitude, from the lowest set bit to the top — the column is cut into")
+    w("  several 158-bit windows with prefix sums of their own (24 bytes per row and window) and nothing is truncated: a truncated bit could decide a tie of the final")
+    w("  rounding, one ulp of the result.")
     w("* `var_samp` / `var_pop`, `stddev_samp` / `stddev_pop`, `covar_samp` / `covar_pop`, `corr`: the reference runs Welford's recurrence in row order and")
     w("  merges states pairwise, so its states move with batch boundaries and its m2 loses about log2(mean² / variance) bits.  Here the moments come from exact")
     w("  Float64 sums of x, y, x², y², x·y (products split exactly with fma): the results are deterministic (the same bits for every order, chunking and grid); a")
