@@ -24,6 +24,7 @@ static_assert(comet::kErrBytes == COMET_ERR_BYTES && comet::kErrAuxWords == COME
 #include <cmath>
 #include <cstring>
 #include <functional>
+#include <set>
 #include <sstream>
 
 namespace comet {
@@ -57,12 +58,23 @@ thread_local bool g_uses_regex_vm = false; // … into comet_regex_vm.hpp (regex
 // the pipeline being generated: where raise sites with a QueryContext are noted, and how many sites of each content it has seen (err_sites.cpp)
 thread_local std::vector<std::pair<uint32_t, std::shared_ptr<QueryContext>>>* g_site_sink = nullptr;
 thread_local std::map<std::string, int>* g_site_ordinals = nullptr;
+// … and where its might_contain expressions note the filters they probe (PipelineDesc::blooms) and themselves (at most kMaxBloomProbes per chain)
+thread_local std::vector<PipelineDesc::BloomRef>* g_bloom_sink = nullptr;
+thread_local std::set<std::string>* g_bloom_seen = nullptr;
+constexpr size_t kMaxBloomProbes = 4;
 struct SiteScope {
   std::map<std::string, int> ordinals;
+  std::set<std::string> bloom_seen;
   // (the optional-header flags start clean: a generation that threw after setting one must not make the next, unrelated kernel include the tables)
-  explicit SiteScope(PipelineDesc& d) { g_site_sink = &d.site_contexts; g_site_ordinals = &ordinals; g_uses_ryu = g_uses_strtod = g_uses_strts = g_uses_regex_vm = false; }
-  ~SiteScope() { g_site_sink = nullptr; g_site_ordinals = nullptr; }
+  explicit SiteScope(PipelineDesc& d) { g_site_sink = &d.site_contexts; g_site_ordinals = &ordinals; g_bloom_sink = &d.blooms; g_bloom_seen = &bloom_seen; g_uses_ryu = g_uses_strtod = g_uses_strts = g_uses_regex_vm = false; }
+  ~SiteScope() { g_site_sink = nullptr; g_site_ordinals = nullptr; g_bloom_sink = nullptr; g_bloom_seen = nullptr; }
 };
+// the filters' buffers travel in the kernel-argument slots the columns leave free, from the top down
+void check_bloom_slots(const PipelineDesc& d, size_t column_slots) {
+  if (column_slots + d.blooms.size() > COMET_MAX_IN)
+    throw CometError("might_contain: no kernel-argument slot is left for the bloom filter (" + std::to_string(column_slots) + " columns and " + std::to_string(d.blooms.size()) +
+                     " filters, " + std::to_string(COMET_MAX_IN) + " slots)");
+}
 std::string with_optional_headers(std::string src) {
   if (g_uses_ryu) {
     const std::string inc = "using namespace comet;\n";
@@ -445,6 +457,13 @@ struct Gen {
     auto it = keymemo.find(e.get());
     if (it != keymemo.end()) return it->second;
     std::ostringstream k;
+    if (e->kind == ExprKind::BloomMightContain && e->children.size() == 2) {
+      // the filter is named by its node (a Subquery becomes a Literal in place), never by its bytes
+      k << "BF" << (const void*)e->children[0].get() << "(" << key_of(e->children[1]) << ")";
+      keymemo[e.get()] = k.str();
+      keymemo_alive.push_back(e);
+      return k.str();
+    }
     k << (int)e->kind << ":" << (int)e->dtype.id << "," << e->dtype.precision << "," << e->dtype.scale << ":"
       << (int)e->eval_mode << e->fail_on_error << e->negated;
     if (e->kind == ExprKind::Bound) k << "#" << e->bound_index;
@@ -2682,6 +2701,7 @@ struct Gen {
         return literal(nul);
       }
       case ExprKind::ListExtract: return list_extract(e);
+      case ExprKind::BloomMightContain: return bloom_might_contain(e);
       case ExprKind::TruncTimestamp: {
         // timestamp_trunc (datetime_funcs/timestamp_trunc.rs → kernels/temporal.rs:179-270, 587-625): the instant's wall clock in the zone cut to the
         // unit, read back as an instant.  The reference sends it for UTC only unless allowIncompatible (datetime.scala CometTruncTimestamp): zones
@@ -2811,6 +2831,42 @@ struct Gen {
         throw CometError(std::string("Expression ") + expr_name(e.proto_tag) + " (tag " + std::to_string(e.proto_tag) +
                          ") is not supported by the MI355X native engine");
     }
+  }
+
+  // might_contain(filter, value) (planner.rs:745-766; bloom_filter_might_contain.rs): the filter is constant at plan time — a Binary Literal, or a Binary
+  // Subquery that is one by the first executePlan — and reaches the kernel as a BUFFER in a kernel-argument slot (device/bloom.hpp's layout), bound by
+  // the executor: the text below names the slot and nothing else, so plans that differ in the filter's bytes, size, k or version share one code object.
+  // A NULL filter is known here and yields NULL for every row; a NULL value yields NULL.
+  Val bloom_might_contain(const Expr& e) {
+    if (e.children.size() != 2) throw CometError("might_contain expects a bloom filter and a value");
+    const ExprP& fe = e.children[0];
+    if ((fe->kind != ExprKind::Literal && fe->kind != ExprKind::Subquery) || !fe->has_dtype || fe->dtype.id != TypeId::Bytes)
+      throw CometError(std::string("might_contain: the bloom filter must be a Binary literal or a Binary scalar subquery, got ") + expr_name(fe->proto_tag) +
+                       (fe->has_dtype ? " of type " + fe->dtype.str() : std::string()));
+    Val v = named(gen(e.children[1]));
+    if (v.t.id != TypeId::Int64) throw CometError("might_contain: the value must be Int64 (Spark sends xxhash64(…)), got " + v.t.str());
+    if (!g_bloom_sink || !g_bloom_seen) throw CometError("might_contain is not supported in this position");
+    g_bloom_seen->insert(key_of(e.children[1]) + "@" + std::to_string((uintptr_t)fe.get()));
+    if (g_bloom_seen->size() > kMaxBloomProbes)
+      throw CometError("might_contain: more than " + std::to_string(kMaxBloomProbes) + " bloom filter probes in one fused chain are not supported");
+    Val r;
+    r.t = DType::of(TypeId::Bool);
+    r.rep = Rep::B;
+    if (fe->kind == ExprKind::Literal && fe->lit_null) {
+      r.v = "false";
+      r.ok = "false";
+      return r;
+    }
+    if (fe->kind == ExprKind::Literal) bloom_check_bytes((const uint8_t*)fe->lit_bytes.data(), fe->lit_bytes.size());      // (refused at createPlan already)
+    size_t j = 0;
+    while (j < g_bloom_sink->size() && (*g_bloom_sink)[j].node.get() != fe.get()) j++;
+    if (j == g_bloom_sink->size()) g_bloom_sink->push_back({fe, fe->subquery_id});
+    if (j >= COMET_MAX_IN) throw CometError("might_contain: no kernel-argument slot is left for the bloom filter");
+    const std::string b = newvar("bool");
+    stmt(b + " = " + (v.ok.empty() ? std::string() : v.ok + " && ") + "comet::bloom_might_contain((const u64*)prm.in[" + std::to_string(COMET_MAX_IN - 1 - (int)j) + "].data, (i64)" + v.v + ");");
+    r.v = b;
+    r.ok = v.ok;
+    return r;
   }
 
   // Filter conjunct: rows survive only where the predicate is TRUE and valid
@@ -4412,6 +4468,7 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
     sink.lower_aggregates(f.agg_ins);
     sink.finish(src, make_gen, source_types != nullptr);
   }
+  check_bloom_slots(d, d.in_types.size());
   d.source = with_optional_headers(src.str());
   d.explain = ex.str();
   return d;
@@ -4882,6 +4939,7 @@ PipelineDesc generate_join(const Operator& j, const std::vector<DType>& lt_in, c
   ex << "  hash join: " << shape.name << ", build " << (bl ? "left" : "right") << ", " << j.left_keys.size() << " key(s)"
      << (fu ? ", probe side fused with its Filter / Projection chain" : "") << (fub ? ", build side fused with its chain" : "") << "\n";
   d.in_types = g.ct;
+  check_bloom_slots(d, build.ncols() + probe.ncols());
   d.source = with_optional_headers(src.str());
   d.explain = ex.str();
   return d;
@@ -4986,6 +5044,7 @@ PipelineDesc generate_sort_keys(const Operator& sort, const std::vector<DType>& 
       << "  for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < prm.n; i += (i64)gridDim.x * 256) P::keys(prm, i);\n}\n";
   d.kernels = {"k_sortkey"};
   d.sort_key_bytes = W;
+  check_bloom_slots(d, types.size());
   if (sort.fetch >= 0) ex << "  fetch " << sort.fetch << "\n";
   d.source = with_optional_headers(src.str());
   d.explain = ex.str();

@@ -75,6 +75,11 @@ struct PipelineDesc {
   // overflowed, so a context is attached only when all of a kind that carry one carry the same; agg_ctx_mixed[k]: they differ
   std::shared_ptr<QueryContext> agg_ctx[2];
   bool agg_ctx_mixed[2] = {false, false}, agg_ctx_seen[2] = {false, false};
+  // the Bloom filters the pipeline's might_contain expressions probe: blooms[j] is bound by the executor (device/bloom.hpp's layout) to
+  // prm.in[COMET_MAX_IN − 1 − j].data.  node: the filter argument (a Literal, or a Subquery that becomes one); subquery_id ≥ 0: the executing
+  // context looks the value up under that id (a cached pipeline's nodes may belong to another task's decode of the same plan bytes)
+  struct BloomRef { ExprP node; int64_t subquery_id = -1; };
+  std::vector<BloomRef> blooms;
   std::string source;              // full HIP translation unit
   std::vector<std::string> kernels;  // extern "C" kernel names present in `source`
   // static row bound under which decimal sums cannot overflow (Appendix C.1 rule); 0 = no limit
@@ -165,6 +170,9 @@ bool lookup_err_site(uint32_t id, ErrSite& out);
 std::string err_site_json(const ErrSite& s, uint64_t lo, uint64_t hi, const uint8_t* str, size_t str_avail, const QueryContext* ctx = nullptr);
 // DecimalSumOverflow of an ANSI decimal sum (kind 0) / average (1), with the aggregate's context when the plan carried one
 std::string decimal_sum_overflow_json(int kind, const QueryContext* ctx);
+// Spark's serialized BloomFilter (V1 / V2), bytes from outside the process: exec_bloom.cpp checks version, 1 ≤ k ≤ 255, 1 ≤ numWords, numWords · 64 < 2^31
+// and the length, and throws a CometError naming might_contain otherwise
+void bloom_check_bytes(const uint8_t* p, size_t len);
 constexpr int kOutFirstCol = 4;      // out[4+2j] = values of col j, out[5+2j] = validity bytes of col j
 
 }  // namespace comet

@@ -1160,6 +1160,11 @@ CDEV i32 pmod(u32 hash, i32 n) {
   return r < 0 ? (r + n) % n : r;
 }
 
+}  // namespace comet
+// Spark's BloomFilter over longs: index generator, bit test / set, device layout (plain C++ the host compiles too)
+#include "bloom.hpp"
+namespace comet {
+
 // ---------------------------------------------------------------------------------------------
 // Wave / block primitives (wave = 64 lanes).
 // ---------------------------------------------------------------------------------------------

@@ -266,6 +266,10 @@ ExecutionContext::ExecutionContext(OperatorP plan, uint64_t plan_hash, std::vect
         node_id_[pr.get()] = (int)node_id_.size();
       }
     }
+    if (is_bloom_agg(op)) {
+      bloom_agg_spec(op);      // (refuses grouped / mixed / filtered shapes and parameters out of range, by name)
+      has_join_ = true;        // runs as an operator over its materialised child
+    }
     if (op.kind == OpKind::HashAgg && &op != plan_.get()) {
       // an aggregate below other operators: materialised too, unless it is the sink of the root chain (checked below)
       nested_aggs_.push_back(&op);
@@ -351,7 +355,7 @@ ExecutionContext::ExecutionContext(OperatorP plan, uint64_t plan_hash, std::vect
 bool ExecutionContext::is_source(const Operator& op, const Operator* chain_top) {
   switch (op.kind) {
     case OpKind::Explode: case OpKind::Scan: case OpKind::HashJoin: case OpKind::NativeScan: case OpKind::Sort: case OpKind::Limit: case OpKind::ShuffleWriter: case OpKind::Expand: case OpKind::Window: return true;
-    case OpKind::HashAgg: return &op != chain_top;
+    case OpKind::HashAgg: return &op != chain_top || is_bloom_agg(op);
     default: return false;
   }
 }
@@ -754,6 +758,42 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
     explain_ += "  shuffle writer: " + std::to_string(op.shuffle_num_partitions) + " partition(s), codec " + std::to_string(op.shuffle_codec) + "\n";
     return {};
   }
+  if (is_bloom_agg(op)) {
+    // ObjectHashAggregate(keys = [], [bloom_filter_agg(child, numItems, numBits)]) (planner.rs:2877-2897): one row, one Binary column.  Partial evaluates the
+    // child expression with a fused Projection over the resident child; PartialMerge / Final read the Binary state column
+    if (op.children.size() != 1) throw CometError("HashAggregate expects exactly one child");
+    const BloomAggSpec spec = bloom_agg_spec(op);
+    std::vector<DType> st = infer_schema(*op.children[0]);
+    if (op.agg_mode == AggMode::Partial) {
+      auto sc = std::make_shared<Operator>();
+      sc->kind = OpKind::Scan;
+      sc->proto_tag = 100;
+      sc->scan_fields = st;
+      auto pr = std::make_shared<Operator>();
+      pr->kind = OpKind::Projection;
+      pr->proto_tag = 101;
+      pr->children.push_back(sc);
+      pr->project_list = op.agg_exprs[0].children;
+      node_id_[pr.get()] = (int)node_id_.size();
+      std::vector<DType> ext = extend_struct_field_types(st);
+      std::vector<bool> none(ext.size(), false);
+      PipelineDesc d = generate_pipeline(*pr, none, &ext);
+      const DType& ct = d.out_cols.at(0).type;
+      if (ct.id == TypeId::String || ct.id == TypeId::Bytes)
+        throw CometError("bloom_filter_agg over a " + ct.str() + " child is not supported by the MI355X native engine: might_contain probes longs only, such a filter could not be used natively");
+      if (!ct.is_integer()) throw CometError("bloom_filter_agg over " + ct.str() + " is not supported (Byte, Short, Int and Long are)");
+      if (compile_in_infer_) jit_compile(d.source);
+      explain_ += d.explain;
+      bloom_proj_[&op] = pr;
+    } else {
+      const size_t sc = (size_t)std::max(0, op.initial_input_buffer_offset);
+      if (sc >= st.size() || st[sc].id != TypeId::Bytes)
+        throw CometError("bloom_filter_agg: the merging aggregate expects its Binary state in column " + std::to_string(sc) + " of its child");
+    }
+    explain_ += std::string("  bloom_filter_agg (") + (op.agg_mode == AggMode::Partial ? "Partial" : op.agg_mode == AggMode::Final ? "Final" : "PartialMerge") + "): V" +
+                std::to_string(spec.version) + ", " + std::to_string(spec.k) + " hash function(s), " + std::to_string(spec.num_words * 64) + " bits\n";
+    return {DType::of(TypeId::Bytes)};
+  }
   if (op.kind == OpKind::NativeScan) {
     std::vector<DType> out;
     for (auto& f : op.required_schema) out.push_back(f.dtype);
@@ -995,6 +1035,7 @@ Variant& ExecutionContext::variant_for(const std::vector<bool>& has_valid, const
 
 void ExecutionContext::launch(Variant& v, const char* kernel, int grid, CometKParams& prm, int block) {
   hipFunction_t fn = v.mod->fn(kernel);
+  if (!v.desc.blooms.empty()) bind_blooms(v.desc, prm);
   void* args[] = {&prm};
   // COMET_KERNEL_TIMES=1 / comet_set_kernel_times(1) (a measurement switch, off by default): an event pair around EVERY generated-kernel launch, summed per kernel
   // name (comet_plan_kernel_times) — what bench.py's Q3 / Q95 rooflines name their dominant kernel from
@@ -1657,6 +1698,10 @@ DevTable ExecutionContext::materialize(const Operator& op) {
     DevTable in = materialize(*op.children[0]);
     return window(op, in);
   }
+  if (is_bloom_agg(op)) {
+    DevTable in = materialize(*op.children[0]);
+    return bloom_aggregate(op, in);
+  }
   if (op.kind == OpKind::HashAgg) return nested_aggregate(op);   // an aggregate below other operators
   // Filter / Projection chain: fused over its source
   const Operator* src = &op;
@@ -1697,6 +1742,7 @@ DevTable ExecutionContext::nested_aggregate(const Operator& agg) {
   mark("context built");
   if (sub.sink_ != SinkKind::AggGrouped && sub.sink_ != SinkKind::AggNoGroup) throw CometError("internal: nested aggregate without an aggregate sink");
   sub.device_result_ = true;
+  sub.blooms_ = blooms_;      // (the filters its chain's might_contain probes are this plan's)
   sub.start();
   mark("started");
   sub.run_to_completion();
@@ -2089,6 +2135,15 @@ void ExecutionContext::resolve_subqueries() {
     }
     mix(&id, 8);
     mix(&is_null, 1);
+    if (e->bloom_arg) {
+      // might_contain's filter: a buffer bound at launch, no part of any kernel's text — tasks with different filters share their pipelines.  Bytes from
+      // outside the process: checked here, before anything is launched
+      if (e->dtype.id != TypeId::Bytes) throw CometError("might_contain: the bloom filter subquery must be Binary, got " + e->dtype.str());
+      if (!is_null) bloom_check_bytes((const uint8_t*)e->lit_bytes.data(), e->lit_bytes.size());
+      if (!blooms_) blooms_ = std::make_shared<BloomRegistry>();
+      blooms_->subquery_nodes[id] = e;
+      continue;
+    }
     mix(v.data(), v.size());
   }
   // the plan's kernels carry the values: planned anew, under a hash that names them

@@ -135,6 +135,18 @@ struct Variant {  // one JIT specialisation of the pipeline (per input-validity 
   std::shared_ptr<LoadedModule> mod;
 };
 
+// bloom_filter_agg's filter as its literals give it (exec_bloom.cpp bloom_agg_spec: refuses, by name, what this engine does not run)
+struct BloomAggSpec { int version = 1, k = 1; int64_t num_words = 0; };
+BloomAggSpec bloom_agg_spec(const Operator& hash_agg);
+bool is_bloom_agg(const Operator& op);      // a HashAggregate that holds a bloom_filter_agg
+// The Bloom filters a plan's might_contain expressions probe, resident for the plan's life: uploaded once (device/bloom.hpp's layout), shared with
+// the sub-contexts of nested aggregates.  subquery_nodes: subquery id → the node that became a Literal (resolve_subqueries)
+struct BloomRegistry {
+  std::map<int64_t, ExprP> subquery_nodes;
+  std::map<const Expr*, std::shared_ptr<struct DevBuf>> buffers;
+  std::vector<ExprP> keep;
+};
+
 // parquet_scan.cpp: run fn(0..n-1) on the process-wide scan threads and wait
 void scan_pool_parallel(size_t n, const std::function<void(size_t)>& fn);
 // row-group / page-index selection of a NativeScan as JSON (parquet_scan.cpp; host only)
@@ -226,6 +238,9 @@ class ExecutionContext {
   DevTable expand(const Operator& ex, const DevTable& in);
   DevTable explode(const Operator& ex, const DevTable& in);
   DevTable window(const Operator& w, const DevTable& in);
+  DevTable bloom_aggregate(const Operator& agg, const DevTable& in);      // exec_bloom.cpp
+  const void* bloom_buffer(const PipelineDesc::BloomRef& ref);
+  void bind_blooms(const PipelineDesc& d, CometKParams& prm);            // might_contain's filters → the kernel-argument slots the pipeline names
   void prepare_dict_keys(DevTable& src);
   static bool is_source(const Operator& op, const Operator* chain_top);
   typedef std::function<std::pair<const DevTable*, int>(int)> GatherSource;   // OutCol::gather_src → (table, column)
@@ -323,6 +338,8 @@ class ExecutionContext {
     std::vector<OutCol> out_cols;   // unified output schema
   };
   std::map<const Operator*, ExpandInfo> expand_info_;
+  std::map<const Operator*, OperatorP> bloom_proj_;     // bloom_filter_agg (Partial) → the synthetic Projection that evaluates its child into one integer column
+  std::shared_ptr<BloomRegistry> blooms_;
   std::map<const Operator*, OperatorP> explode_proj_;   // Explode → the synthetic Projection of the columns it carries alongside
   std::map<const Operator*, OperatorP> window_psort_, window_osort_;   // Window → synthetic Sorts describing its partition / order keys
   std::map<const Operator*, OperatorP> range_sort_, range_bsort_;   // ShuffleWriter(range) → synthetic Sort over its rows / its boundary rows

@@ -69,6 +69,7 @@ enum class ExprKind : int {
   UnaryMinus = 41, ShiftRight = 42, ShiftLeft = 43, If = 44, IntegralDivide = 59, NormalizeNaNAndZero = 45, Unbound = 51,
   GetStructField = 54,              // expr.proto:528-531: child = 1, ordinal = 2 (kept in Expr::bound_index)
   Subquery = 50,                    // expr.proto:513-516: a scalar subquery's result — id = 1 (kept in Expr::lit_i64), datatype = 2; a Literal once the executor has asked for it
+  BloomMightContain = 52,           // expr.proto:518-521: bloom_filter = 1, value = 2 (children = [filter, value]); the filter a Binary Literal or Subquery
   ListExtract = 56,                 // expr.proto:533-539: children = [child, ordinal, (default value)], one_based, fail_on_error
   Unsupported = -1
 };
@@ -108,6 +109,8 @@ struct Expr {
   double lit_f64 = 0;             // float/double
   i128 lit_dec = 0;               // decimal unscaled value (literal.proto:38, BE two's complement)
   std::string lit_bytes;          // string/bytes
+  int64_t subquery_id = -1;       // a Subquery's id, kept when the node becomes a Literal (resolve_subqueries)
+  bool bloom_arg = false;         // the filter argument of a BloomMightContain: its bytes are bound as a buffer, never part of a kernel's text
   int lit_case = 0;               // which Literal.value arm was present (1..11), 0 = none
   uint64_t expr_id = 0;
   bool has_expr_id = false;
@@ -116,6 +119,7 @@ struct Expr {
 
 // AggExpr.expr_struct oneof tags (expr.proto:143-176)
 enum class AggKind : int { Count = 2, Sum = 3, Min = 4, Max = 5, Avg = 6, First = 7, Last = 8, BitAnd = 9, BitOr = 10, BitXor = 11, Covariance = 12, Variance = 13, Stddev = 14, Correlation = 15,
+                           BloomFilter = 16,      // expr.proto:289-299: child = 1, numItems = 2, numBits = 3, datatype = 4, version = 5
                            Unsupported = -1 };
 
 struct AggExpr {
@@ -129,6 +133,8 @@ struct AggExpr {
   bool ignore_nulls = false;      // First / Last
   int stats_type = 0;             // Variance / Stddev / Covariance: StatisticsType (expr.proto:178-181) 0 SAMPLE, 1 POPULATION
   bool null_on_divide_by_zero = false;   // Variance / Stddev / Covariance / Correlation
+  ExprP bloom_num_items, bloom_num_bits;   // BloomFilter: the two Int64 literals
+  int bloom_version = 1;                   // BloomFilter: BloomFilterVersion (0 unspecified → V1, 1 V1, 2 V2)
   uint64_t expr_id = 0;
   bool has_expr_id = false;
   std::shared_ptr<QueryContext> qctx;      // AggExpr.query_context = 90: goes with the aggregate's DecimalSumOverflow (sum_decimal.rs wrap_error_with_context)
@@ -154,6 +160,21 @@ inline const char* order_bit_agg_name(AggKind k) {
     case AggKind::BitAnd: return "bit_and";
     case AggKind::BitOr: return "bit_or";
     case AggKind::BitXor: return "bit_xor";
+    default: return nullptr;
+  }
+}
+
+// Spark's SQL name of an aggregate, for messages ("sum", "bloom_filter_agg" …); nullptr for an unknown tag
+inline const char* agg_name(const AggExpr& a) {
+  if (const char* n = stat_agg_name(a)) return n;
+  if (const char* n = order_bit_agg_name(a.kind)) return n;
+  switch (a.kind) {
+    case AggKind::Count: return "count";
+    case AggKind::Sum: return "sum";
+    case AggKind::Min: return "min";
+    case AggKind::Max: return "max";
+    case AggKind::Avg: return "avg";
+    case AggKind::BloomFilter: return "bloom_filter_agg";
     default: return nullptr;
   }
 }

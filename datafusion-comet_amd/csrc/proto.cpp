@@ -323,11 +323,28 @@ ExprP decode_expr(Reader r) {
         Reader b = r.sub();
         while (!b.done()) {
           int wt2, f2 = b.tag(wt2);
-          if (f2 == 1 && wt2 == 0) e->lit_i64 = (int64_t)b.varint();
+          if (f2 == 1 && wt2 == 0) e->subquery_id = e->lit_i64 = (int64_t)b.varint();
           else if (f2 == 2 && wt2 == 2) { e->dtype = decode_datatype(b.sub()); e->has_dtype = true; }
           else b.skip(wt2);
         }
+        if (e->subquery_id < 0) e->subquery_id = 0;      // (proto3 omits a zero id)
         if (g_decoded_subqueries) g_decoded_subqueries->push_back(e);
+        break;
+      }
+      case 52: {      // BloomFilterMightContain{bloom_filter = 1, value = 2} (expr.proto:518-521): children = [filter, value]
+        e->kind = ExprKind::BloomMightContain;
+        ExprP kids[2];
+        Reader b = r.sub();
+        while (!b.done()) {
+          int wt2, f2 = b.tag(wt2);
+          if ((f2 == 1 || f2 == 2) && wt2 == 2) kids[f2 - 1] = decode_expr(b.sub());
+          else b.skip(wt2);
+        }
+        if (!kids[0] || !kids[1]) throw CometError("might_contain expects a bloom filter and a value");
+        kids[0]->bloom_arg = true;
+        e->children = {kids[0], kids[1]};
+        e->dtype = DType::of(TypeId::Bool);
+        e->has_dtype = true;
         break;
       }
       case 3: case 4: case 5: case 6: case 7: case 8: case 9: case 10: case 11: case 12: case 13: case 14:
@@ -355,8 +372,23 @@ AggExpr decode_agg_expr(Reader r) {
     if (f == 90 || wt != 2) { r.skip(wt); continue; }
     a.proto_tag = f;
     Reader b = r.sub();
-    if (f >= 2 && f <= 15) a.kind = (AggKind)f;      // (9-11: BitAndAgg / BitOrAgg / BitXorAgg{child = 1, datatype = 2}, expr.proto:222-235)
+    if (f >= 2 && f <= 16) a.kind = (AggKind)f;      // (9-11: BitAndAgg / BitOrAgg / BitXorAgg{child = 1, datatype = 2}, expr.proto:222-235)
     else { a.kind = AggKind::Unsupported; continue; }
+    if (f == 16) {
+      // BloomFilterAgg{child = 1, numItems = 2, numBits = 3, datatype = 4, version = 5} (expr.proto:289-305)
+      ExprP child;
+      while (!b.done()) {
+        int wt2, f2 = b.tag(wt2);
+        if (f2 == 1 && wt2 == 2) child = decode_expr(b.sub());
+        else if (f2 == 2 && wt2 == 2) a.bloom_num_items = decode_expr(b.sub());
+        else if (f2 == 3 && wt2 == 2) a.bloom_num_bits = decode_expr(b.sub());
+        else if (f2 == 4 && wt2 == 2) a.dtype = decode_datatype(b.sub());
+        else if (f2 == 5 && wt2 == 0) a.bloom_version = b.varint() == 2 ? 2 : 1;      // (planner.rs:2884-2889: everything but V2 is V1)
+        else b.skip(wt2);
+      }
+      if (child) a.children.push_back(child);
+      continue;
+    }
     if (f >= 12 && f <= 15) {
       // Covariance{child1 = 1, child2 = 2, null_on_divide_by_zero = 3, datatype = 4, stats_type = 5}, Variance / Stddev{child = 1,
       // null_on_divide_by_zero = 2, datatype = 3, stats_type = 4}, Correlation{child1 = 1, child2 = 2, null_on_divide_by_zero = 3, datatype = 4}
@@ -927,7 +959,7 @@ const char* expr_name(int t) {
     case 19: return "SortOrder"; case 25: return "CheckOverflow"; case 26: return "Like"; case 30: return "RLike"; case 31: return "ScalarFunc";
     case 32: return "EqNullSafe"; case 33: return "NeqNullSafe"; case 37: return "Remainder"; case 38: return "CaseWhen";
     case 39: return "In"; case 40: return "Not"; case 41: return "UnaryMinus"; case 44: return "If"; case 54: return "GetStructField"; case 56: return "ListExtract";
-    case 45: return "NormalizeNaNAndZero"; case 47: return "TruncTimestamp"; case 50: return "Subquery"; case 65: return "UnixTimestamp"; default: return "Expr";
+    case 45: return "NormalizeNaNAndZero"; case 47: return "TruncTimestamp"; case 50: return "Subquery"; case 52: return "might_contain"; case 65: return "UnixTimestamp"; default: return "Expr";
   }
 }
 

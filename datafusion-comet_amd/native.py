@@ -1358,3 +1358,32 @@ def parquet_prune_report(plan: bytes, page_index: bool = True, bloom_filters: bo
     if n < 0:
         _raise_last(0)
     return json.loads(buf.value.decode())
+
+
+def spark_bloom_might_contain(filter_bytes: bytes, value: int) -> Optional[bool]:
+    """might_contain(filter, value) by the device's code on the host (comet_spark_bloom_might_contain): None for bytes the executor would refuse"""
+    f = lib().comet_spark_bloom_might_contain
+    f.restype = ctypes.c_int32
+    f.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64]
+    rc = f(filter_bytes, len(filter_bytes), value)
+    return None if rc < 0 else bool(rc)
+
+
+def spark_bloom_build(values, num_items: int, num_bits: int, version: int = 0) -> Optional[bytes]:
+    """bloom_filter_agg's Partial state over `values` (ints, None = NULL) by the device's code on the host (comet_spark_bloom_build): None for parameters
+    the planner refuses"""
+    import numpy as np
+    vals = np.array([0 if v is None else v for v in values], dtype=np.int64)
+    n = len(vals)
+    valid = np.packbits(np.array([v is not None for v in values], dtype=np.uint8), bitorder="little") if any(v is None for v in values) else None
+    f = lib().comet_spark_bloom_build
+    f.restype = ctypes.c_int64
+    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]
+    vp = vals.ctypes.data if n else None
+    bp = valid.ctypes.data if valid is not None else None
+    need = f(vp, bp, n, num_items, num_bits, version, None, 0)
+    if need < 0:
+        return None
+    out = ctypes.create_string_buffer(need)
+    f(vp, bp, n, num_items, num_bits, version, ctypes.cast(out, ctypes.c_void_p), need)
+    return out.raw

@@ -135,6 +135,7 @@ def decimal(p: int, s: int) -> DataType:
 
 T_BOOL, T_INT8, T_INT16, T_INT32, T_INT64 = (DataType(t) for t in (BOOL, INT8, INT16, INT32, INT64))
 T_FLOAT, T_DOUBLE, T_STRING, T_DATE, T_TIMESTAMP = (DataType(t) for t in (FLOAT, DOUBLE, STRING, DATE, TIMESTAMP))
+T_BINARY = DataType(BYTES)
 
 LEGACY, TRY, ANSI = 0, 1, 2
 
@@ -183,7 +184,7 @@ class Expr:
     TAGS = dict(subquery=50, list_extract=56, trunc_timestamp=47, unix_timestamp=65, hour=22, minute=23, second=24, literal=2, bound=3, add=4, subtract=5, multiply=6, divide=7, cast=8, eq=9, neq=10, gt=11, gt_eq=12,
                 lt=13, lt_eq=14, is_null=15, is_not_null=16, and_=17, or_=18, check_overflow=25, like=26, rlike=30, scalar_func=31, eq_null_safe=32,
                 neq_null_safe=33, bit_and=34, bit_or=35, bit_xor=36, shift_right=42, shift_left=43, integral_divide=59, remainder=37, case_when=38, in_=39, not_=40, unary_minus=41, if_=44, normalize_nan_and_zero=45,
-                unbound=51, get_struct_field=54)
+                unbound=51, get_struct_field=54, bloom_filter_might_contain=52)
 
     def encode(self) -> bytes:
         k = self.kind
@@ -384,6 +385,12 @@ def subquery(sub_id: int, dtype: DataType) -> Expr:
     return Expr("subquery", [], dtype=dtype, value=sub_id)
 
 
+def bloom_filter_might_contain(bloom_filter: Expr, value: Expr) -> Expr:
+    """might_contain(filter, value) (BloomFilterMightContain{bloom_filter = 1, value = 2}, expr.proto:518-521): the filter a Binary literal or a Binary scalar
+    subquery (Spark's InjectRuntimeFilter sends ScalarSubquery(bloom_filter_agg …)), the value an Int64 expression (xxhash64(key))"""
+    return Expr("bloom_filter_might_contain", [bloom_filter, value])
+
+
 def list_extract(child: Expr, ordinal: Expr, one_based: bool = False, fail_on_error: bool = False, default: Optional[Expr] = None) -> Expr:
     """GetArrayItem (arr[i], from 0) / ElementAt on an array (element_at(arr, i), from 1, negative from the end) — expr.proto:533-539"""
     e = Expr("list_extract", [child, ordinal] + ([default] if default is not None else []), fail_on_error=fail_on_error)
@@ -461,10 +468,10 @@ class AggExpr:
     eval_mode: int = LEGACY
     filter: Optional[Expr] = None
     ignore_nulls: bool = False      # first | last
-    stats_type: int = 0             # variance | stddev | covariance: SAMPLE (0) or POPULATION (1)
+    stats_type: int = 0             # variance | stddev | covariance: SAMPLE (0) or POPULATION (1); bloom_filter: BloomFilterVersion
     null_on_divide_by_zero: bool = True      # variance | stddev | covariance | corr
 
-    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, bit_and=9, bit_or=10, bit_xor=11, covariance=12, variance=13, stddev=14, corr=15)
+    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, bit_and=9, bit_or=10, bit_xor=11, covariance=12, variance=13, stddev=14, corr=15, bloom_filter=16)
 
     def encode(self) -> bytes:
         if self.kind == "count":
@@ -489,6 +496,10 @@ class AggExpr:
             body = (_f_msg(1, self.children[0].encode()) + _f_msg(2, self.children[1].encode()) + (_f_varint(3, 1) if self.null_on_divide_by_zero else b"") +
                     _f_msg(4, self.dtype.encode()))
             if self.kind == "covariance" and self.stats_type:
+                body += _f_varint(5, self.stats_type)
+        elif self.kind == "bloom_filter":      # BloomFilterAgg{child=1, numItems=2, numBits=3, datatype=4, version=5} (expr.proto:289-305); children = [child, numItems, numBits]
+            body = b"".join(_f_msg(i + 1, c.encode()) for i, c in enumerate(self.children)) + _f_msg(4, self.dtype.encode())
+            if self.stats_type:
                 body += _f_varint(5, self.stats_type)
         else:
             raise ValueError(self.kind)
@@ -537,6 +548,11 @@ def bit_or_agg(child: Expr, dtype: DataType, filter: Optional[Expr] = None) -> A
 
 def bit_xor_agg(child: Expr, dtype: DataType, filter: Optional[Expr] = None) -> AggExpr:
     return AggExpr("bit_xor", [child], dtype=dtype, filter=filter)
+
+
+def bloom_filter_agg(child: Expr, num_items: int, num_bits: int, version: int = 0, filter: Optional[Expr] = None) -> AggExpr:
+    """bloom_filter_agg(child, numItems, numBits): the two sizes travel as Int64 literals; version: BloomFilterVersion 0 unspecified (V1), 1 V1, 2 V2 (Spark 4.1+)"""
+    return AggExpr("bloom_filter", [child, lit(num_items, T_INT64), lit(num_bits, T_INT64)], dtype=T_BINARY, stats_type=version, filter=filter)
 
 
 SAMPLE, POPULATION = 0, 1      # StatisticsType (expr.proto:178-181)

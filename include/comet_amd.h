@@ -230,6 +230,14 @@ int64_t comet_error_site_json(uint32_t site_id, uint64_t lo, uint64_t hi, const 
 int comet_calib_read(const void* buf, int64_t bytes, int32_t width, uint64_t* sink, void* stream);
 /* the headline's Utf8 pass on its own (kernels_static.hip utf8_uniform_kernel): *flag becomes non-zero unless every value of the n offsets has length L */
 int comet_launch_utf8_uniform(const int32_t* offsets, int64_t n, int32_t L, uint32_t* flag, void* stream);
+/* Spark's BloomFilter over longs (csrc/device/bloom.hpp: the code the kernels run) on the host — diagnostic entries, no GPU.
+ * comet_spark_bloom_might_contain: `bytes` is a serialized filter (V1: i32 1 | numHashFunctions | numWords | words, V2: i32 2 | numHashFunctions | seed | numWords | words,
+ * all big-endian) → 1 / 0, or -1 for bytes the executor would refuse (unknown version, numHashFunctions outside 1 … 255, no words, 2^31 bits or more, truncated, empty).
+ * comet_spark_bloom_build: bloom_filter_agg's Partial state over n longs (valid: Arrow validity bitmap or NULL; NULL rows are skipped) with the aggregate's own
+ * rule for numHashFunctions and numWords (version 0 / 1: V1, 2: V2): the serialization's length, its bytes written when they fit `cap`; -1 for parameters the
+ * planner refuses. */
+int32_t comet_spark_bloom_might_contain(const uint8_t* bytes, size_t len, int64_t value);
+int64_t comet_spark_bloom_build(const int64_t* values, const uint8_t* valid, int64_t n, int64_t num_items, int64_t num_bits, int32_t version, uint8_t* out, int64_t cap);
 #endif /* COMET_TEST_ABI */
 
 /* ---- scalar subqueries (expr.proto:513-516 Subquery{id, datatype}; native/core/src/execution/expressions/subquery.rs:72-180) ------------------------------

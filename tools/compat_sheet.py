@@ -135,6 +135,8 @@ def probes():
         "Md5": (f("md5", [S.cast(s, S.DataType(S.BYTES))], S.T_STRING), "of a Utf8 column (under Cast AS BINARY too); derived column"), "Sha1": (f("sha1", [S.cast(s, S.DataType(S.BYTES))], S.T_STRING), ""),
         "Sha2": (f("sha2", [S.cast(s, S.DataType(S.BYTES)), L(256, S.T_INT32)], S.T_STRING), "224 / 256 / 0 / 384 / 512"), "Crc32": (f("crc32", [S.cast(s, S.DataType(S.BYTES))], S.T_INT64), ""),
         "StringInstr": (f("instr", [s, L("b", S.T_STRING)], S.T_INT32), "literal substring"), "Ascii": (f("ascii", [s], S.T_INT32), ""),
+        "BloomFilterMightContain": (S.bloom_filter_might_contain(S.subquery(2, S.T_BINARY), f("xxhash64", [i64, L(42, S.T_INT64)], S.T_INT64)),
+                                    "might_contain(filter, value) with a Binary literal or a Binary scalar subquery as the filter and an Int64 value: Spark's V1 and V2 filters; the filter is a buffer bound at launch (checked on the host first), so tasks with different filters share their kernels; at most four probes per fused chain"),
         "ScalarSubquery": (S.subquery(1, S.T_INT64), "Subquery{id, datatype}: the value is asked of CometScalarSubquery's static methods (or comet_plan_set_subquery) at the first executePlan and becomes a literal of the kernels"),
         "StringSplit": (f("split", [s, L(",", S.T_STRING), L(-1, S.T_INT32)], S.list_type(S.T_STRING, False)),
                         "under spark.comet.expression.StringSplit.allowIncompatible: of a Utf8 COLUMN with a literal pattern and limit, computed over the chain's source and passed through / exploded; the matcher's pattern subset"),
@@ -190,7 +192,8 @@ ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64
                        "VarianceSamp": "Float64, not over window frames (exact moments, order independent)", "VariancePop": "Float64, not over window frames (exact moments, order independent)",
                        "StddevSamp": "Float64, not over window frames (exact moments, order independent)", "StddevPop": "Float64, not over window frames (exact moments, order independent)",
                        "CovSample": "Float64, not over window frames (exact moments, order independent)", "CovPopulation": "Float64, not over window frames (exact moments, order independent)",
-                       "Corr": "Float64, not over window frames (exact moments, order independent)"}
+                       "Corr": "Float64, not over window frames (exact moments, order independent)",
+                       "BloomFilterAggregate": "Byte / Short / Int / Long child, without grouping keys and alone in its HashAggregate (the shape InjectRuntimeFilter plans), Partial / PartialMerge / Final, V1 and V2"}
 
 
 def probe_plan(expr):
@@ -269,6 +272,13 @@ def render() -> str:
     w("  signs beyond its precision does).  Over window frames an ANSI / TRY integer sum is refused at `createPlan` (the frame sums wrap like LEGACY's).")
     w("* `First` / `Last` of Utf8, Binary and nested values in a HashAggregate (their state is fixed-width; over window frames any flat type runs); `BitAndAgg` /")
     w("  `BitOrAgg` / `BitXorAgg` over anything but Byte / Short / Int / Long, and over window frames.")
+    w("* `BloomFilterAggregate`: grouped, mixed with other aggregate functions, or with a FILTER clause; a Utf8 child (the reference accepts it, but `might_contain` probes")
+    w("  longs only, so such a filter could not be used natively); numItems <= 0, numBits <= 0, numBits that round up to 2^31 bits or more; more than 255 hash functions")
+    w("  (numBits / numItems * ln 2 — the cap bounds a kernel's per-row loop, Spark has none).  A merging aggregate fails the task with the reference's messages when a state")
+    w("  does not match (`BloomFilter merge: version mismatch`, `num_hash_functions mismatch`, `seed mismatch`, `num_words mismatch`, `truncated bit array`).")
+    w("* `BloomFilterMightContain`: a filter argument that is neither a Binary literal nor a Binary scalar subquery, a value that is not Int64, more than four probes in one")
+    w("  fused chain, no kernel-argument slot left beside 24 columns; filter bytes with an unknown version, numHashFunctions outside 1 … 255, no words, 2^31 bits or more, or")
+    w("  shorter than their header says fail by name (a literal at `createPlan`, a subquery's value at the first `executePlan`, before anything is launched).")
     w("* `RLike`: patterns outside the byte-exact subset (`\\\\p{..}`, scoped flags, look-around, `\\\\b` under `(?m)`) are refused by name.")
     w("* `Concat`: of Utf8 columns and literals (at most eight), as an output column.")
     w("* Computed Utf8 values used as operands of further expressions must fit 15 bytes (literals, substring, CASE over those).")
