@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "kparams.h"
 #include "plan.hpp"
 
 namespace comet {
@@ -107,6 +108,9 @@ struct PipelineDesc {
 };
 constexpr int kFixScaleArg = 6;      // scales of sums 0-3, 16 bits each
 constexpr int kFixScaleArg2 = 4;     // … of sums 4-7 (round 6: eight exact Float64 sums / averages per aggregate)
+constexpr int kGuardArg = 1;         // k_gagg: the Utf8 columns whose predicted length every block checks against the end points first (comet_device.hpp utf8_guard_ok), 0 = none
+constexpr int kGuardMaxCols = 6;     // (three bits of count, nine bits per column: input column and length)
+constexpr uint32_t kErrGuardBit = 1u << 30;   // … the bit a failed guard raises in the error word (comet::kErrUtf8Guard)
 constexpr int kRowBaseArg = 3;       // aggregate sinks: rows the task's aggregate consumed before this chunk (the ordinals of first / last count from it)
 constexpr int kFixMaxSums = 8;
 constexpr int kFixW = 158;            // must equal comet::kFixW
@@ -148,6 +152,7 @@ constexpr int kOutPartials = 0;      // AggNoGroup: partials;  Output: mask word
 constexpr int kOutCounts = 1;        // Output: tile counts / offsets
 constexpr int kOutErr = 2;           // u32[4] error flags (ANSI overflow etc.)
 constexpr int kErrBytes = 512;       // error/aux block (kparams.h COMET_ERR_BYTES): flags, group counter, aux words, error detail, scratch
+constexpr int kUtf8RecBytes = COMET_UTF8_MAX_COLS * COMET_UTF8_REC_WORDS * 4;   // utf8_uniform_kernel's records, behind the error block in the same allocation
 constexpr int kErrAuxWords = 22;     // (COMET_ERR_AUX_WORDS)
 constexpr int kErrDetailWord = 24;   // (COMET_ERR_DETAIL_WORD)
 constexpr int kErrDetailStrBytes = 224;

@@ -2373,11 +2373,36 @@ CDEV void group_update(const GroupCtx<P>& g, bool active, const u64* key, const 
   if (!fresh) slot_apply<P, __HIP_MEMORY_SCOPE_AGENT>(&s->acc[0], val);
 }
 
-// Kernel template C body.  prm.out[0] = global table, prm.iarg[0] = its capacity, prm.out[2] = err/aux words.
+// A launch on PREDICTED Utf8 lengths (the executor has not read the columns' offsets yet; its check runs beside this kernel): ld_str_fixed addresses
+// aux + (offset + i)·L without looking at an offset, so before its first tile every workgroup makes sure that the end points of each such column say the
+// same — first offset = offset·L, last − first = L·n.  Then every aux[first + i], i < n·L, lies inside the range the column's own offsets span, whatever
+// the offsets in between turn out to be (the check decides whether the pass COUNTS).  `guard` (prm.iarg[kGuardArg]): bits [0, 3) = number of columns, then
+// nine bits per column: input column (5 bits), L (4 bits).  Two scalar-rate loads per column and workgroup; nothing per row.
+constexpr int kGuardArg = 1;
+constexpr unsigned int kErrUtf8Guard = 1u << 30;
+CDEV bool utf8_guard_ok(const CometKParams& prm, u64 guard) {
+  const int cnt = (int)(guard & 7);
+  bool ok = true;
+  for (int k = 0; k < cnt; k++) {
+    const u32 f = (u32)(guard >> (3 + 9 * k)) & 511u;
+    const CometCol& col = prm.in[f & 31u];
+    const i64 L = (i64)(f >> 5);
+    const COMET_GLOBAL i32* off = (const COMET_GLOBAL i32*)col.data + col.offset;
+    const i64 first = off[0], last = off[prm.n];
+    ok = ok && first == col.offset * L && last - first == L * prm.n;
+  }
+  return ok;
+}
+
+// Kernel template C body.  prm.out[0] = global table, prm.iarg[0] = its capacity, prm.out[2] = err/aux words, prm.iarg[kGuardArg] = guarded Utf8 columns.
 template <class P>
 CDEV void agg_grouped_body(const CometKParams& prm) {
   typedef Slot<P::NK, P::NW> S;
   typedef LSlot<P::NK, P::NPW> LS;
+  if (prm.iarg[kGuardArg] != 0 && !utf8_guard_ok(prm, (u64)prm.iarg[kGuardArg])) {      // (uniform over the launch: every workgroup leaves, nothing is touched)
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr((unsigned int*)prm.out[2], kErrUtf8Guard);
+    return;
+  }
   __shared__ LS s_tbl[P::LDS_CAP > 0 ? P::LDS_CAP : 1];
   __shared__ u64 s_priv[P::GC * P::NPW * P::COPIES];
   __shared__ u32 s_count;

@@ -907,6 +907,12 @@ ExecutionContext::~ExecutionContext() {
     (void)hipStreamSynchronize(stream_);  // pooled buffers go back only once the stream is idle
     for (auto& pr : timed_) { pool_put_event(device_id_, pr.first); pool_put_event(device_id_, pr.second); }
     for (hipEvent_t& e : aux_ev_) if (e) { pool_put_event(device_id_, e); e = nullptr; }
+    if (check_stream_) {
+      (void)hipStreamSynchronize(check_stream_);
+      pool_put_stream(device_id_, check_stream_);
+      check_stream_ = nullptr;
+    }
+    if (check_fork_ev_) { pool_put_event(device_id_, check_fork_ev_); check_fork_ev_ = nullptr; }
     for (auto& p : kt_pending_) { pool_put_event(device_id_, p.a); pool_put_event(device_id_, p.b); }
     kt_pending_.clear();
     pool_put_stream(device_id_, stream_);
@@ -1628,7 +1634,8 @@ DevTable ExecutionContext::materialize(const Operator& op) {
     } else {
       std::shared_ptr<void> keep;
       int64_t rows = 0;
-      if (pull_device_table(input, op.scan_fields, t.cols, t.has_valid, rows, keep)) {
+      // (the root Scan of a grouped aggregate: its batch may launch on predicted Utf8 lengths, run_to_completion)
+      if (pull_device_table(input, op.scan_fields, t.cols, t.has_valid, rows, keep, &op == root_source_ ? &root_spec_ : nullptr)) {
         t.rows = rows;
         t.owners.push_back(keep);
         std::vector<DeviceColumnView> c2;
@@ -1980,7 +1987,13 @@ void ExecutionContext::run_to_completion() {
     if (plan_.get() == root_source_) throw CometError("internal: bare join root");
     if (sink_ == SinkKind::AggGrouped) prepare_dict_keys(src);
     single_chunk_hint_ = true;      // (the join's output is the aggregate's whole input)
-    process_chunk(src.cols, src.has_valid, src.rows);
+    process_chunk(src.cols, src.has_valid, src.rows, &root_spec_);
+    if (root_spec_.voided) {        // launched on a predicted Utf8 length that the check did not confirm: again, from the key measurement on, with what the check found
+      root_spec_.apply_checked(src.cols);
+      root_spec_.voided = false;
+      if (sink_ == SinkKind::AggGrouped) prepare_dict_keys(src);
+      process_chunk(src.cols, src.has_valid, src.rows);
+    }
     HIP_CHECK(hipStreamSynchronize(stream_));
     return;
   }
@@ -1996,7 +2009,7 @@ void ExecutionContext::start() {
     // Lazy start like the reference (jni_api.rs:795-872): nothing touches the input before the first executePlan.
     HIP_CHECK(hipSetDevice(device_id_));
     stream_ = pool_get_stream(device_id_);
-    err_flags_.ensure(kErrBytes);
+    err_flags_.ensure(kErrBytes + kUtf8RecBytes);      // (the Utf8 check's records sit behind the error block)
     HIP_CHECK(hipMemsetAsync(err_flags_.p, 0, kErrBytes, stream_));
     started_ = true;
   } else {

@@ -114,6 +114,18 @@ struct DeviceColumnView {
 };
 
 // a table resident in HBM (Arrow layout); owners keep pooled buffers / producer arrays alive
+// A device batch whose Utf8 lengths were PREDICTED (utf8_memo.hpp) instead of verified before its kernel is chosen: the check is still owed,
+// and the chunk's kernel launches guarded (exec_pipeline.cpp process_chunk).  Belongs to the pulled batch, not to the context: batches are pulled one ahead.
+struct Utf8Pending {
+  bool active = false;
+  bool voided = false;                // process_chunk: nothing of the chunk counts — run it again with views[col[k]].fixed_len = checked_len[k], as a checked chunk
+  std::vector<int> checked_len;
+  void apply_checked(std::vector<DeviceColumnView>& views) const;
+  size_t input = 0;
+  std::vector<size_t> col;            // the predicted columns …
+  std::vector<CometUtf8Check> chk;    // … as the check launch reads them (expect = the predicted length)
+};
+
 struct DevTable {
   int64_t rows = 0;
   std::vector<DType> types;
@@ -207,7 +219,7 @@ class ExecutionContext {
   void start();
   std::vector<std::vector<int>> fixed_len_hint_;   // per device input, per column: producer-asserted uniform Utf8 length, -1 = none
   Variant& variant_for(const std::vector<bool>& has_valid, const std::vector<int>& str_fixed_len);
-  void process_chunk(const std::vector<DeviceColumnView>& cols, const std::vector<bool>& has_valid, int64_t n);
+  void process_chunk(const std::vector<DeviceColumnView>& cols, const std::vector<bool>& has_valid, int64_t n, Utf8Pending* spec = nullptr);
   void finish_aggregate();
   void finish_grouped();
   DevTable grouped_to_device();
@@ -258,7 +270,12 @@ class ExecutionContext {
   bool pull_host_table(size_t input, const std::vector<DType>& types, int64_t max_rows, std::vector<DeviceColumnView>& views,
                        std::vector<bool>& has_valid, int64_t& rows);
   bool pull_device_table(size_t input, const std::vector<DType>& types, std::vector<DeviceColumnView>& views, std::vector<bool>& has_valid,
-                         int64_t& rows, std::shared_ptr<void>& keepalive);
+                         int64_t& rows, std::shared_ptr<void>& keepalive, Utf8Pending* spec = nullptr);
+  // Utf8 length verification of a device batch (exec_input.cpp): check first, then choose the kernel
+  void verify_utf8_lengths(size_t input, int64_t rows, const std::vector<size_t>& scols, std::vector<CometUtf8Check>& chk, std::vector<DeviceColumnView>& views);
+  void run_utf8_check(const CometUtf8Check* cols, int n, uint32_t* rec);
+  uint32_t* utf8_records() { return (uint32_t*)((char*)err_flags_.p + kErrBytes); }      // the check's records sit behind the error block: one read-back brings both
+  void launch_utf8_check_beside(const Utf8Pending& spec);
   void validate_input_schema(size_t input, const std::vector<DType>& types);
   void export_batch(HostBatch& b, ArrowArray** out_arrays, ArrowSchema** out_schemas, int n_out);
   void check_device_errors();
@@ -311,8 +328,7 @@ class ExecutionContext {
   struct KtPending { std::string name; hipEvent_t a, b; };
   std::vector<KtPending> kt_pending_;                        // COMET_KERNEL_TIMES=1: one event pair per generated-kernel launch
   std::map<std::string, std::pair<double, int64_t>> kernel_times_;
-  hipEvent_t aux_ev_[2] = {nullptr, nullptr};              // (start, stop) around pull_device_table's verification launches; aux_n_ of them
-  int aux_n_ = 0;
+  hipEvent_t aux_ev_[2] = {nullptr, nullptr};              // (start, stop) around pull_device_table's verification launch
   bool started_ = false, finished_ = false;
   std::vector<DType> in_types_;
   std::map<std::string, Variant> variants_;
@@ -373,8 +389,12 @@ class ExecutionContext {
     int64_t rows = 0;
     std::shared_ptr<void> keep;
     bool valid = false;
+    Utf8Pending spec;
   };
   DevPending dev_pending_;
+  Utf8Pending root_spec_;           // … and of the single batch a grouped aggregate over Utf8 keys takes whole (run_to_completion)
+  // plans whose device batches may launch on a predicted length: a grouped aggregate straight over its Scan (a real join's inputs are checked first)
+  bool utf8_predictable_plan() const { return sink_ == SinkKind::AggGrouped && (!has_join_ || (root_source_ && root_source_->kind == OpKind::Scan)); }
   bool dev_stream_done_ = false;
   int64_t dev_chunks_seen_ = 0;
   int64_t bytes_scanned_ = 0;
@@ -404,6 +424,9 @@ class ExecutionContext {
   long long packed_fix_scales(const PipelineDesc& d, int first = 0);
   bool adjust_fix_scales(const PipelineDesc& d, const uint64_t* aux, std::vector<int>& shift_right);
   DevBuf err_flags_;
+  DevBuf err_snapshot_;    // the error block as it was before a speculative pass (restored when the pass is voided)
+  hipStream_t check_stream_ = nullptr;   // a speculative batch's check runs here, beside k_gagg
+  hipEvent_t check_fork_ev_ = nullptr;   // … behind this event of the plan's stream (so the producer's sync_event orders it too)
   PinnedBuf result_host_;
   PinnedBuf small_host_;   // 4 KiB pinned scratch for flag / count read-backs
   PinnedBuf export_host_;  // a small result's buffers land here side by side (one copy kernel instead of a hipMemcpy per buffer)

@@ -1,5 +1,6 @@
 // Plan inputs: host ArrowArrayStreams staged through pinned memory (casts, dictionaries, Utf8 rebasing), device streams consumed in place.
 #include "exec_internal.hpp"
+#include "utf8_memo.hpp"
 #include <emmintrin.h>
 #include <mutex>
 #include <set>
@@ -561,15 +562,42 @@ bool uniform_verdict_known(const void* off, int64_t rows, int32_t len, int32_t f
   std::lock_guard<std::mutex> g(g_uniform_mu);
   return g_uniform_ok.count(UniformKey{off, rows, len, first}) != 0;
 }
+// … is anything remembered about these offsets at this length, whatever the first offset was?  (the first offset is only known once the launch is back)
+bool uniform_verdict_seen(const void* off, int64_t rows, int32_t len) {
+  std::lock_guard<std::mutex> g(g_uniform_mu);
+  auto it = g_uniform_ok.lower_bound(UniformKey{off, rows, len, INT32_MIN});
+  return it != g_uniform_ok.end() && it->off == off && it->rows == rows && it->len == len;
+}
 void remember_uniform_verdict(const void* off, int64_t rows, int32_t len, int32_t first) {
   std::lock_guard<std::mutex> g(g_uniform_mu);
   if (g_uniform_ok.size() >= 4096) g_uniform_ok.clear();
   g_uniform_ok.insert(UniformKey{off, rows, len, first});
 }
+Utf8LengthMemo g_utf8_memo;
 }  // namespace
 
+// Experiment switches (read once).  COMET_UTF8_SPECULATE=0: never launch on a predicted length — every batch is checked first.
+// COMET_UTF8_CHECK_STREAM=1: a speculative batch's check runs on a second stream beside k_gagg instead of in front of it on the plan's stream.
+// COMET_UTF8_CHECK_BLOCKS_PER_CU: workgroups per CU of that co-running check (k_gagg leaves 4 of 8 wave slots per SIMD, its registers two of them to this kernel).
+bool utf8_speculate() {
+  static const bool on = !(getenv("COMET_UTF8_SPECULATE") && atoi(getenv("COMET_UTF8_SPECULATE")) == 0);
+  return on;
+}
+bool utf8_check_stream() {
+  static const bool on = getenv("COMET_UTF8_CHECK_STREAM") ? atoi(getenv("COMET_UTF8_CHECK_STREAM")) != 0 : kUtf8CheckStreamDefault;
+  return on;
+}
+int utf8_check_blocks() {
+  static const int per_cu = getenv("COMET_UTF8_CHECK_BLOCKS_PER_CU") ? std::max(1, std::min(8, atoi(getenv("COMET_UTF8_CHECK_BLOCKS_PER_CU")))) : kUtf8CheckBlocksPerCuDefault;
+  return 256 * per_cu;
+}
+void Utf8Pending::apply_checked(std::vector<DeviceColumnView>& views) const {
+  for (size_t k = 0; k < col.size() && k < checked_len.size(); k++) views[col[k]].fixed_len = checked_len[k];
+}
+void utf8_memo_forget(uint64_t plan_hash, size_t input, size_t column) { g_utf8_memo.forget(plan_hash, input, column); }
+
 bool ExecutionContext::pull_device_table(size_t input, const std::vector<DType>& types, std::vector<DeviceColumnView>& views,
-                                         std::vector<bool>& has_valid, int64_t& rows, std::shared_ptr<void>& keepalive) {
+                                         std::vector<bool>& has_valid, int64_t& rows, std::shared_ptr<void>& keepalive, Utf8Pending* spec) {
   InputSource& in = inputs_[input];
   rows = 0;
   if (in.exhausted) return false;
@@ -615,88 +643,132 @@ bool ExecutionContext::pull_device_table(size_t input, const std::vector<DType>&
   }
   rows = da->array.length;
   // Utf8 columns: check on the device whether all values share one length (one pass over the offsets, 4 B/row); if so the fused
-  // kernels skip the offsets and the dependent byte load altogether.  All columns at once: the first / last offsets of every column
-  // come back with ONE synchronisation, the verification launches run back to back, their flags come back with a second one.
+  // kernels skip the offsets and the dependent byte load altogether.
   std::vector<size_t> scols;
   for (size_t c = 0; c < nc && rows > 0; c++)
     if (types[c].id == TypeId::String) scols.push_back(c);
-  if (!scols.empty() && scols.size() <= 16) {
-    small_host_.ensure(4096);
-    int32_t* ends = (int32_t*)small_host_.p;                 // [2 k], [2 k + 1] = first / last offset of string column k
+  if (!scols.empty() && scols.size() <= COMET_UTF8_MAX_COLS) {
+    std::vector<CometUtf8Check> chk(scols.size());
+    bool predictable = spec != nullptr && utf8_speculate() && utf8_predictable_plan() && scols.size() <= (size_t)kGuardMaxCols;
     for (size_t k = 0; k < scols.size(); k++) {
       const ArrowArray* col = da->array.children[scols[k]];
-      const int32_t* off = (const int32_t*)col->buffers[1] + col->offset;
-      HIP_CHECK(hipMemcpyAsync(ends + 2 * k, off, 4, hipMemcpyDeviceToHost, stream_));
-      HIP_CHECK(hipMemcpyAsync(ends + 2 * k + 1, off + rows, 4, hipMemcpyDeviceToHost, stream_));
-    }
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    std::vector<int32_t> first(scols.size()), len(scols.size(), -1);
-    std::vector<bool> declared(scols.size(), false);
-    uint32_t* flags = (uint32_t*)err_flags_.p + (kErrBytes / 4 - 16);   // last 16 words of the error/aux block: scratch
-    HIP_CHECK(hipMemsetAsync(flags, 0, 64, stream_));
-    bool any = false;
-    if (!aux_ev_[0]) { aux_ev_[0] = pool_get_event(device_id_); aux_ev_[1] = pool_get_event(device_id_); }
-    HIP_CHECK(hipEventRecord(aux_ev_[0], stream_));
-    int aux_launched = 0;
-    for (size_t k = 0; k < scols.size(); k++) {
-      first[k] = ends[2 * k];
-      const int64_t total = (int64_t)ends[2 * k + 1] - ends[2 * k];
       const int hint = input < fixed_len_hint_.size() && scols[k] < fixed_len_hint_[input].size() ? fixed_len_hint_[input][scols[k]] : -1;
-      const ArrowArray* col = da->array.children[scols[k]];
-      const int32_t* off = (const int32_t*)col->buffers[1] + col->offset;
-      if (hint >= 0) {
-        // A declaration is a promise about an IMMUTABLE buffer, and it is still verified: the end points on every batch, every offset in
-        // between by utf8_uniform_kernel the first time this (offsets address, rows, length) is seen in the process — the verdict is
-        // remembered, so the tasks after the first pay nothing.  A batch that contradicts the declaration is refused, never mis-read.
-        if (total != (int64_t)hint * rows)
-          throw CometError("device input column " + std::to_string(scols[k]) + " is declared comet:utf8_fixed_len=" + std::to_string(hint) + " but holds " +
-                           std::to_string(total) + " bytes in " + std::to_string(rows) + " rows");
-        if ((int64_t)first[k] != (int64_t)col->offset * hint) continue;      // a sliced column: offset-based accessors only
-        if (uniform_verdict_known(off, rows, hint, first[k])) {
-          views[scols[k]].fixed_len = hint;
-          continue;
-        }
-        if (comet_launch_utf8_uniform(off, rows, hint, flags + k, stream_) != 0) continue;
-        aux_launched++;
-        len[k] = hint;
-        declared[k] = true;
-        any = true;
-        continue;
-      }
-      if (total % rows != 0 || total / rows > 15 || total < 0) continue;
-      if (comet_launch_utf8_uniform(off, rows, (int32_t)(total / rows), flags + k, stream_) != 0) continue;
-      aux_launched++;
-      len[k] = (int32_t)(total / rows);
-      any = true;
+      chk[k].offsets = (const int*)col->buffers[1];
+      chk[k].rows = rows;
+      chk[k].col_offset = col->offset;
+      chk[k].expect = hint;
+      chk[k].ends_only = 0;
+      int guess = -1;
+      predictable = predictable && hint < 0 && col->offset == 0 && g_utf8_memo.get(plan_hash_, input, scols[k], guess);
+      if (predictable) chk[k].expect = guess;
     }
-    if (any) {
-      HIP_CHECK(hipEventRecord(aux_ev_[1], stream_));
-      uint32_t f[16];
-      read_small(f, flags, 64);      // (synchronises the stream: the event pair is complete)
-      float aux = 0;
-      if (hipEventElapsedTime(&aux, aux_ev_[0], aux_ev_[1]) == hipSuccess) { last_aux_ms += aux; last_aux_launches += aux_launched; }
-      HIP_CHECK(hipMemsetAsync(flags, 0, 64, stream_));
-      for (size_t k = 0; k < scols.size(); k++) {
-        if (len[k] < 0) continue;
-        const size_t c = scols[k];
-        const ArrowArray* col = da->array.children[c];
-        if (declared[k]) {
-          if (f[k] != 0)
-            throw CometError("device input column " + std::to_string(c) + " is declared comet:utf8_fixed_len=" + std::to_string(len[k]) +
-                             " but its offsets are not " + std::to_string(len[k]) + " bytes apart (the byte total alone matches)");
-          remember_uniform_verdict((const int32_t*)col->buffers[1] + col->offset, rows, len[k], first[k]);
-          views[c].fixed_len = len[k];
-          continue;
-        }
-        if (f[k] != 0) continue;
-        // value i then sits at aux + (offset + i)·len.  Only claimed when that base IS the data buffer (an unsliced column), because the
-        // offset-based accessors (substring, LIKE, views …) of the same kernels keep addressing aux + offsets[i]
-        if ((int64_t)first[k] != (int64_t)col->offset * len[k]) continue;
-        views[c].fixed_len = len[k];
-      }
+    if (predictable) {
+      // Every column's length was verified by an earlier task of this plan: take it as a GUESS about which variant to launch, and leave the
+      // host alone — the chunk's kernel launches guarded and the check runs beside it (exec_pipeline.cpp process_chunk), every offset is
+      // still verified before the chunk's result counts.
+      spec->active = true;
+      spec->input = input;
+      spec->col = scols;
+      spec->chk = chk;
+      for (size_t k = 0; k < scols.size(); k++) views[scols[k]].fixed_len = chk[k].expect;
+      return true;
     }
+    for (size_t k = 0; k < scols.size(); k++) chk[k].expect = input < fixed_len_hint_.size() && scols[k] < fixed_len_hint_[input].size() ? fixed_len_hint_[input][scols[k]] : -1;
+    verify_utf8_lengths(input, rows, scols, chk, views);
   }
   return true;
+}
+
+// Check first, then choose the kernel: ONE launch covers every column and reads the end points itself, ONE read-back brings flags and end
+// points together (utf8_uniform_kernel's records).  chk[k] describes column scols[k]; views[…].fixed_len is set where the check allows.
+void ExecutionContext::verify_utf8_lengths(size_t input, int64_t rows, const std::vector<size_t>& scols, std::vector<CometUtf8Check>& chk,
+                                           std::vector<DeviceColumnView>& views) {
+  const bool memo = utf8_predictable_plan();      // (where a prediction would be used)
+  std::vector<int> round(scols.size(), 0);                // the launch a column's record comes from; -1 = settled
+  for (size_t k = 0; k < scols.size(); k++) {
+    views[scols[k]].fixed_len = -1;
+    // A declaration is a promise about an IMMUTABLE buffer, and it is still verified: the end points on every batch, every offset in
+    // between the first time this (offsets address, rows, length, first offset) is seen in the process — the verdict is remembered, so
+    // the tasks after the first read the end points only.  A batch that contradicts the declaration is refused, never mis-read.
+    chk[k].ends_only = chk[k].expect >= 0 && uniform_verdict_seen((const int32_t*)chk[k].offsets + chk[k].col_offset, rows, chk[k].expect) ? 1 : 0;
+  }
+  // (a second launch only when a remembered verdict turns out to be about another first offset: those columns are then read in full)
+  for (int r = 0; r < 2; r++) {
+    std::vector<CometUtf8Check> now;
+    std::vector<size_t> who;
+    for (size_t k = 0; k < scols.size(); k++)
+      if (round[k] == r) { now.push_back(chk[k]); who.push_back(k); }
+    if (now.empty()) break;
+    uint32_t rec[COMET_UTF8_MAX_COLS * COMET_UTF8_REC_WORDS];
+    run_utf8_check(now.data(), (int)now.size(), rec);
+    for (size_t j = 0; j < who.size(); j++) {
+      const size_t k = who[j], c = scols[k];
+      const uint32_t* q = rec + j * COMET_UTF8_REC_WORDS;
+      const int32_t first = (int32_t)q[1], last = (int32_t)q[2], len = (int32_t)q[3];
+      const int hint = chk[k].expect;
+      const int64_t col_offset = chk[k].col_offset;
+      round[k] = -1;
+      if (hint >= 0) {
+        if (q[0] & 2u)
+          throw CometError("device input column " + std::to_string(c) + " is declared comet:utf8_fixed_len=" + std::to_string(hint) + " but holds " +
+                           std::to_string((int64_t)last - first) + " bytes in " + std::to_string(rows) + " rows");
+        if ((int64_t)first != col_offset * hint) continue;      // a sliced column: offset-based accessors only
+        const int32_t* off = (const int32_t*)chk[k].offsets + col_offset;
+        if (now[j].ends_only) {
+          if (uniform_verdict_known(off, rows, hint, first)) views[c].fixed_len = hint;
+          else { chk[k].ends_only = 0; round[k] = r + 1; }
+          continue;
+        }
+        if (q[0] & 1u)
+          throw CometError("device input column " + std::to_string(c) + " is declared comet:utf8_fixed_len=" + std::to_string(hint) +
+                           " but its offsets are not " + std::to_string(hint) + " bytes apart (the byte total alone matches)");
+        remember_uniform_verdict(off, rows, hint, first);
+        views[c].fixed_len = hint;
+        continue;
+      }
+      // value i then sits at aux + (offset + i)·len.  Only claimed when that base IS the data buffer (an unsliced column), because the
+      // offset-based accessors (substring, LIKE, views …) of the same kernels keep addressing aux + offsets[i]
+      if (q[0] != 0 || (int64_t)first != col_offset * len) {
+        if (memo) g_utf8_memo.forget(plan_hash_, input, c);
+        continue;
+      }
+      views[c].fixed_len = len;
+      if (memo && col_offset == 0) g_utf8_memo.put(plan_hash_, input, c, len);      // the next task of this plan launches on it before it has checked
+    }
+  }
+}
+
+// A speculative batch's check, beside the kernel that was launched on the prediction: on a second stream behind an event of the plan's stream
+// (whatever ordered the plan's stream behind the producer orders the check too), in the wave slots k_gagg leaves free — or, with
+// COMET_UTF8_CHECK_STREAM=0, in front of that kernel on the plan's own stream (no overlap, exact per-kernel times).  Called between the record
+// of that event / the launch of k_gagg; the caller makes the plan's stream wait for aux_ev_[1] before it reads the records.
+void ExecutionContext::launch_utf8_check_beside(const Utf8Pending& spec) {
+  const bool beside = utf8_check_stream();
+  if (!aux_ev_[0]) { aux_ev_[0] = pool_get_event(device_id_); aux_ev_[1] = pool_get_event(device_id_); }
+  hipStream_t st = stream_;
+  if (beside) {
+    if (!check_stream_) check_stream_ = pool_get_stream(device_id_);
+    st = check_stream_;
+    HIP_CHECK(hipStreamWaitEvent(st, check_fork_ev_, 0));
+  }
+  HIP_CHECK(hipEventRecord(aux_ev_[0], st));
+  if (comet_launch_utf8_check(spec.chk.data(), (int)spec.chk.size(), utf8_records(), beside ? utf8_check_blocks() : 0, st) != 0)
+    throw CometError("Utf8 length check: launch failed");
+  HIP_CHECK(hipEventRecord(aux_ev_[1], st));
+}
+
+// One verification launch over `n` Utf8 columns on the plan's stream and its records (n × COMET_UTF8_REC_WORDS words) back on the host: one
+// synchronisation.  Timed apart from the main kernels (last_aux_ms / last_aux_launches).
+void ExecutionContext::run_utf8_check(const CometUtf8Check* cols, int n, uint32_t* rec) {
+  const size_t bytes = (size_t)n * COMET_UTF8_REC_WORDS * 4;
+  HIP_CHECK(hipMemsetAsync(utf8_records(), 0, bytes, stream_));
+  if (!aux_ev_[0]) { aux_ev_[0] = pool_get_event(device_id_); aux_ev_[1] = pool_get_event(device_id_); }
+  HIP_CHECK(hipEventRecord(aux_ev_[0], stream_));
+  if (comet_launch_utf8_check(cols, n, utf8_records(), 0, stream_) != 0) throw CometError("Utf8 length check: launch failed");
+  HIP_CHECK(hipEventRecord(aux_ev_[1], stream_));
+  read_small(rec, utf8_records(), bytes);      // (synchronises the stream: the event pair is complete)
+  float aux = 0;
+  if (hipEventElapsedTime(&aux, aux_ev_[0], aux_ev_[1]) == hipSuccess) { last_aux_ms += aux; last_aux_launches += 1; }
 }
 
 // HBM-resident input (Arrow C Device stream, ARROW_DEVICE_ROCM): zero copy.
@@ -706,19 +778,23 @@ bool ExecutionContext::pull_device_batch() {
     cur = std::move(dev_pending_);
     dev_pending_ = DevPending();
   } else {
-    if (dev_stream_done_ || !pull_device_table(0, in_types_, cur.views, cur.has_valid, cur.rows, cur.keep)) return false;
+    if (dev_stream_done_ || !pull_device_table(0, in_types_, cur.views, cur.has_valid, cur.rows, cur.keep, &cur.spec)) return false;
   }
   // A grouped aggregate looks ONE batch ahead before its first chunk: a merging aggregate whose whole input is that chunk can run partitioned
   // (exec_pipeline.cpp try_partitioned_merge) — the usual shape of a Final aggregate over a device-resident table of Partial states
   if (sink_ == SinkKind::AggGrouped && dev_chunks_seen_ == 0 && !dev_stream_done_) {
-    dev_pending_.valid = pull_device_table(0, in_types_, dev_pending_.views, dev_pending_.has_valid, dev_pending_.rows, dev_pending_.keep);
+    dev_pending_.valid = pull_device_table(0, in_types_, dev_pending_.views, dev_pending_.has_valid, dev_pending_.rows, dev_pending_.keep, &dev_pending_.spec);
     if (!dev_pending_.valid) dev_stream_done_ = true;
     single_chunk_hint_ = !dev_pending_.valid;
   } else {
     single_chunk_hint_ = false;
   }
   dev_chunks_seen_++;
-  process_chunk(cur.views, cur.has_valid, cur.rows);
+  process_chunk(cur.views, cur.has_valid, cur.rows, &cur.spec);
+  if (cur.spec.voided) {      // launched on a predicted Utf8 length that the check did not confirm: again, with what the check found
+    cur.spec.apply_checked(cur.views);
+    process_chunk(cur.views, cur.has_valid, cur.rows);
+  }
   HIP_CHECK(hipStreamSynchronize(stream_));
   return true;
 }

@@ -117,8 +117,16 @@ extern "C" int comet_launch_sort_select(const uint8_t* plane, const uint32_t* ca
                                         void* stream);
 extern "C" int comet_launch_fix_rescale(uint64_t* base, int64_t count, int64_t stride_words, int32_t word_off, int32_t shift, void* stream);
 extern "C" int comet_launch_utf8_uniform(const int32_t* offsets, int64_t n, int32_t L, uint32_t* flag, void* stream);
+extern "C" int comet_launch_utf8_check(const CometUtf8Check* cols, int ncols, uint32_t* rec, int max_blocks, void* stream);
 
 namespace comet {
+// Utf8 length speculation (exec_input.cpp): the experiment switches and the prediction memo's eraser
+bool utf8_speculate();
+bool utf8_check_stream();
+int utf8_check_blocks();
+void utf8_memo_forget(uint64_t plan_hash, size_t input, size_t column);
+constexpr bool kUtf8CheckStreamDefault = true;
+constexpr int kUtf8CheckBlocksPerCuDefault = 2;
 // a resident column of any type, children included, into host memory (exec.cpp: nested results and nested shuffle payloads)
 HostColumn download_column(const DeviceColumnView& v, const DType& t, bool has_valid, int64_t rows, hipStream_t st);
 

@@ -3,12 +3,25 @@
 
 namespace comet {
 // one chunk of input rows resident in HBM → run the fused pipeline on it
-void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, const std::vector<bool>& has_valid, int64_t n) {
+void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, const std::vector<bool>& has_valid, int64_t n, Utf8Pending* spec) {
   if (n == 0) return;
   std::vector<int> fixed_lens(cols.size(), -1);
   for (size_t i = 0; i < cols.size(); i++) fixed_lens[i] = cols[i].fixed_len;
   Variant& v = variant_for(has_valid, fixed_lens);
   const PipelineDesc& d = v.desc;
+  // The chunk's Utf8 lengths are a prediction (pull_device_table): only template C's k_gagg launches guarded.  Anything else — a merging aggregate, which
+  // may take the partitioned kernels — checks first after all, and starts over with what the check allows.
+  bool speculative = spec && spec->active;
+  if (speculative && (d.sink != SinkKind::AggGrouped || d.merges_states)) {
+    std::vector<DeviceColumnView> checked = cols;
+    for (CometUtf8Check& c : spec->chk) c.expect = -1;
+    verify_utf8_lengths(spec->input, n, spec->col, spec->chk, checked);
+    spec->active = false;
+    spec->voided = true;
+    spec->checked_len.clear();
+    for (size_t c : spec->col) spec->checked_len.push_back(checked[c].fixed_len);
+    return;
+  }
   if (d.max_rows_exact && input_rows + n > d.max_rows_exact)
     throw CometError("decimal or integer sum over more rows than its static no-overflow proof allows (" + std::to_string(d.max_rows_exact) + ")");
   CometKParams prm;
@@ -63,7 +76,7 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
     if (agg_variant_ && (agg_variant_->desc.NW != d.NW || agg_variant_->desc.NK != d.NK))
       throw CometError("internal: group slot layout differs between variants");
     agg_variant_ = &v;
-    if (try_partitioned_merge(v, prm, n)) return;
+    if (!speculative && try_partitioned_merge(v, prm, n)) return;      // (the partitioned kernels are not guarded)
     const size_t slot_bytes = 8 + 8 * (size_t)(d.NK + d.NW);
     auto alloc_table = [&](DevBuf& buf, int64_t cap) {
       buf.ensure((size_t)cap * slot_bytes);
@@ -104,13 +117,70 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
       prm.out[0] = group_table_.p;
       prm.iarg[0] = group_cap_;
       prm.iarg[kFixScaleArg] = packed_fix_scales(d), prm.iarg[kFixScaleArg2] = packed_fix_scales(d, 4);
-      timed_begin();
-      launch(v, "k_gagg", grid, prm);
-      timed_end();
-      uint64_t head[2 + (kErrBytes - 16) / 8];
+      uint64_t head[2 + (kErrBytes - 16) / 8 + kUtf8RecBytes / 8];
       uint32_t flags[4];
-      read_small(head, err_flags_.p, d.fix_sums.empty() ? 16 : sizeof head);
-      memcpy(flags, head, 16);
+      if (speculative) {
+        // Launch on the prediction: k_gagg's fixed-length variant, guarded (every workgroup compares the columns' end points with the predicted length before
+        // it addresses a byte), and the check of every offset beside it.  The error block is kept as it is now: a miss voids the pass.  No host round trip
+        // before the kernel starts; the read-back behind it brings the check's records along.
+        uint64_t guard = (uint64_t)spec->col.size();
+        for (size_t k = 0; k < spec->col.size(); k++) guard |= (uint64_t)((uint32_t)spec->col[k] | ((uint32_t)spec->chk[k].expect << 5)) << (3 + 9 * k);
+        prm.iarg[kGuardArg] = (long long)guard;
+        const size_t rec_bytes = spec->col.size() * COMET_UTF8_REC_WORDS * 4;
+        err_snapshot_.ensure(kErrBytes);
+        HIP_CHECK(hipMemcpyAsync(err_snapshot_.p, err_flags_.p, kErrBytes, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemsetAsync(utf8_records(), 0, rec_bytes, stream_));
+        const bool beside = utf8_check_stream();
+        if (beside) {
+          if (!check_fork_ev_) check_fork_ev_ = pool_get_event(device_id_);
+          HIP_CHECK(hipEventRecord(check_fork_ev_, stream_));
+        } else {
+          launch_utf8_check_beside(*spec);
+        }
+        timed_begin();
+        launch(v, "k_gagg", grid, prm);
+        timed_end();
+        if (beside) {
+          launch_utf8_check_beside(*spec);
+          HIP_CHECK(hipStreamWaitEvent(stream_, aux_ev_[1], 0));
+        }
+        read_small(head, err_flags_.p, kErrBytes + rec_bytes);
+        float aux = 0;
+        if (hipEventElapsedTime(&aux, aux_ev_[0], aux_ev_[1]) == hipSuccess) { last_aux_ms += aux; last_aux_launches += 1; }
+        memcpy(flags, head, 16);
+        const uint32_t* rec = (const uint32_t*)head + kErrBytes / 4;
+        bool miss = (flags[0] & kErrGuardBit) != 0;
+        for (size_t k = 0; k < spec->col.size(); k++) miss = miss || rec[k * COMET_UTF8_REC_WORDS] != 0;
+        if (miss) {
+          // The pass is void: table and error block (flags, group counter, the aggregates' aux words) go back to where they were, the rows are not
+          // counted, the prediction is forgotten.  The records say what the check found — a column that is uniform after all (at the predicted length; another
+          // length was not looked for) keeps its fixed-length loads —, and the chunk runs again as a checked one.
+          if (clear) HIP_CHECK(hipMemsetAsync(group_table_.p, 0, (size_t)group_cap_ * slot_bytes, stream_));
+          else HIP_CHECK(hipMemcpyAsync(group_table_.p, group_backup_.p, (size_t)group_cap_ * slot_bytes, hipMemcpyDeviceToDevice, stream_));
+          HIP_CHECK(hipMemcpyAsync(err_flags_.p, err_snapshot_.p, kErrBytes, hipMemcpyDeviceToDevice, stream_));
+          spec->checked_len.clear();
+          for (size_t k = 0; k < spec->col.size(); k++) {
+            const uint32_t* q = rec + k * COMET_UTF8_REC_WORDS;
+            const bool good = q[0] == 0 && (int32_t)q[3] == spec->chk[k].expect && (int64_t)(int32_t)q[1] == spec->chk[k].col_offset * spec->chk[k].expect;
+            spec->checked_len.push_back(good ? spec->chk[k].expect : -1);
+            if (!good) utf8_memo_forget(plan_hash_, spec->input, spec->col[k]);
+          }
+          spec->active = false;
+          spec->voided = true;
+          if (!has_join_) input_rows -= n;
+          agg_rows_seen_ -= n;
+          return;
+        }
+        speculative = false;      // verified: what follows (a full table, a moved float window) re-runs the chunk as a checked one
+        spec->active = false;
+        prm.iarg[kGuardArg] = 0;
+      } else {
+        timed_begin();
+        launch(v, "k_gagg", grid, prm);
+        timed_end();
+        read_small(head, err_flags_.p, d.fix_sums.empty() ? 16 : (size_t)kErrBytes);
+        memcpy(flags, head, 16);
+      }
       uint64_t groups_now;
       memcpy(&groups_now, &flags[2], 8);
       const bool full = (flags[0] & 32u) != 0;

@@ -42,36 +42,84 @@ __global__ __launch_bounds__(256) void pmod_kernel(const u32* hashes, i64 n, i32
   for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) out[i] = pmod(hashes[i], np);
 }
 
-// Are all n Utf8 values exactly L bytes long?  (lets the fused kernels address the bytes directly, see ld_str_fixed)
-// Streaming read of the offsets: four independent 16-byte loads per lane and iteration; offset i must equal off[0] + i·L, so no value
-// depends on its neighbour and nothing is exchanged between lanes.
-__global__ __launch_bounds__(256) void utf8_uniform_kernel(const i32* off, i64 n, i32 L, u32* flag) {
+// Are all values of a Utf8 column equally long?  (lets the fused kernels address the bytes directly, see ld_str_fixed)
+// ONE launch checks every Utf8 column of a batch: workgroup row blockIdx.y streams the offsets of column y.  The kernel reads the column's end
+// points itself — L = (off[n] − off[0]) / n unless the caller expects a length — and leaves a record per column: bit 0 of word 0 = some value
+// is not L bytes long, bit 1 = the end points rule a uniform length out (the byte total is no multiple of the rows, negative, more than 15
+// bytes per value, or not what the caller expects: nothing else is read then), words 1 … 3 = first offset, last offset, L.
+// The loads are lane-contiguous: lane l of a wave reads the 16-byte group wave_base + u·64 + l, so every load instruction of a wave covers
+// 1 KiB of consecutive bytes and every cache line is asked for by one instruction; kUtf8Unroll of them are in flight per lane.  Offset i must
+// equal off[0] + i·L, so no value depends on its neighbour and nothing is exchanged between lanes.
+constexpr int kUtf8Unroll = 8;
+constexpr int kUtf8MaxCols = COMET_UTF8_MAX_COLS;
+constexpr int kUtf8MaxBlocks = 256 * 8;      // all columns together: every workgroup of the launch is resident at once
+struct Utf8CheckCol {
+  const i32* off;      // the column's offsets buffer
+  i64 rows;
+  i64 col_offset;      // Arrow `offset` of the column: its offsets start at off + col_offset
+  i32 expect;          // the length every value must have, −1 = whatever the end points give
+  i32 ends_only;       // ≠ 0: end points and record only (the offsets in between were verified before)
+};
+struct Utf8CheckArgs { Utf8CheckCol c[kUtf8MaxCols]; };
+typedef int utf8_v4i __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void utf8_uniform_kernel(const Utf8CheckArgs args, u32* rec, int rec_words) {
+  const Utf8CheckCol c = args.c[blockIdx.y];
+  const i64 n = c.rows;
+  if (n <= 0) return;
+  const COMET_GLOBAL i32* off = (const COMET_GLOBAL i32*)c.off + c.col_offset;
+  u32* r = rec + (size_t)blockIdx.y * rec_words;
+  const i32 o0 = off[0], o_n = off[n];
+  const i64 bytes = (i64)o_n - (i64)o0;
+  i32 L = c.expect;
+  bool ends_bad;
+  if (L >= 0) {
+    ends_bad = bytes != (i64)L * n;
+  } else {
+    ends_bad = bytes < 0 || bytes % n != 0 || bytes / n > 15;
+    L = ends_bad ? -1 : (i32)(bytes / n);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (rec_words >= 4) { r[1] = (u32)o0; r[2] = (u32)o_n; r[3] = (u32)L; }
+    if (ends_bad) atomicOr(r, 2u);
+  }
+  if (ends_bad || c.ends_only) return;
   bool bad = false;
-  const i32 o0 = off[0];
   const i64 total = n + 1;                                   // offsets to check
-  i64 head = 0;                                              // elements before the first 16-byte boundary
-  while (head < total && ((((uintptr_t)(off + head)) & 15) != 0)) head++;
-  const int4* v4 = (const int4*)(off + head);
+  i64 head = (i64)(((16 - ((uintptr_t)off & 15)) & 15) >> 2);   // elements before the first 16-byte boundary
+  if (head > total) head = total;
+  const COMET_GLOBAL utf8_v4i* v4 = (const COMET_GLOBAL utf8_v4i*)(off + head);
   const i64 ngroups = (total - head) / 4;
-  constexpr int U = 4;
-  for (i64 g0 = ((i64)blockIdx.x * 256 + threadIdx.x) * U; g0 < ngroups; g0 += (i64)gridDim.x * 256 * U) {
-    int4 v[U];
+  constexpr int U = kUtf8Unroll;
+  const u32 uL = (u32)L, u0 = (u32)o0;                        // expected offsets wrap like the offsets would; compared for equality only
+  const int lane = threadIdx.x & 63;
+  const i64 wave = (i64)blockIdx.x * (256 / 64) + (threadIdx.x >> 6), waves = (i64)gridDim.x * (256 / 64);
+  for (i64 g0 = wave * (U * 64); g0 < ngroups; g0 += waves * (U * 64)) {
+    if (g0 + U * 64 <= ngroups) {                            // (wave-uniform) a whole chunk: U loads in flight, no predicate between them
+      utf8_v4i v[U];
 #pragma unroll
-    for (int u = 0; u < U; u++) v[u] = g0 + u < ngroups ? v4[g0 + u] : make_int4(0, 0, 0, 0);
+      for (int u = 0; u < U; u++) v[u] = __builtin_nontemporal_load(v4 + g0 + u * 64 + lane);
 #pragma unroll
-    for (int u = 0; u < U; u++) {
-      if (g0 + u < ngroups) {
-        const i64 i = head + 4 * (g0 + u);
-        const i32 e = o0 + (i32)(i * L);                      // wraps like the offsets would; compared for equality only
-        bad |= (v[u].x != e) | (v[u].y != e + L) | (v[u].z != e + 2 * L) | (v[u].w != e + 3 * L);
+      for (int u = 0; u < U; u++) {
+        const u32 e = u0 + (u32)(head + 4 * (g0 + u * 64 + lane)) * uL;
+        bad |= ((u32)v[u].x != e) | ((u32)v[u].y != e + uL) | ((u32)v[u].z != e + 2 * uL) | ((u32)v[u].w != e + 3 * uL);
+      }
+    } else {                                                 // the column's last, ragged chunk
+      for (int u = 0; u < U; u++) {
+        const i64 g = g0 + u * 64 + lane;
+        if (g < ngroups) {
+          const utf8_v4i v = __builtin_nontemporal_load(v4 + g);
+          const u32 e = u0 + (u32)(head + 4 * g) * uL;
+          bad |= ((u32)v.x != e) | ((u32)v.y != e + uL) | ((u32)v.z != e + 2 * uL) | ((u32)v.w != e + 3 * uL);
+        }
       }
     }
   }
   if (blockIdx.x == 0) {
-    for (i64 i = threadIdx.x; i < head; i += 256) bad |= off[i] != o0 + (i32)(i * L);
-    for (i64 i = head + ngroups * 4 + threadIdx.x; i < total; i += 256) bad |= off[i] != o0 + (i32)(i * L);
+    for (i64 i = threadIdx.x; i < head; i += 256) bad |= (u32)off[i] != u0 + (u32)i * uL;
+    for (i64 i = head + ngroups * 4 + threadIdx.x; i < total; i += 256) bad |= (u32)off[i] != u0 + (u32)i * uL;
   }
-  if (__any(bad) && lane_id() == 0) atomicOr(flag, 1u);
+  if (__any(bad) && lane_id() == 0) atomicOr(r, 1u);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -207,9 +255,42 @@ extern "C" int comet_calib_read(const void* p, int64_t n_bytes, int32_t lane_byt
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// cols[0 … ncols): one launch; rec = ncols records of COMET_UTF8_REC_WORDS words each, zeroed by the caller.  max_blocks > 0 caps the workgroups of
+// the whole launch (a check that runs beside another kernel takes the wave slots that kernel leaves free).
+static int utf8_check_grid(i64 rows, int ncols, int max_blocks) {
+  const i64 per_block = (i64)256 * kUtf8Unroll * 4;          // offsets one workgroup covers per grid-stride iteration
+  i64 g = (rows + 1 + per_block - 1) / per_block;
+  const int nc = ncols > 0 ? ncols : 1;
+  i64 cap = kUtf8MaxBlocks / nc;
+  if (max_blocks > 0 && max_blocks / nc < cap) cap = max_blocks / nc;
+  if (cap < 1) cap = 1;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+extern "C" int comet_launch_utf8_check(const CometUtf8Check* cols, int ncols, uint32_t* rec, int max_blocks, void* stream) {
+  if (ncols <= 0) return 0;
+  if (ncols > kUtf8MaxCols) return -1;
+  Utf8CheckArgs a = {};
+  i64 rows = 0;
+  for (int k = 0; k < ncols; k++) {
+    a.c[k].off = cols[k].offsets;
+    a.c[k].rows = cols[k].rows;
+    a.c[k].col_offset = cols[k].col_offset;
+    a.c[k].expect = cols[k].expect;
+    a.c[k].ends_only = cols[k].ends_only;
+    if (cols[k].rows > rows && !cols[k].ends_only) rows = cols[k].rows;
+  }
+  hipLaunchKernelGGL(utf8_uniform_kernel, dim3((unsigned)utf8_check_grid(rows, ncols, max_blocks), (unsigned)ncols), dim3(256), 0, (hipStream_t)stream, a, rec,
+                     COMET_UTF8_REC_WORDS);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// one column, one flag word: *flag becomes non-zero unless every one of the n values is L bytes long
 extern "C" int comet_launch_utf8_uniform(const int32_t* offsets, int64_t n, int32_t L, uint32_t* flag, void* stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(utf8_uniform_kernel, grid_for(n), 256, 0, (hipStream_t)stream, offsets, (i64)n, L, flag);
+  Utf8CheckArgs a = {};
+  a.c[0].off = offsets;
+  a.c[0].rows = n;
+  a.c[0].expect = L;
+  hipLaunchKernelGGL(utf8_uniform_kernel, dim3((unsigned)utf8_check_grid(n, 1, 0)), dim3(256), 0, (hipStream_t)stream, a, flag, 1);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -31,4 +31,17 @@ typedef struct CometKParams {
   void* out[COMET_MAX_OUT];    /* outputs / scratch, meaning defined per kernel template */
 } CometKParams;
 
+/* One Utf8 column of a batch as the verification launch sees it (kernels_static.hip utf8_uniform_kernel), and what the launch leaves per
+ * column: COMET_UTF8_REC_WORDS u32 — [0] bit 0 = some value is not L bytes long, bit 1 = the end points rule a uniform length out (or
+ * contradict `expect`), [1] first offset, [2] last offset, [3] L. */
+#define COMET_UTF8_REC_WORDS 4
+#define COMET_UTF8_MAX_COLS 16
+typedef struct CometUtf8Check {
+  const int* offsets;          /* the column's offsets buffer */
+  long long rows;
+  long long col_offset;        /* Arrow `offset` of the column */
+  int expect;                  /* the length every value must have, -1 = what the end points give */
+  int ends_only;               /* != 0: end points and record only */
+} CometUtf8Check;
+
 #endif

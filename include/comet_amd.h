@@ -107,9 +107,11 @@ int64_t comet_plan_kernel_times(int64_t handle, char* buf, size_t cap);
 /* … the same switch at run time (process-wide; plans created afterwards time their launches). */
 void comet_set_kernel_times(int32_t on);
 
-/* … and of the input-verification launches that run ahead of them (utf8_uniform_kernel over the Utf8 offsets of an HBM-resident input,
- * the check behind addressing fixed-length strings directly): total milliseconds and launches, timed apart from the main kernels so that
- * bench.py's roofline charges every column's bytes to the kernel that reads them. */
+/* … and of the input-verification launches (utf8_uniform_kernel over the Utf8 offsets of an HBM-resident input, the check behind addressing
+ * fixed-length strings directly; one launch per batch covers all its Utf8 columns): total milliseconds and launches, timed apart from the main
+ * kernels so that bench.py's roofline charges every column's bytes to the kernel that reads them.  The check runs ahead of the main kernel, or —
+ * when the plan has verified these columns' lengths in an earlier task and launches on that prediction — beside it on a second stream: the
+ * event pair then spans the time both kernels shared the memory system, and aux_ms + the main kernels' ms exceeds the task's GPU time. */
 void comet_plan_aux_kernel_stats(int64_t handle, double* aux_ms, int64_t* aux_launches);
 
 /* Decode + plan + generate + compile (hiprtc, gfx950) without touching a GPU.  Returns 0 on success and
@@ -228,7 +230,7 @@ int64_t comet_embedded_header(const char* name, char* out, int64_t cap);
 int64_t comet_error_site_json(uint32_t site_id, uint64_t lo, uint64_t hi, const uint8_t* str, int64_t str_avail, char* out, int64_t cap);
 /* a streaming read of `bytes` bytes with `width`-byte loads (4 / 8 / 16) into a sink word: the known byte count tools/pmc_calibrate.py calibrates FETCH_SIZE on */
 int comet_calib_read(const void* buf, int64_t bytes, int32_t width, uint64_t* sink, void* stream);
-/* the headline's Utf8 pass on its own (kernels_static.hip utf8_uniform_kernel): *flag becomes non-zero unless every value of the n offsets has length L */
+/* the headline's Utf8 pass on its own (kernels_static.hip utf8_uniform_kernel, its one-column form): *flag becomes non-zero unless every one of the n values has length L */
 int comet_launch_utf8_uniform(const int32_t* offsets, int64_t n, int32_t L, uint32_t* flag, void* stream);
 /* Spark's BloomFilter over longs (csrc/device/bloom.hpp: the code the kernels run) on the host — diagnostic entries, no GPU.
  * comet_spark_bloom_might_contain: `bytes` is a serialized filter (V1: i32 1 | numHashFunctions | numWords | words, V2: i32 2 | numHashFunctions | seed | numWords | words,
