@@ -747,6 +747,13 @@ int32_t comet_split_host(const char* pattern, int32_t limit, const uint8_t* valu
   });
 }
 
+int64_t comet_regexp_replace_host(const char* pattern, const char* replacement, const uint8_t* value, size_t value_len, uint8_t* out, int64_t cap) {
+  return guarded(nullptr, (int64_t)-2, [&]() -> int64_t {
+    const RegexReplace r = compile_regex_replace(pattern ? pattern : "", replacement ? replacement : "");
+    return regex_replace_host(r, value, value_len, out, cap);
+  });
+}
+
 namespace comet_dates_host {
 #include "device/dates.hpp"
 }

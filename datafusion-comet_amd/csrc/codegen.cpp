@@ -339,6 +339,51 @@ ExprP lower_split(const ExprP& e) {
   b->has_dtype = true;
   return b;
 }
+// regexp_replace(<Utf8 source column>, <pattern>, <replacement>, 'g') (strings.scala:545-587 sends this form only, under
+// spark.comet.expression.RegExpReplace.allowIncompatible and for pos = 1; DataFusion's regexp_replace with the g flag = the crate's Regex::replace_all):
+// a derived Utf8 column like the string functions above — the matcher's programs and the parsed replacement travel with it (regex.cpp compile_regex_replace).
+ExprP lower_regexp_replace(const ExprP& e) {
+  const std::string f = "regexp_replace";
+  if (!g_derived || !g_source_cols) throw CometError(f + " is supported in Projection / Filter chains only");
+  if (e->children.size() != 4) throw CometError("regexp_replace expects 4 arguments (subject, pattern, replacement, 'g'), got " + std::to_string(e->children.size()));
+  const ExprP &subject = e->children[0], &pat = e->children[1], &rep = e->children[2], &flags = e->children[3];
+  const int nsrc = (int)g_source_cols->size();
+  if (subject->kind != ExprKind::Bound || subject->bound_index < 0 || subject->bound_index >= nsrc || !subject->has_dtype || subject->dtype.id != TypeId::String)
+    throw CometError(f + " is supported over a Utf8 COLUMN of the source (not over a computed string) by the MI355X native engine");
+  auto str_lit = [&](const ExprP& x, const char* what) {
+    if (x->kind != ExprKind::Literal || (x->dtype.id != TypeId::String && !x->lit_null)) throw CometError(f + ": " + what + " must be a string literal");
+    if (x->lit_null) throw CometError(f + " with a NULL " + what + " is not supported by the MI355X native engine");
+  };
+  str_lit(pat, "pattern");
+  str_lit(rep, "replacement");
+  if (flags->kind != ExprKind::Literal || flags->lit_null || flags->dtype.id != TypeId::String || flags->lit_bytes != "g")
+    throw CometError("regexp_replace: the flags argument must be the literal 'g' (what Spark's regexp_replace means)");
+  const RegexReplace r = compile_regex_replace(pat->lit_bytes, rep->lit_bytes);
+  DerivedCol dc;
+  dc.kind = 3;
+  dc.op = kDerivedRegexpReplace;
+  dc.src = subject->bound_index;
+  dc.arg_a = pat->lit_bytes;
+  dc.arg_b = rep->lit_bytes;
+  dc.prog = r.progs[0].words;
+  for (size_t k = 1; k < r.progs.size(); k++) dc.group_progs.push_back(r.progs[k].words);
+  dc.segs = r.segs;
+  dc.lits = r.lits;
+  dc.type = DType::of(TypeId::String);
+  size_t k = 0;
+  for (; k < g_derived->size(); k++) {
+    const DerivedCol& o = (*g_derived)[k];
+    if (o.kind == 3 && o.src == dc.src && o.op == dc.op && o.arg_a == dc.arg_a && o.arg_b == dc.arg_b) break;
+  }
+  if (k == g_derived->size()) g_derived->push_back(dc);
+  auto b = std::make_shared<Expr>();
+  b->kind = ExprKind::Bound;
+  b->proto_tag = 3;
+  b->bound_index = derived_index(nsrc, k);
+  b->dtype = dc.type;
+  b->has_dtype = true;
+  return b;
+}
 ExprP lower_struct_field(const ExprP& e, const ExprP& child) {
   if (child->kind != ExprKind::Bound || !child->has_dtype || child->dtype.id != TypeId::Struct)
     throw CometError("GetStructField of anything but a struct COLUMN is not supported yet");
@@ -363,6 +408,10 @@ ExprP substitute(const ExprP& e, const std::vector<ExprP>& cols, std::map<const 
     auto n = std::make_shared<Expr>(*e);
     for (auto& c : n->children) c = substitute(c, cols, memo);
     out = lower_split(n);
+  } else if (e->kind == ExprKind::ScalarFunc && e->func == "regexp_replace") {
+    auto n = std::make_shared<Expr>(*e);
+    for (auto& c : n->children) c = substitute(c, cols, memo);
+    out = lower_regexp_replace(n);
   } else if (e->kind == ExprKind::Bound) {
     if (e->bound_index < 0 || (size_t)e->bound_index >= cols.size())
       throw CometError("Column index " + std::to_string(e->bound_index) + " is out of bound. Schema has " +

@@ -45,16 +45,22 @@ struct OutCol {
 // which the chain passes through by row index like any nested column.
 struct DerivedCol {
   int kind = 0;                     // 1: split, 2: regexp_extract_all (two columns each: the list, then its elements), 3: a string function → Utf8 (one column)
-  int op = 0;                       // kind 3: device/strfn.hpp's operation (SF_REVERSE …)
-  std::string arg_a, arg_b;         // kind 3: the literal arguments' bytes
+  int op = 0;                       // kind 3: device/strfn.hpp's operation (SF_REVERSE …), or kDerivedRegexpReplace
+  std::string arg_a, arg_b;         // kind 3: the literal arguments' bytes (regexp_replace: the pattern and the replacement as written)
   long long arg_k = 0;              // kind 3: the integer argument
   int columns() const { return kind == 3 ? 1 : 2; }
   int src = -1;                     // the source column
   std::vector<uint32_t> prog;       // the pattern as a group-0 program of device/regex_vm.hpp
   std::vector<uint32_t> prog2;      // regexp_extract_all: the wanted group's program (empty: group 0)
   int limit = -1;
+  // regexp_replace (kind 3, op kDerivedRegexpReplace; `prog` drives the iteration): the programs of the groups ≥ 1 the replacement names, and the
+  // replacement as rx_replace's segments (three words each) over its literal bytes
+  std::vector<std::vector<uint32_t>> group_progs;
+  std::vector<uint32_t> segs;
+  std::string lits;
   DType type;
 };
+constexpr int kDerivedRegexpReplace = 30;
 
 // How the host must treat each group-key word / accumulator word of a grouped aggregate.
 struct PipelineDesc {

@@ -195,31 +195,44 @@ RXVM_FN bool rx_extract(const rx_u32* w, P text, rx_i32 n, rx_i32& m0, rx_i32& m
   return rx_search(w, text, n, 0, m0, m1);
 }
 
+// The crate's find_iter over a group-0 program: the successive leftmost matches, each search starting where the last match ended.  An empty match
+// that ends where the previous match ended is dropped and the search resumes one character (not one byte) on — and since a search from the end of
+// an EMPTY match can only find that match again, it is not run at all.  `f(k, at, m0, m1)` sees match k = [m0, m1) and the position `at` its search
+// started from (a group's program searched from there finds the same match); at most `max_matches` matches when that is ≥ 0.  → the number of matches.
+template <class P, class F>
+RXVM_FN rx_i32 rx_for_matches(const rx_u32* w, P text, rx_i32 n, rx_i32 max_matches, F f) {
+  rx_i32 at = 0, last_end = -1, k = 0;
+  bool last_empty = false;
+  while (max_matches < 0 || k < max_matches) {
+    rx_i32 m0 = -1, m1 = -1;
+    bool hit = !last_empty && rx_search(w, text, n, at, m0, m1) && m0 >= 0;
+    if (last_empty || (hit && m0 == m1 && m1 == last_end)) {
+      at = at + 1;
+      while (at < n && (text[at] & 0xC0u) == 0x80u) at++;
+      hit = rx_search(w, text, n, at, m0, m1) && m0 >= 0;
+    }
+    if (!hit) break;
+    f(k, at, m0, m1);
+    k++;
+    at = m1;
+    last_end = m1;
+    last_empty = m0 == m1;
+  }
+  return k;
+}
+
 // split(str, pattern, limit) (string_funcs/split.rs:434-472 over the crate's Regex::split / find_iter): the pieces between successive
-// matches of a group-0 program.  find_iter's rule for empty matches: one that ends where the previous match ended is dropped and the
-// search resumes one character on.  limit > 0: at most limit − 1 cuts; limit = 0: trailing empty pieces are dropped (nothing left = one
+// matches of a group-0 program.  limit > 0: at most limit − 1 cuts; limit = 0: trailing empty pieces are dropped (nothing left = one
 // empty piece); limit < 0: every piece.  `emit(k, start, len)` sees piece k; → the number of pieces the list holds.  With `max_emit` the
 // caller bounds what is emitted (the writing pass passes the count the counting pass returned).
 template <class P, class F>
 RXVM_FN rx_i32 rx_split(const rx_u32* w, P text, rx_i32 n, rx_i32 limit, rx_i32 max_emit, F emit) {
-  rx_i32 last = 0, at = 0, last_end = -1, k = 0, kept = 0;
-  while (true) {
-    if (limit > 0 && k >= limit - 1) break;
-    rx_i32 m0 = -1, m1 = -1;
-    if (!rx_search(w, text, n, at, m0, m1) || m0 < 0) break;
-    if (m0 == m1 && m1 == last_end) {
-      // an empty match right behind the previous match: the search resumes behind the next character
-      at = at + 1;
-      while (at < n && (text[at] & 0xC0u) == 0x80u) at++;
-      if (!rx_search(w, text, n, at, m0, m1) || m0 < 0) break;
-    }
-    if (k < max_emit) emit(k, last, m0 - last);
-    if (m0 > last) kept = k + 1;
-    k++;
+  rx_i32 last = 0, kept = 0;
+  rx_i32 k = rx_for_matches(w, text, n, limit > 0 ? limit - 1 : -1, [&](rx_i32 j, rx_i32, rx_i32 m0, rx_i32 m1) {
+    if (j < max_emit) emit(j, last, m0 - last);
+    if (m0 > last) kept = j + 1;
     last = m1;
-    at = m1;
-    last_end = m1;
-  }
+  });
   if (k < max_emit) emit(k, last, n - last);
   if (n > last) kept = k + 1;
   k++;
@@ -232,23 +245,44 @@ RXVM_FN rx_i32 rx_split(const rx_u32* w, P text, rx_i32 n, rx_i32 limit, rx_i32 
 // from the same position both find the same match.  `emit(k, start, len)` sees match k's group (empty when it took no part); → the number of matches.
 template <class P, class F>
 RXVM_FN rx_i32 rx_find_all(const rx_u32* w0, const rx_u32* wg, P text, rx_i32 n, rx_i32 max_emit, F emit) {
-  rx_i32 at = 0, last_end = -1, k = 0;
-  while (true) {
-    rx_i32 m0 = -1, m1 = -1;
-    if (!rx_search(w0, text, n, at, m0, m1) || m0 < 0) break;
-    if (m0 == m1 && m1 == last_end) {
-      at = at + 1;
-      while (at < n && (text[at] & 0xC0u) == 0x80u) at++;
-      if (!rx_search(w0, text, n, at, m0, m1) || m0 < 0) break;
-    }
-    if (k < max_emit) {
+  return rx_for_matches(w0, text, n, -1, [&](rx_i32 k, rx_i32 at, rx_i32 m0, rx_i32 m1) {
+    if (k >= max_emit) return;
+    rx_i32 g0 = m0, g1 = m1;
+    if (wg != w0 && !rx_search(wg, text, n, at, g0, g1)) g0 = g1 = -1;
+    emit(k, g0 < 0 ? 0 : g0, g0 < 0 ? 0 : g1 - g0);
+  });
+}
+
+// regexp_replace(str, pattern, replacement, 'g') (DataFusion's regexp_replace with the g flag = the crate's Regex::replace_all): for every match in
+// order the text since the last match, then the replacement template expanded for the match; behind the last match the rest of the text.  The
+// template is parsed on the host (regex.cpp parse_replacement: the crate's Captures::expand) into `nseg` segments of three words: kind, a, b —
+//   kind 0: `b` literal bytes at byte `a` of the template's literal bytes      kind 1: the group whose program is progs[a] (a = 0: the whole match)
+// A group's span comes from its own program searched from the position the match's search started from; a group that took no part in the match
+// expands to nothing.  `put_text(start, len)` sees bytes of the text, `put_lit(start, len)` bytes of the template's literals, both in output order;
+// → the result's length.  The length pass hands in callbacks that do nothing, the writing pass ones that copy: one source for both.
+constexpr int kRxReplaceGroups = 4;      // programs beside the group-0 program: distinct groups ≥ 1 one template may name
+template <class P, class T, class L>
+RXVM_FN rx_u64 rx_replace(const rx_u32* const* progs, const rx_u32* segs, rx_i32 nseg, P text, rx_i32 n, T put_text, L put_lit) {
+  rx_i32 last = 0;
+  rx_u64 total = 0;
+  rx_for_matches(progs[0], text, n, -1, [&](rx_i32, rx_i32 at, rx_i32 m0, rx_i32 m1) {
+    put_text(last, m0 - last);
+    total += (rx_u64)(m0 - last);
+    for (rx_i32 s = 0; s < nseg; s++) {
+      const rx_u32 kind = segs[3 * s], a = segs[3 * s + 1], b = segs[3 * s + 2];
+      if (kind == 0u) {
+        put_lit((rx_i32)a, (rx_i32)b);
+        total += b;
+        continue;
+      }
       rx_i32 g0 = m0, g1 = m1;
-      if (wg != w0 && !rx_search(wg, text, n, at, g0, g1)) g0 = g1 = -1;
-      emit(k, g0 < 0 ? 0 : g0, g0 < 0 ? 0 : g1 - g0);
+      if (a != 0u && !rx_search(progs[a], text, n, at, g0, g1)) g0 = g1 = -1;
+      if (g0 < 0) continue;
+      put_text(g0, g1 - g0);
+      total += (rx_u64)(g1 - g0);
     }
-    k++;
-    at = m1;
-    last_end = m1;
-  }
-  return k;
+    last = m1;
+  });
+  put_text(last, n - last);
+  return total + (rx_u64)(n - last);
 }

@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "exec_internal.hpp"
+#include "regex.hpp"
 
 namespace comet {
 
@@ -1428,6 +1429,7 @@ DevTable ExecutionContext::outputs_to_table(Variant& v, const std::vector<std::s
 }
 
 // A derived Utf8 column (DerivedCol kind 3): a string function of a source column with new bytes (device/strfn.hpp) — lengths, prefix sum, bytes.
+// regexp_replace takes the same three steps with the matcher's kernels (regex_kernels.hip) in place of the string functions'.
 void ExecutionContext::extend_derived_strfn(DevTable& in, const DerivedCol& dc) {
   if (dc.src < 0 || (size_t)dc.src >= in.cols.size()) throw CometError("internal: unknown derived column");
   const DeviceColumnView sc = in.cols[(size_t)dc.src];
@@ -1437,8 +1439,30 @@ void ExecutionContext::extend_derived_strfn(DevTable& in, const DerivedCol& dc) 
   if (hv && sc.offset != 0) throw CometError("a string function over a sliced Utf8 column with NULLs is not supported yet");
   DevBuf args, lengths, tiles, flag;
   auto offsets = std::make_shared<DevBuf>(), bytes = std::make_shared<DevBuf>();
-  const size_t na = dc.arg_a.size(), nb = dc.arg_b.size();
-  args.ensure(na + nb + 16);
+  const bool rx = dc.op == kDerivedRegexpReplace;
+  // regexp_replace: the programs (group 0, then the named groups'), the replacement's segments and its literal bytes, one upload each into `args`
+  const uint32_t* progs[kRegexReplaceGroups + 1] = {};
+  const uint32_t* segs = nullptr;
+  const uint8_t* lits = nullptr;
+  if (rx) {
+    if (dc.group_progs.size() > (size_t)kRegexReplaceGroups) throw CometError("internal: regexp_replace with too many group programs");
+    size_t words = dc.prog.size() + dc.segs.size();
+    for (auto& g : dc.group_progs) words += g.size();
+    args.ensure(words * 4 + dc.lits.size() + 16);
+    char* at = (char*)args.p;
+    auto put = [&](const void* src, size_t n) {
+      char* here = at;
+      if (n) HIP_CHECK(hipMemcpyAsync(here, src, n, hipMemcpyHostToDevice, stream_));
+      at += n;
+      return here;
+    };
+    progs[0] = (const uint32_t*)put(dc.prog.data(), dc.prog.size() * 4);
+    for (size_t g = 0; g < dc.group_progs.size(); g++) progs[g + 1] = (const uint32_t*)put(dc.group_progs[g].data(), dc.group_progs[g].size() * 4);
+    segs = (const uint32_t*)put(dc.segs.data(), dc.segs.size() * 4);
+    lits = (const uint8_t*)put(dc.lits.data(), dc.lits.size());
+  }
+  const size_t na = rx ? 0 : dc.arg_a.size(), nb = rx ? 0 : dc.arg_b.size();
+  if (!rx) args.ensure(na + nb + 16);
   if (na) HIP_CHECK(hipMemcpyAsync(args.p, dc.arg_a.data(), na, hipMemcpyHostToDevice, stream_));
   if (nb) HIP_CHECK(hipMemcpyAsync((char*)args.p + na, dc.arg_b.data(), nb, hipMemcpyHostToDevice, stream_));
   flag.ensure(16);
@@ -1451,7 +1475,9 @@ void ExecutionContext::extend_derived_strfn(DevTable& in, const DerivedCol& dc) 
   const int32_t* offs = (const int32_t*)sc.data + sc.offset;
   const uint8_t* vbits = hv ? sc.valid : nullptr;
   const uint8_t *a = (const uint8_t*)args.p, *b = (const uint8_t*)args.p + na;
-  if (comet_launch_strfn_len(dc.op, offs, (const uint8_t*)sc.aux, vbits, sc.offset, rows, a, (int32_t)na, b, (int32_t)nb, dc.arg_k, (uint32_t*)lengths.p, (uint32_t*)flag.p, stream_) != 0)
+  const int32_t nseg = (int32_t)(dc.segs.size() / 3);
+  if ((rx ? comet_launch_replace_len(offs, (const uint8_t*)sc.aux, vbits, sc.offset, rows, progs, segs, nseg, lits, (uint32_t*)lengths.p, (uint32_t*)flag.p, stream_)
+          : comet_launch_strfn_len(dc.op, offs, (const uint8_t*)sc.aux, vbits, sc.offset, rows, a, (int32_t)na, b, (int32_t)nb, dc.arg_k, (uint32_t*)lengths.p, (uint32_t*)flag.p, stream_)) != 0)
     throw CometError("string function: launch failed");
   if (rows) pq_launch_u32_scan((const uint32_t*)lengths.p, rows, (uint64_t*)tiles.p, (int32_t*)offsets->p, stream_);
   int32_t total = 0;
@@ -1460,7 +1486,8 @@ void ExecutionContext::extend_derived_strfn(DevTable& in, const DerivedCol& dc) 
   read_small(&too_long, flag.p, 4);
   if (total < 0 || too_long) throw CometError("Utf8 column exceeds 2 GiB of string data (LargeUtf8 is not supported)");
   bytes->ensure((size_t)total + 16);
-  if (comet_launch_strfn_write(dc.op, offs, (const uint8_t*)sc.aux, vbits, sc.offset, rows, a, (int32_t)na, b, (int32_t)nb, dc.arg_k, (const int32_t*)offsets->p, (uint8_t*)bytes->p, stream_) != 0)
+  if ((rx ? comet_launch_replace_write(offs, (const uint8_t*)sc.aux, vbits, sc.offset, rows, progs, segs, nseg, lits, (const int32_t*)offsets->p, (uint8_t*)bytes->p, stream_)
+          : comet_launch_strfn_write(dc.op, offs, (const uint8_t*)sc.aux, vbits, sc.offset, rows, a, (int32_t)na, b, (int32_t)nb, dc.arg_k, (const int32_t*)offsets->p, (uint8_t*)bytes->p, stream_)) != 0)
     throw CometError("string function: launch failed");
   HIP_CHECK(hipStreamSynchronize(stream_));      // the literals, lengths and tiles go back to the pool
   DeviceColumnView cv;

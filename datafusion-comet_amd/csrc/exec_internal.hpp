@@ -79,6 +79,10 @@ extern "C" int comet_launch_split_count(const int32_t* offs, const uint8_t* byte
                                         uint32_t* counts, void* stream);
 extern "C" int comet_launch_split_write(const int32_t* offs, const uint8_t* bytes, const uint8_t* valid_bits, int64_t valid_first, int64_t n, const uint32_t* prog, const uint32_t* prog2, int32_t limit,
                                         const int32_t* list_offs, void* views, void* stream);
+extern "C" int comet_launch_replace_len(const int32_t* offs, const uint8_t* bytes, const uint8_t* valid_bits, int64_t valid_first, int64_t n, const uint32_t* const* progs, const uint32_t* segs, int32_t nseg,
+                                        const uint8_t* lits, uint32_t* lengths, uint32_t* too_long, void* stream);
+extern "C" int comet_launch_replace_write(const int32_t* offs, const uint8_t* bytes, const uint8_t* valid_bits, int64_t valid_first, int64_t n, const uint32_t* const* progs, const uint32_t* segs, int32_t nseg,
+                                          const uint8_t* lits, const int32_t* out_offs, uint8_t* out, void* stream);
 extern "C" int comet_launch_strview_lengths(const void* views, const uint8_t* ok_bytes, int64_t n, const uint8_t* pattern, int32_t pattern_bytes, uint32_t* lengths, void* stream);
 extern "C" int comet_launch_strview_copy(const void* views, const uint8_t* ok_bytes, const int32_t* src_offs, const uint8_t* src_bytes, int64_t n, const uint8_t* pattern,
                                          int32_t pattern_bytes, int pad_left, const int32_t* out_offs, uint8_t* out_bytes, void* stream);

@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <set>
@@ -1203,6 +1204,77 @@ std::vector<std::pair<int32_t, int32_t>> regex_prog_find_all(const RegexProg& wh
   std::vector<std::pair<int32_t, int32_t>> out((size_t)count, {-1, -1});
   rx_find_all(w0, wg, s, (int32_t)n, count, [&](int32_t k, int32_t a, int32_t len) { out[(size_t)k] = {a, len}; });
   return out;
+}
+
+// The replacement template by the crate's documented Captures::expand rules: $$ = a literal $, ${N} and $N (the longest run of [0-9A-Za-z_]) = group N,
+// a $ that starts neither = a literal $.  A name that is not a decimal number would be a NAMED group to the crate — the matcher has none: refused.
+static_assert(kRegexReplaceGroups == kRxReplaceGroups, "the executor's program table and the kernels' differ");
+RegexReplace compile_regex_replace(const std::string& pattern, const std::string& rep) {
+  const char* fn = "regexp_replace";
+  RegexReplace out;
+  out.progs.push_back(compile_regex_captures(pattern, 0, fn));
+  if (rep.find('\\') != std::string::npos)
+    throw CometError("regexp_replace replacement '" + rep + "': a backslash in the replacement is not supported by the MI355X native engine (Spark and DataFusion read it differently)");
+  std::vector<int> slots;      // slots[k] = the group whose program is progs[k + 1]
+  std::string lit;
+  auto flush = [&]() {
+    if (lit.empty()) return;
+    out.segs.insert(out.segs.end(), {0u, (uint32_t)out.lits.size(), (uint32_t)lit.size()});
+    out.lits += lit;
+    lit.clear();
+  };
+  auto is_name = [](char c) { return (c >= '0' && c <= '9') || (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || c == '_'; };
+  for (size_t i = 0; i < rep.size();) {
+    if (rep[i] != '$') { lit += rep[i++]; continue; }
+    if (i + 1 < rep.size() && rep[i + 1] == '$') { lit += '$'; i += 2; continue; }
+    std::string name;
+    size_t end = i + 1;
+    if (i + 1 < rep.size() && rep[i + 1] == '{') {
+      const size_t close = rep.find('}', i + 2);
+      if (close == std::string::npos) { lit += '$'; i++; continue; }
+      name = rep.substr(i + 2, close - i - 2);
+      end = close + 1;
+    } else {
+      while (end < rep.size() && is_name(rep[end])) end++;
+      if (end == i + 1) { lit += '$'; i++; continue; }
+      name = rep.substr(i + 1, end - i - 1);
+    }
+    const std::string ref = rep.substr(i, end - i);
+    if (name.empty() || name.find_first_not_of("0123456789") != std::string::npos)
+      throw CometError("regexp_replace replacement '" + rep + "': the reference '" + ref + "' names a group, and named groups are not supported by the MI355X native engine (write ${N} to end a number)");
+    const int group = name.size() > 9 ? 0x7fffffff : atoi(name.c_str());
+    uint32_t slot = 0;
+    if (group != 0) {
+      size_t k = 0;
+      while (k < slots.size() && slots[k] != group) k++;
+      if (k == slots.size()) {
+        RegexProg p = compile_regex_captures(pattern, group, fn);      // (the reference's message for an index out of range)
+        if (slots.size() >= (size_t)kRxReplaceGroups)
+          throw CometError("regexp_replace replacement '" + rep + "' names more than " + std::to_string(kRxReplaceGroups) + " distinct groups: not supported by the MI355X native engine");
+        slots.push_back(group);
+        out.progs.push_back(std::move(p));
+      }
+      slot = (uint32_t)k + 1;
+    }
+    flush();
+    out.segs.insert(out.segs.end(), {1u, slot, 0u});
+    i = end;
+  }
+  flush();
+  return out;
+}
+
+int64_t regex_replace_host(const RegexReplace& r, const uint8_t* s, size_t n, uint8_t* out, int64_t cap) {
+  const uint32_t* progs[kRxReplaceGroups + 1] = {};
+  for (size_t k = 0; k < r.progs.size(); k++) progs[k] = r.progs[k].words.data();
+  const int32_t nseg = (int32_t)(r.segs.size() / 3);
+  // the device's two passes: every length, then the bytes
+  const int64_t len = (int64_t)rx_replace(progs, r.segs.data(), nseg, s, (int32_t)n, [](int32_t, int32_t) {}, [](int32_t, int32_t) {});
+  if (len > cap || !out) return len;
+  uint8_t* o = out;
+  rx_replace(progs, r.segs.data(), nseg, s, (int32_t)n, [&](int32_t a, int32_t m) { memcpy(o, s + a, (size_t)m); o += m; },
+             [&](int32_t a, int32_t m) { memcpy(o, r.lits.data() + a, (size_t)m); o += m; });
+  return len;
 }
 
 bool regex_dfa_match(const RegexDfa& d, const uint8_t* s, size_t n) {

@@ -38,4 +38,17 @@ std::vector<std::pair<int32_t, int32_t>> regex_prog_split(const RegexProg& prog,
 // regexp_extract_all: group spans of every match, by the device's two passes (`whole` = the group-0 program, `group` = the wanted group's or `whole` itself)
 std::vector<std::pair<int32_t, int32_t>> regex_prog_find_all(const RegexProg& whole, const RegexProg& group, const uint8_t* s, size_t n);
 
+// regexp_replace(str, pattern, replacement, 'g') (the crate's Regex::replace_all): the pattern and the replacement template as device/regex_vm.hpp's
+// rx_replace reads them.  Throws by name for what is refused: a backslash or a named reference in the replacement, a group above the pattern's count
+// (regexp_extract's message), more distinct groups ≥ 1 than kRxReplaceGroups, a pattern outside the matcher's subset.
+constexpr int kRegexReplaceGroups = 4;      // device/regex_vm.hpp's kRxReplaceGroups (regex.cpp asserts it)
+struct RegexReplace {
+  std::vector<RegexProg> progs;      // [0] the group-0 program, then one program per distinct group ≥ 1 the template names
+  std::vector<uint32_t> segs;        // three words per segment: 0, first byte in `lits`, byte count | 1, index into `progs`, 0
+  std::string lits;                  // the template's literal bytes
+};
+RegexReplace compile_regex_replace(const std::string& pattern, const std::string& replacement);
+// the device's two passes on the host (tests): → the result's length; its bytes in `out` when they fit `cap`
+int64_t regex_replace_host(const RegexReplace& r, const uint8_t* s, size_t n, uint8_t* out, int64_t cap);
+
 }  // namespace comet

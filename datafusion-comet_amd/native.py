@@ -168,6 +168,8 @@ def _load() -> ctypes.CDLL:
     lib.comet_embedded_header.argtypes = [c.c_char_p, c.c_void_p, c.c_int64]
     lib.comet_plan_set_subquery.restype = c.c_int32
     lib.comet_plan_set_subquery.argtypes = [c.c_int64, c.c_int64, c.c_int32, c.c_char_p, c.c_size_t]
+    lib.comet_regexp_replace_host.restype = c.c_int64
+    lib.comet_regexp_replace_host.argtypes = [c.c_char_p, c.c_char_p, c.c_char_p, c.c_size_t, c.c_void_p, c.c_int64]
     lib.comet_split_host.restype = c.c_int32
     lib.comet_split_host.argtypes = [c.c_char_p, c.c_int32, c.c_char_p, c.c_size_t, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.c_int32]
     lib.comet_date_fn_host.restype = c.c_int32
@@ -1314,6 +1316,17 @@ def split_host(pattern: str, limit: int, value: str):
     if k < 0:
         _raise_last(0)
     return [v[a[i]:a[i] + b[i]].decode() for i in range(k)]
+
+
+def regexp_replace_host(pattern: str, replacement: str, value: str) -> str:
+    """regexp_replace(value, pattern, replacement, 'g') by the device's two passes on the host (comet_regexp_replace_host)"""
+    v, p, r = value.encode(), pattern.encode(), replacement.encode()
+    n = lib().comet_regexp_replace_host(p, r, v, len(v), None, 0)
+    if n < 0:
+        _raise_last(0)
+    buf = ctypes.create_string_buffer(max(n, 1))
+    lib().comet_regexp_replace_host(p, r, v, len(v), buf, n)
+    return buf.raw[:n].decode()
 
 
 def date_fn_host(fn: int, a: int, b: int = 0, c: int = 0):

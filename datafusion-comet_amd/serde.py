@@ -421,6 +421,11 @@ def scalar_func(name: str, args: Sequence[Expr], return_type: Optional[DataType]
     return Expr("scalar_func", list(args), dtype=return_type, value=name, fail_on_error=fail_on_error)
 
 
+def regexp_replace(subject: Expr, pattern: str, replacement: str) -> Expr:
+    """RegExpReplace(subject, pattern, replacement, pos = 1) as the JVM sends it (strings.scala:545-587): ScalarFunc regexp_replace with the flags literal 'g'"""
+    return scalar_func("regexp_replace", [subject, lit(pattern, T_STRING), lit(replacement, T_STRING), lit("g", T_STRING)], T_STRING)
+
+
 def unscaled_value(child: Expr) -> Expr:
     """UnscaledValue(decimal(p <= 18, s)) -> Long, what Spark's DecimalAggregates rule puts under sum / avg of short decimals (decimalExpressions.scala:27-45)."""
     return scalar_func("unscaled_value", [child], T_INT64)

@@ -267,6 +267,11 @@ int32_t comet_extract_all_host(const char* pattern, int32_t group, const uint8_t
  * subset.  Needs no GPU. */
 int32_t comet_split_host(const char* pattern, int32_t limit, const uint8_t* value, size_t value_len, int32_t* starts, int32_t* lens, int32_t cap);
 
+/* regexp_replace(value, pattern, replacement, 'g') (the crate's Regex::replace_all; the replacement by Captures::expand's rules: $$, $N, ${N}) by the
+ * device's two passes (csrc/device/regex_vm.hpp rx_replace) on the host: the result's length, its bytes written when they fit `cap`; -2 and
+ * comet_last_error(0) for a pattern or a replacement the engine refuses.  Needs no GPU. */
+int64_t comet_regexp_replace_host(const char* pattern, const char* replacement, const uint8_t* value, size_t value_len, uint8_t* out, int64_t cap);
+
 /* The calendar functions of the generated kernels (csrc/device/dates.hpp) on the host — diagnostic entry: fn 0 date_part(days, part), 1 isodow, 2 ISO week,
  * 3 date_trunc(days, unit), 4 last_day, 5 next_day(days, weekday Monday = 0), 6 make_date(y, m, d), 7 timestamp_trunc(wall-clock µs, unit).  → 1 and *out,
  * 0 = NULL, -2 and comet_last_error(0).  Needs no GPU. */

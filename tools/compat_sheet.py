@@ -140,6 +140,8 @@ def probes():
         "ScalarSubquery": (S.subquery(1, S.T_INT64), "Subquery{id, datatype}: the value is asked of CometScalarSubquery's static methods (or comet_plan_set_subquery) at the first executePlan and becomes a literal of the kernels"),
         "StringSplit": (f("split", [s, L(",", S.T_STRING), L(-1, S.T_INT32)], S.list_type(S.T_STRING, False)),
                         "under spark.comet.expression.StringSplit.allowIncompatible: of a Utf8 COLUMN with a literal pattern and limit, computed over the chain's source and passed through / exploded; the matcher's pattern subset"),
+        "RegExpReplace": (S.regexp_replace(s, r"(\d+)-(\d+)", "${2}/$1"),
+                          "under spark.comet.expression.RegExpReplace.allowIncompatible (pos = 1, what the JVM sends): of a Utf8 COLUMN with a literal pattern and replacement; the crate's replace_all ($N, ${N}, $$) as a derived Utf8 column (usable as an operand, any length); the matcher's pattern subset"),
         "UnixDate": (S.cast(d, S.T_INT32), "serialized as Cast(date AS int)"), "Days": (S.cast(d, S.T_INT32), "serialized as Cast(date AS int)"),
         "WeekDay": (S.date_part("isodow", d), "datepart('isodow') − 1"), "WeekOfYear": (S.date_part("week", d), "the ISO-8601 week"),
         "LastDay": (f("last_day", [d], S.T_DATE), ""), "DateFromUnixDate": (f("date_from_unix_date", [i32], S.T_DATE), ""),
@@ -280,6 +282,10 @@ def render() -> str:
     w("  fused chain, no kernel-argument slot left beside 24 columns; filter bytes with an unknown version, numHashFunctions outside 1 … 255, no words, 2^31 bits or more, or")
     w("  shorter than their header says fail by name (a literal at `createPlan`, a subquery's value at the first `executePlan`, before anything is launched).")
     w("* `RLike`: patterns outside the byte-exact subset (`\\\\p{..}`, scoped flags, look-around, `\\\\b` under `(?m)`) are refused by name.")
+    w("* `RegExpReplace`: a subject that is not a Utf8 COLUMN of the chain's source, a non-literal or NULL pattern / replacement, flags other than the literal `g`;")
+    w("  in the replacement any backslash (Spark and DataFusion read it differently), a reference that is not a decimal number (`$1a`, `${name}`: named groups),")
+    w("  a group number above the pattern's count (the crate would write nothing there), more than four distinct groups >= 1; patterns outside the matcher's")
+    w("  subset, by the matcher's own messages.  A result column beyond 2 GiB fails the task.")
     w("* `Concat`: of Utf8 columns and literals (at most eight), as an output column.")
     w("* Computed Utf8 values used as operands of further expressions must fit 15 bytes (literals, substring, CASE over those).")
     w("* Window: RANGE frames with value offsets over non-integer keys, MIN / MAX of floats over frames, MIN / MAX over sliding frames wider")
