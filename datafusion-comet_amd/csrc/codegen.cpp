@@ -765,7 +765,39 @@ struct Gen {
       raise_value(cond, code, site, "0");
       return;
     }
-    stmt("if (" + cond + ") atomicOr((unsigned int*)prm.out[" + std::to_string(kOutErr) + "], " + std::to_string(1u << code) + "u);");
+    emit_raise(cond, "atomicOr((unsigned int*)prm.out[" + std::to_string(kOutErr) + "], " + std::to_string(1u << code) + "u);");
+  }
+
+  // A raise lowered inside a branch of If / CaseWhen / coalesce holds only for the rows that reach the branch (Spark and the reference evaluate conditionals
+  // per row, the picked branch alone).  The values of a branch are still computed for every row — branch-free — but its raise statements are held back
+  // (the conditions that pick the branch are generated after it) and written behind the conditional with the branch's guard and-ed into their condition.
+  // Outside a branch (guard_slot < 0) a raise is written where it stands, as ever.
+  struct HeldRaise { int slot; std::string cond, action; };
+  std::vector<HeldRaise> held;
+  int guard_slot = -1, nslots = 0;
+  size_t nheld = 0;      // raises held so far, and uses of a lowering that holds one (never decreases): tells gen() whether a lowering under a guard is bound to it
+  void emit_raise(const std::string& cond, const std::string& action) {
+    if (guard_slot < 0) { stmt("if (" + cond + ") " + action); return; }
+    held.push_back({guard_slot, cond, action});
+    nheld++;
+  }
+  Val gen_in(int slot, const ExprP& ep) {
+    const int outer = guard_slot;
+    guard_slot = slot;
+    struct Restore { int& g; int v; ~Restore() { g = v; } } restore{guard_slot, outer};
+    return gen(ep);
+  }
+  // the branch `slot` is picked where `guard` holds ("false": never): its raises go to the enclosing branch, or into the code
+  void settle(int slot, const std::string& guard) {
+    std::vector<HeldRaise> rest;
+    for (auto& h : held) {
+      if (h.slot != slot) { rest.push_back(h); continue; }
+      if (guard == "false") continue;
+      const std::string cond = "((" + h.cond + ") && " + guard + ")";      // (the raise condition first: it is almost never true, and a guard may be a call)
+      if (guard_slot < 0) stmt("if (" + cond + ") " + h.action);
+      else rest.push_back({guard_slot, cond, h.action});
+    }
+    held.swap(rest);
   }
 
   // the expression whose code is being emitted (innermost last): its QueryContext goes with the errors it raises (planner.rs:302-316, 582-597 —
@@ -788,8 +820,8 @@ struct Gen {
   void raise_value(const std::string& cond, int code, const ErrSite& site, const std::string& lo, const std::string& hi = "0") {
     uses_err = true;
     const std::string eb = "prm.out[" + std::to_string(kOutErr) + "]";
-    stmt("if (" + cond + ") { atomicOr((unsigned int*)" + eb + ", " + std::to_string(1u << code) + "u); comet::err_detail(" + eb + ", " +
-         std::to_string(site_id(site)) + "u, (u64)(" + lo + "), (u64)(" + hi + ")); }");
+    emit_raise(cond, "{ atomicOr((unsigned int*)" + eb + ", " + std::to_string(1u << code) + "u); comet::err_detail(" + eb + ", " +
+               std::to_string(site_id(site)) + "u, (u64)(" + lo + "), (u64)(" + hi + ")); }");
   }
   void raise_value128(const std::string& cond, int code, const ErrSite& site, const Val& x) {
     if (x.rep == Rep::I128) raise_value(cond, code, site, "(u128)(" + x.v + ")", "((u128)(" + x.v + ") >> 64)");
@@ -798,8 +830,8 @@ struct Gen {
   void raise_str(const std::string& cond, int code, const ErrSite& site, const std::string& ptr, const std::string& len) {
     uses_err = true;
     const std::string eb = "prm.out[" + std::to_string(kOutErr) + "]";
-    stmt("if (" + cond + ") { atomicOr((unsigned int*)" + eb + ", " + std::to_string(1u << code) + "u); comet::err_detail_str(" + eb + ", " +
-         std::to_string(site_id(site)) + "u, (const u8*)(" + ptr + "), (i32)(" + len + ")); }");
+    emit_raise(cond, "{ atomicOr((unsigned int*)" + eb + ", " + std::to_string(1u << code) + "u); comet::err_detail_str(" + eb + ", " +
+               std::to_string(site_id(site)) + "u, (const u8*)(" + ptr + "), (i32)(" + len + ")); }");
   }
   static ErrSite out_of_range_site(const DType& to) {      // decimal_overflow_error (common/src/error.rs:769-775): the unscaled value, the target's (p, s)
     ErrSite s;
@@ -1447,8 +1479,8 @@ struct Gen {
       auto raise_with_string = [&](const std::string& cond, int code, const ErrSite& site) {
         uses_err = true;
         const std::string eb = "prm.out[" + std::to_string(kOutErr) + "]";
-        stmt("if (" + cond + ") { atomicOr((unsigned int*)" + eb + ", " + std::to_string(1u << code) + "u); i32 en_; comet::strp ep_ = comet::utf8_bytes(prm.in[" +
-             std::to_string(loc.first) + "], " + loc.second + ", en_); comet::err_detail_str(" + eb + ", " + std::to_string(site_id(site)) + "u, (const u8*)ep_, en_); }");
+        emit_raise(cond, "{ atomicOr((unsigned int*)" + eb + ", " + std::to_string(1u << code) + "u); i32 en_; comet::strp ep_ = comet::utf8_bytes(prm.in[" +
+                   std::to_string(loc.first) + "], " + loc.second + ", en_); comet::err_detail_str(" + eb + ", " + std::to_string(site_id(site)) + "u, (const u8*)ep_, en_); }");
       };
       ErrSite site;
       const bool datetime = err_bit == 10 || err_bit == 13 || err_bit == 14;
@@ -1887,9 +1919,17 @@ struct Gen {
     if (f == "coalesce") {
       // the first non-NULL argument (Spark Coalesce → DataFusion's coalesce): a chain of selects from the last argument backwards
       if (e.children.empty()) throw CometError("coalesce needs at least one argument");
-      Val acc = named(gen(e.children.back()));
-      for (size_t k = e.children.size() - 1; k-- > 0;) {
-        Val a = named(gen(e.children[k]));
+      // (argument k is evaluated where every argument before it is NULL: its raises wait in a slot of their own until those are known)
+      const size_t na = e.children.size();
+      std::vector<int> slots(na, -1);
+      std::vector<std::string> oks(na);
+      for (size_t k = 1; k < na; k++) slots[k] = nslots++;
+      auto arg_k = [&](size_t k) { return named(k ? gen_in(slots[k], e.children[k]) : gen(e.children[k])); };
+      Val acc = arg_k(na - 1);
+      oks[na - 1] = acc.ok;
+      for (size_t k = na - 1; k-- > 0;) {
+        Val a = arg_k(k);
+        oks[k] = a.ok;
         if (a.ok.empty()) { acc = a; continue; }      // never NULL: everything after it is dead
         Val is_set;
         is_set.t = DType::of(TypeId::Bool);
@@ -1898,6 +1938,11 @@ struct Gen {
         Val picked = a;
         picked.ok = "";                                // inside the branch it IS set
         acc = named(select(is_set, picked, acc));
+      }
+      std::string guard;      // behind a never-NULL argument: "false" — the raises of what follows it are dropped, like its value
+      for (size_t k = 1; k < na; k++) {
+        if (guard != "false") guard = oks[k - 1].empty() ? "false" : guard.empty() ? "!" + oks[k - 1] : guard + " && !" + oks[k - 1];
+        settle(slots[k], guard);
       }
       return acc;
     }
@@ -2611,11 +2656,18 @@ struct Gen {
     const Expr& e = *ep;
     std::string key = key_of(ep);
     auto it = cse.find(key);
-    if (it != cse.end()) return it->second;
+    if (it != cse.end()) return it->second;      // (lowered outside every branch: it raised for every row already, or holds no raise at all)
+    // a lowering that holds a raise under a branch's guard serves that branch alone: an unguarded use, or one under another guard, is lowered anew
+    const std::string gkey = guard_slot < 0 ? std::string() : "G" + std::to_string(guard_slot) + "|" + key;
+    if (guard_slot >= 0 && (it = cse.find(gkey)) != cse.end()) {
+      nheld++;      // whatever is being lowered around this use relies on the branch's raise: it is the branch's too
+      return it->second;
+    }
+    const size_t held_before = nheld;
     Val out = gen_uncached(e);
     // keep cheap leaf expressions inline, name everything else once
     if (e.kind != ExprKind::Literal && e.kind != ExprKind::Bound) out = named(out);
-    cse[key] = out;
+    cse[guard_slot >= 0 && nheld != held_before ? gkey : key] = out;
     return out;
   }
 
@@ -2822,23 +2874,49 @@ struct Gen {
       case ExprKind::RLike: return rlike(e);
       case ExprKind::If: {
         if (e.children.size() != 3) throw CometError("If needs three children");
-        return select(named(gen(e.children[0])), named(gen(e.children[1])), named(gen(e.children[2])));
+        // (ELSE, THEN, condition: the order the statements have always been written in; a branch's raises wait for the condition — see emit_raise)
+        const int st = nslots++, sf = nslots++;
+        const Val f = named(gen_in(sf, e.children[2]));
+        const Val t = named(gen_in(st, e.children[1]));
+        const Val c = named(gen(e.children[0]));
+        const std::string picked = "(" + and_ok(c.ok, c.v) + ")";
+        settle(st, picked);
+        settle(sf, "!" + picked);
+        return select(c, t, f);
       }
       case ExprKind::CaseWhen: {
         // planner.rs:677-704 → DataFusion CaseExpr without base expression: the first WHEN that is TRUE (not NULL) picks its
         // THEN; no match → ELSE, or NULL without one.  Lowered to a chain of selects built from the last pair backwards.
         const size_t n = (size_t)e.n_when;
         if (n == 0 || (e.children.size() != 2 * n && e.children.size() != 2 * n + 1)) throw CometError("CaseWhen: when/then lists differ in length");
+        // Evaluated per row like CaseExpr: THEN i where WHEN i is the first TRUE one, WHEN i where none before it was TRUE, ELSE where none was — the
+        // raises of each wait in a slot of their own until the conditions are written (WHEN 0 is evaluated for every row)
+        std::vector<int> then_slot(n), when_slot(n, -1);
+        for (size_t i = 0; i < n; i++) then_slot[i] = nslots++;
+        for (size_t i = 1; i < n; i++) when_slot[i] = nslots++;
+        const int else_slot = nslots++;
         std::vector<Val> thens;
-        for (size_t i = 0; i < n; i++) thens.push_back(named(gen(e.children[n + i])));
+        for (size_t i = 0; i < n; i++) thens.push_back(named(gen_in(then_slot[i], e.children[n + i])));
         Val r;
         if (e.children.size() == 2 * n + 1) {
-          r = named(gen(e.children[2 * n]));
+          r = named(gen_in(else_slot, e.children[2 * n]));
         } else {
           r = thens[0];       // typed NULL: same representation, never valid
           r.ok = "false";
         }
-        for (size_t i = n; i-- > 0;) r = named(select(named(gen(e.children[i])), thens[i], r));
+        std::vector<std::string> picked(n);
+        for (size_t i = n; i-- > 0;) {
+          const Val c = named(i ? gen_in(when_slot[i], e.children[i]) : gen(e.children[i]));
+          picked[i] = "(" + and_ok(c.ok, c.v) + ")";
+          r = named(select(c, thens[i], r));
+        }
+        std::string none_before;      // "!w0 && !w1 && …"
+        for (size_t i = 0; i < n; i++) {
+          if (i) settle(when_slot[i], none_before);
+          settle(then_slot[i], none_before.empty() ? picked[i] : none_before + " && " + picked[i]);
+          none_before += (none_before.empty() ? "!" : " && !") + picked[i];
+        }
+        settle(else_slot, none_before);
         return r;
       }
       case ExprKind::In: {
@@ -4647,6 +4725,7 @@ struct JoinSide {
   int ncols() const { return (int)types.size(); }
   int nlogical() const { return fu ? (int)fu->cols.size() : ncols(); }
   bool filters() const { return fu && !fu->preds.empty(); }
+  std::string keep_call() const { return std::string(row[0] == 'i' ? "bkeep" : "pkeep") + "(prm, " + row + ")"; }      // the row passes the side's fused Filters
   std::function<std::pair<int, std::string>(int)> locate() const {
     const int b = base;
     const std::string r = row;
@@ -4662,8 +4741,12 @@ struct LoweredKeys {
   std::vector<std::string> words;
   explicit LoweredKeys(const JoinSide& s) : g(s.types, s.valid) {
     g.locate = s.locate();
+    // The kernels' branch-free sweeps call these functors on rows the side's fused Filters dropped (whose isnotnull-filtered columns are read without
+    // their validity here): a key's raise holds only where the row passes P::bkeep / P::pkeep.  (Without Filters every row the kernels pass is one of
+    // the side's own, and the raise stands where it always stood.)
+    const int slot = s.filters() ? g.nslots++ : -1;
     for (auto& ke : s.keys) {
-      Val v = g.named(g.gen(ke));
+      Val v = g.named(slot >= 0 ? g.gen_in(slot, ke) : g.gen(ke));
       ok = Gen::and_ok(ok, v.ok);
       switch (v.rep) {
         case Rep::B: words.push_back("(u64)(" + v.v + " ? 1 : 0)"); break;
@@ -4674,6 +4757,7 @@ struct LoweredKeys {
         case Rep::STR: words.push_back(v.v + ".a"); words.push_back(v.v + ".b"); break;
       }
     }
+    if (slot >= 0) g.settle(slot, s.keep_call());
   }
   std::string store_words() const {      // kw[w] = …;
     std::string t;
@@ -4789,11 +4873,30 @@ struct JoinGen {
   }
 
   // the residual condition over the physical schema, NULL = false
-  std::string lower_condition(Gen& g) const {
+  std::string lower_condition(Gen& g, int slot) const {
     std::map<const Expr*, ExprP> m2;
-    Val c = g.gen(substitute(j.join_condition, phys, m2));
+    Val c = g.gen_in(slot, substitute(j.join_condition, phys, m2));
     if (c.rep != Rep::B) throw CometError("join condition must be boolean");
     return Gen::and_ok(c.ok, c.v);
+  }
+  // every key pair equal (NULL never equals)
+  std::string lower_key_equality(Gen& g, int slot) const {
+    std::string eq;
+    for (size_t k = 0; k < j.left_keys.size(); k++) {
+      std::map<const Expr*, ExprP> m2;
+      Val a = g.gen_in(slot, substitute(j.left_keys[k], phys, m2));
+      Val b = g.gen_in(slot, substitute(shift_bound(j.right_keys[k], nl), phys, m2));      // right keys are bound to the right child's schema
+      Val c = g.compare(ExprKind::Eq, a, b);
+      eq = Gen::and_ok(eq, Gen::and_ok(c.ok, c.v));
+    }
+    return eq;
+  }
+  // The reference evaluates the residual condition on key-matched pairs only; the kernels' sweeps also call match / cond on pairs that are none (a lane
+  // without a hit asks about build row 0; rows their side's Filters dropped).  The residual's raises hold where the keys are equal and both rows passed their
+  // Filters.  The keys' own raises are dropped here: every row that reaches a pair went through its side's hash functors, which raise them.
+  void settle_pair_raises(Gen& g, int key_slot, int cond_slot, const std::string& keys_equal) const {
+    g.settle(key_slot, "false");
+    g.settle(cond_slot, keys_equal + (build.filters() ? " && " + build.keep_call() : "") + (probe.filters() ? " && " + probe.keep_call() : ""));
   }
   void write_pair_fn(const char* name, Gen& g, const std::string& value) {
     Val r;
@@ -4807,18 +4910,14 @@ struct JoinGen {
   void write_match() {
     Gen g(ct, cv);
     g.locate = locate_combined();
-    std::string cond;
-    for (size_t k = 0; k < j.left_keys.size(); k++) {
-      std::map<const Expr*, ExprP> m2;
-      Val a = g.gen(substitute(j.left_keys[k], phys, m2));
-      Val b = g.gen(substitute(shift_bound(j.right_keys[k], nl), phys, m2));      // right keys are bound to the right child's schema
-      Val c = g.compare(ExprKind::Eq, a, b);
-      cond = Gen::and_ok(cond, Gen::and_ok(c.ok, c.v));
-    }
+    const int key_slot = g.nslots++, cond_slot = g.nslots++;
+    const std::string keys_equal = lower_key_equality(g, key_slot);
+    std::string cond = keys_equal;
     if (j.join_condition) {
-      cond = Gen::and_ok(cond, lower_condition(g));
+      cond = Gen::and_ok(cond, lower_condition(g, cond_slot));
       ex << "  condition: " << explain_expr(j.join_condition) << "\n";
     }
+    settle_pair_raises(g, key_slot, cond_slot, keys_equal);
     write_pair_fn("match", g, cond);
   }
 
@@ -4831,7 +4930,13 @@ struct JoinGen {
     }
     Gen g(ct, cv);
     g.locate = locate_combined();
-    write_pair_fn("cond", g, lower_condition(g));
+    const int cond_slot = g.nslots++;
+    const std::string cond = lower_condition(g, cond_slot);
+    if (!g.held.empty()) {      // (a residual that can raise asks for the keys again: cond alone does not know whether the pair is one)
+      const int key_slot = g.nslots++;
+      settle_pair_raises(g, key_slot, cond_slot, lower_key_equality(g, key_slot));
+    }
+    write_pair_fn("cond", g, cond);
   }
 
   // output = left columns then right columns (Inner / outer); left columns only (Semi / Anti): types and nullability (a fused column is a computed expression)

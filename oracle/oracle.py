@@ -254,6 +254,25 @@ class Evaluator:
     def _as_dec(self, c: Col) -> np.ndarray:
         return c.values
 
+    def _pick(self, cols, n, parts) -> Col:
+        """Conditionals are evaluated per row (DataFusion's CaseExpr: evaluate_selection over the rows a WHEN picked, the later WHENs over the remainder): each
+        (rows, expression) of `parts` — disjoint sets of rows — is evaluated over ITS rows alone, so that an error a branch would raise for a row that does not
+        reach it is not raised.  Rows in no part are NULL.  The result has the first part's type."""
+        out_t, vals, ok = None, None, np.zeros(n, bool)
+        for rows, ex in parts:
+            idx = np.nonzero(rows)[0]
+            if len(idx) == 0 and out_t is not None:
+                continue
+            c = self.eval(ex, cols, n) if len(idx) == n else self.eval(ex, [_take(x, idx) for x in cols], len(idx))
+            if out_t is None:
+                out_t = c.dtype
+                vals = np.full(n, None, dtype=object) if c.values.dtype == object else np.zeros(n, dtype=c.values.dtype)
+            if len(idx):
+                assert c.values.dtype == vals.dtype, (c.values.dtype, vals.dtype)      # (an assignment would narrow a wider branch silently)
+                vals[idx] = c.values
+                ok[idx] = c.ok()
+        return Col(out_t, vals, None if ok.all() else ok)
+
     def eval(self, e, cols: List[Col], n: int) -> Col:
         S = self.S
         k = e.kind
@@ -379,11 +398,10 @@ class Evaluator:
         if k == "cast":
             return self._cast(e, self.eval(e.children[0], cols, n))
         if k == "if_":
-            c, t, f = (self.eval(x, cols, n) for x in e.children)
+            # IfExpr is a CaseExpr with one WHEN (conditional_funcs/if_expr.rs): each side is evaluated over the rows that pick it, no others
+            c = self.eval(e.children[0], cols, n)
             sel = c.ok() & c.values.astype(bool)
-            vals = np.where(sel, t.values, f.values) if t.dtype.type_id != S.DECIMAL else np.where(sel, t.values, f.values)
-            ok = np.where(sel, t.ok(), f.ok())
-            return Col(t.dtype, vals, None if ok.all() else ok)
+            return self._pick(cols, n, [(sel, e.children[1]), (~sel, e.children[2])])
         if k in ("bit_and", "bit_or", "bit_xor", "shift_left", "shift_right"):
             # Spark BitwiseAnd / Or / Xor, ShiftLeft / ShiftRight with Java semantics (count modulo the value's width, arithmetic >>)
             a, b = self.eval(e.children[0], cols, n), self.eval(e.children[1], cols, n)
@@ -449,19 +467,20 @@ class Evaluator:
             return self._scalar_func(e, cols, n)
         if k == "case_when":
             # planner.rs:677-704 → DataFusion CaseExpr (no base expression): first WHEN that is TRUE wins, else ELSE / NULL
+            # — per row: WHEN i is evaluated over the rows no earlier WHEN picked, THEN i over the rows WHEN i picks, ELSE over what remains
             nw = e.index
-            thens = [self.eval(x, cols, n) for x in e.children[nw:2 * nw]]
+            rest = np.ones(n, bool)
+            parts = []
+            for i in range(nw):
+                idx = np.nonzero(rest)[0]
+                c = self.eval(e.children[i], cols, n) if len(idx) == n else self.eval(e.children[i], [_take(x, idx) for x in cols], len(idx))
+                sel = np.zeros(n, bool)
+                sel[idx] = c.ok() & c.values.astype(bool)
+                parts.append((sel, e.children[nw + i]))
+                rest = rest & ~sel
             if len(e.children) == 2 * nw + 1:
-                r = self.eval(e.children[2 * nw], cols, n)
-                vals, ok = r.values.copy(), r.ok().copy()
-            else:
-                vals, ok = thens[0].values.copy(), np.zeros(n, bool)
-            for i in range(nw - 1, -1, -1):
-                c = self.eval(e.children[i], cols, n)
-                sel = c.ok() & c.values.astype(bool)
-                vals = np.where(sel, thens[i].values, vals)
-                ok = np.where(sel, thens[i].ok(), ok)
-            return Col(thens[0].dtype, vals, None if ok.all() else ok)
+                parts.append((rest, e.children[2 * nw]))
+            return self._pick(cols, n, parts)
         if k == "in_":
             v = self.eval(e.children[0], cols, n)
             hit = np.zeros(n, bool)
@@ -897,15 +916,24 @@ class Evaluator:
                 out[i] = "".join(a.values[i] for a in args) if ok[i] else None
             return Col(S.T_STRING, out, None if ok.all() else ok)
         if f == "coalesce":
-            # the first non-NULL argument
-            args = [self.eval(c, cols, n) for c in e.children]
-            out_vals = args[-1].values.copy()
-            out_ok = args[-1].ok().copy()
-            for a in reversed(args[:-1]):
-                ok = a.ok()
-                out_vals = np.where(ok, a.values, out_vals) if a.values.dtype != object else np.array([x if k else y for x, y, k in zip(a.values, out_vals, ok)], dtype=object)
-                out_ok = ok | out_ok
-            return Col(args[0].dtype, out_vals, None if out_ok.all() else out_ok)
+            # the first non-NULL argument; argument k is evaluated over the rows whose earlier arguments are all NULL (Coalesce → CaseWhen(IsNotNull(c), c …),
+            # serde/conditional.scala:91-126)
+            rest = np.ones(n, bool)
+            out_t, out_vals, out_ok = None, None, np.zeros(n, bool)
+            for c in e.children:
+                idx = np.nonzero(rest)[0]
+                if len(idx) == 0 and out_t is not None:
+                    break
+                a = self.eval(c, cols, n) if len(idx) == n else self.eval(c, [_take(x, idx) for x in cols], len(idx))
+                if out_t is None:
+                    out_t = a.dtype
+                    out_vals = np.full(n, None, dtype=object) if a.values.dtype == object else np.zeros(n, dtype=a.values.dtype)
+                got = idx[a.ok()]
+                assert a.values.dtype == out_vals.dtype, (a.values.dtype, out_vals.dtype)
+                out_vals[got] = a.values[a.ok()]
+                out_ok[got] = True
+                rest[got] = False
+            return Col(out_t, out_vals, None if out_ok.all() else out_ok)
         if f in ("starts_with", "ends_with", "contains"):
             # byte-wise on the UTF-8 encodings (UTF8_BINARY collation; strings.scala:343-360)
             a, lit = self.eval(e.children[0], cols, n), e.children[1].value.encode()

@@ -37,6 +37,9 @@ PLAIN = {
     "tests.test_split_gpu": ["test_what_split_refuses"], "tests.test_strfn_gpu": ["test_refusals"], "tests.test_string_views_gpu": ["test_long_pad_strings_are_refused"],
     # (a Scan with list columns: the element columns are bound behind the real ones, as the executor does)
     "tests.test_list_exprs_gpu": ["test_array_contains", "test_elements_by_position", "test_errors_of_the_reference_and_refusals", "test_size_and_nullness"],
+    # ANSI raises only for the rows Spark evaluates (the joins of that module stay the GPU's)
+    "tests.test_dead_rows_gpu": ["test_a_null_operand_raises_nothing", "test_c_one_expression_under_two_guards",
+                                 "test_c_parent_of_a_guarded_expression_used_bare_raises"],
 }
 PARAMS = [("tests.test_q6_gpu", "test_q6_host_stream_matches_oracle", dict(n=n)) for n in (1, 64, 65, 100_003, 1 << 20)] + \
          [("tests.test_q1_gpu", "test_q1_host_stream_matches_oracle", dict(n=n)) for n in (1, 8192, 200_003)] + \
@@ -50,7 +53,12 @@ PARAMS = [("tests.test_q6_gpu", "test_q6_host_stream_matches_oracle", dict(n=n))
           ("tests.test_string_casts_gpu", "test_string_to_values", dict(mode=1)), ("tests.test_string_casts_gpu", "test_strings_to_timestamps", dict(tz="America/New_York")),
           ("tests.test_string_casts_gpu", "test_strings_to_timestamps", dict(tz="+05:30")),
           ("tests.test_rlike_gpu", "test_projection_and_filter_match_the_oracle", dict(pattern="\\bRose\\b")), ("tests.test_rlike_gpu", "test_projection_and_filter_match_the_oracle", dict(pattern="^[\\w#]+\\d{9}$"))] + \
-         [("tests.test_fuzz_gpu", "test_random_filter_project", dict(seed=s)) for s in (0, 1, 2, 3, 4, 5, 6, 7)]
+         [("tests.test_fuzz_gpu", "test_random_filter_project", dict(seed=s)) for s in (0, 1, 2, 3, 4, 5, 6, 7)] + \
+         [("tests.test_dead_rows_gpu", "test_c_unpicked_branch_raises_nothing", dict(form=f)) for f in
+          ("if_then", "if_else", "case_then", "case_then_with_else", "case_later_when", "case_else", "coalesce_as_case", "coalesce_function", "if_inside_case_then")] + \
+         [("tests.test_dead_rows_gpu", "test_c_one_expression_guarded_and_unguarded_raises_for_the_unguarded_use", dict(guarded_first=g)) for g in (False, True)] + \
+         [("tests.test_dead_rows_gpu", "test_b_rows_a_lower_filter_drops_raise_nothing", dict(name=nm)) for nm in
+          ("filter_project", "filter_filter", "filter_aggregate", "filter_isnotnull_project")]
 
 
 @pytest.mark.parametrize("module,fn", [(m, f) for m, fs in PLAIN.items() for f in fs])

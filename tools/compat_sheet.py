@@ -335,6 +335,18 @@ def render() -> str:
     w("* Everything else on the path — integers, decimals (HALF_UP, overflow → NULL / ANSI error), dates, timestamps, strings, hashes (murmur3 / xxhash64), partition")
     w("  ids, Parquet decode — is bit-exact against the oracle and the reference's own vectors.")
     w("")
+    w("## 6. Which rows an expression is evaluated for (where an ANSI error can come from)")
+    w("")
+    w("* An ANSI error is raised only for a row — or a pair of rows — the reference evaluates.  A NULL operand raises nothing; a row that a Filter lower in the same")
+    w("  fused chain dropped raises nothing, whatever its slots physically hold.")
+    w("* `If`, `CaseWhen` and `Coalesce` (the `CaseWhen(IsNotNull(c), c …)` form the JVM sends, and the `coalesce` scalar function) are lazy per row, as DataFusion's")
+    w("  CaseExpr is: a row evaluates the WHENs up to its first TRUE one, that THEN, or all WHENs and the ELSE; `coalesce` its arguments up to the first that is not")
+    w("  NULL, and nothing behind an argument that is never NULL.  `CASE WHEN y <> 0 THEN x / y END`, `if(y = 0, NULL, x / y)` and `coalesce(a, x / y)` do not raise")
+    w("  for the rows that do not reach the division.  The values of every branch are still computed for every row (branch-free); only the raise is conditional.")
+    w("* `And` / `Or` evaluate both sides for every row, as the reference does (no per-row short circuit): `y <> 0 AND x / y > 1` under ANSI raises for y = 0 on both.")
+    w("* Hash join: key expressions of a fused chain are evaluated for the rows that pass the chain's Filters; the residual condition for key-matched pairs of such")
+    w("  rows (`tests/test_dead_rows_gpu.py`; the oracle is held to the same rule by `tests/test_dead_rows_cpu.py`).")
+    w("")
     return "\n".join(out) + "\n"
 
 
