@@ -271,6 +271,10 @@ ExecutionContext::ExecutionContext(OperatorP plan, uint64_t plan_hash, std::vect
       bloom_agg_spec(op);      // (refuses grouped / mixed / filtered shapes and parameters out of range, by name)
       has_join_ = true;        // runs as an operator over its materialised child
     }
+    if (is_percentile_agg(op)) {
+      percentile_spec(op);     // (refuses mixed aggregates / modes, percentages that are no literal in [0, 1] and too many value columns, by name)
+      has_join_ = true;        // runs as an operator over its materialised child
+    }
     if (op.kind == OpKind::HashAgg && &op != plan_.get()) {
       // an aggregate below other operators: materialised too, unless it is the sink of the root chain (checked below)
       nested_aggs_.push_back(&op);
@@ -356,7 +360,7 @@ ExecutionContext::ExecutionContext(OperatorP plan, uint64_t plan_hash, std::vect
 bool ExecutionContext::is_source(const Operator& op, const Operator* chain_top) {
   switch (op.kind) {
     case OpKind::Explode: case OpKind::Scan: case OpKind::HashJoin: case OpKind::NativeScan: case OpKind::Sort: case OpKind::Limit: case OpKind::ShuffleWriter: case OpKind::Expand: case OpKind::Window: return true;
-    case OpKind::HashAgg: return &op != chain_top || is_bloom_agg(op);
+    case OpKind::HashAgg: return &op != chain_top || is_bloom_agg(op) || is_percentile_agg(op);
     default: return false;
   }
 }
@@ -795,6 +799,7 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
                 std::to_string(spec.version) + ", " + std::to_string(spec.k) + " hash function(s), " + std::to_string(spec.num_words * 64) + " bits\n";
     return {DType::of(TypeId::Bytes)};
   }
+  if (is_percentile_agg(op)) return plan_percentile(op);
   if (op.kind == OpKind::NativeScan) {
     std::vector<DType> out;
     for (auto& f : op.required_schema) out.push_back(f.dtype);
@@ -1735,6 +1740,10 @@ DevTable ExecutionContext::materialize(const Operator& op) {
   if (is_bloom_agg(op)) {
     DevTable in = materialize(*op.children[0]);
     return bloom_aggregate(op, in);
+  }
+  if (is_percentile_agg(op)) {
+    DevTable in = materialize(*op.children[0]);
+    return percentile_aggregate(op, in);
   }
   if (op.kind == OpKind::HashAgg) return nested_aggregate(op);   // an aggregate below other operators
   // Filter / Projection chain: fused over its source

@@ -151,6 +151,22 @@ struct Variant {  // one JIT specialisation of the pipeline (per input-validity 
 struct BloomAggSpec { int version = 1, k = 1; int64_t num_words = 0; };
 BloomAggSpec bloom_agg_spec(const Operator& hash_agg);
 bool is_bloom_agg(const Operator& op);      // a HashAggregate that holds a bloom_filter_agg
+// Spark's exact percentile (exec_percentile.cpp): a HashAggregate all of whose aggregate functions are percentiles runs as an operator over its materialised child
+bool is_percentile_agg(const Operator& op);      // a HashAggregate that holds a percentile
+struct PercentileSpec {
+  std::vector<double> p;                            // per aggregate: its percentage
+  std::vector<int> value_of;                        // per aggregate: its entry of `values`
+  std::vector<std::pair<ExprP, ExprP>> values;      // the distinct (child, FILTER) pairs
+};
+PercentileSpec percentile_spec(const Operator& hash_agg);      // refuses, by name, what this engine does not run
+struct PercentilePlan {
+  PercentileSpec spec;
+  std::vector<DType> key_types;
+  OperatorP proj;                      // Partial: Projection(keys ++ one Float64 column per distinct (child, FILTER)) over a Scan of the child's schema
+  OperatorP key_proj;                  // PartialMerge / Final: Projection(keys) over a Scan of the child's schema (none without keys)
+  std::vector<int> state_col;          // … per aggregate: its state column's index in the child
+  OperatorP sort, key_sort;            // Sort by (keys, value) over (keys, value) rows; the keys alone (group boundaries)
+};
 // The Bloom filters a plan's might_contain expressions probe, resident for the plan's life: uploaded once (device/bloom.hpp's layout), shared with
 // the sub-contexts of nested aggregates.  subquery_nodes: subquery id → the node that became a Literal (resolve_subqueries)
 struct BloomRegistry {
@@ -251,6 +267,9 @@ class ExecutionContext {
   DevTable explode(const Operator& ex, const DevTable& in);
   DevTable window(const Operator& w, const DevTable& in);
   DevTable bloom_aggregate(const Operator& agg, const DevTable& in);      // exec_bloom.cpp
+  std::vector<DType> plan_percentile(const Operator& agg);                 // exec_percentile.cpp (createPlan: derived operators, types)
+  DevTable percentile_aggregate(const Operator& agg, const DevTable& in);
+  DevTable percentile_flatten(const DevTable& in, int state_col, const DevTable& keys);      // a List<Float64> state column → (keys, value) rows
   const void* bloom_buffer(const PipelineDesc::BloomRef& ref);
   void bind_blooms(const PipelineDesc& d, CometKParams& prm);            // might_contain's filters → the kernel-argument slots the pipeline names
   void prepare_dict_keys(DevTable& src);
@@ -356,6 +375,7 @@ class ExecutionContext {
   std::map<const Operator*, ExpandInfo> expand_info_;
   std::map<const Operator*, OperatorP> bloom_proj_;     // bloom_filter_agg (Partial) → the synthetic Projection that evaluates its child into one integer column
   std::shared_ptr<BloomRegistry> blooms_;
+  std::map<const Operator*, PercentilePlan> pct_plans_;   // a percentile HashAggregate → its derived operators
   std::map<const Operator*, OperatorP> explode_proj_;   // Explode → the synthetic Projection of the columns it carries alongside
   std::map<const Operator*, OperatorP> window_psort_, window_osort_;   // Window → synthetic Sorts describing its partition / order keys
   std::map<const Operator*, OperatorP> range_sort_, range_bsort_;   // ShuffleWriter(range) → synthetic Sort over its rows / its boundary rows

@@ -86,6 +86,7 @@ struct QueryContext {
   int32_t sql_text_idx = -1;      // index into the root Operator.sql_text_pool (resolved into sql_text by decode_operator)
 };
 
+// (exec_percentile.cpp same_expr compares two expressions field by field to share a value column: a field added here that bears on the value belongs there too)
 struct Expr {
   ExprKind kind = ExprKind::Unsupported;
   int proto_tag = 0;              // raw oneof tag (for error messages)
@@ -120,6 +121,7 @@ struct Expr {
 // AggExpr.expr_struct oneof tags (expr.proto:143-176)
 enum class AggKind : int { Count = 2, Sum = 3, Min = 4, Max = 5, Avg = 6, First = 7, Last = 8, BitAnd = 9, BitOr = 10, BitXor = 11, Covariance = 12, Variance = 13, Stddev = 14, Correlation = 15,
                            BloomFilter = 16,      // expr.proto:289-299: child = 1, numItems = 2, numBits = 3, datatype = 4, version = 5
+                           Percentile = 18,       // expr.proto:266-271: child = 1, percentage = 2, datatype = 3
                            Unsupported = -1 };
 
 struct AggExpr {
@@ -135,6 +137,7 @@ struct AggExpr {
   bool null_on_divide_by_zero = false;   // Variance / Stddev / Covariance / Correlation
   ExprP bloom_num_items, bloom_num_bits;   // BloomFilter: the two Int64 literals
   int bloom_version = 1;                   // BloomFilter: BloomFilterVersion (0 unspecified → V1, 1 V1, 2 V2)
+  ExprP percentage;                        // Percentile: the Float64 literal in [0, 1]
   uint64_t expr_id = 0;
   bool has_expr_id = false;
   std::shared_ptr<QueryContext> qctx;      // AggExpr.query_context = 90: goes with the aggregate's DecimalSumOverflow (sum_decimal.rs wrap_error_with_context)
@@ -175,6 +178,7 @@ inline const char* agg_name(const AggExpr& a) {
     case AggKind::Max: return "max";
     case AggKind::Avg: return "avg";
     case AggKind::BloomFilter: return "bloom_filter_agg";
+    case AggKind::Percentile: return "percentile";
     default: return nullptr;
   }
 }

@@ -372,7 +372,7 @@ AggExpr decode_agg_expr(Reader r) {
     if (f == 90 || wt != 2) { r.skip(wt); continue; }
     a.proto_tag = f;
     Reader b = r.sub();
-    if (f >= 2 && f <= 16) a.kind = (AggKind)f;      // (9-11: BitAndAgg / BitOrAgg / BitXorAgg{child = 1, datatype = 2}, expr.proto:222-235)
+    if ((f >= 2 && f <= 16) || f == 18) a.kind = (AggKind)f;      // (9-11: BitAndAgg / BitOrAgg / BitXorAgg{child = 1, datatype = 2}, expr.proto:222-235)
     else { a.kind = AggKind::Unsupported; continue; }
     if (f == 16) {
       // BloomFilterAgg{child = 1, numItems = 2, numBits = 3, datatype = 4, version = 5} (expr.proto:289-305)
@@ -384,6 +384,19 @@ AggExpr decode_agg_expr(Reader r) {
         else if (f2 == 3 && wt2 == 2) a.bloom_num_bits = decode_expr(b.sub());
         else if (f2 == 4 && wt2 == 2) a.dtype = decode_datatype(b.sub());
         else if (f2 == 5 && wt2 == 0) a.bloom_version = b.varint() == 2 ? 2 : 1;      // (planner.rs:2884-2889: everything but V2 is V1)
+        else b.skip(wt2);
+      }
+      if (child) a.children.push_back(child);
+      continue;
+    }
+    if (f == 18) {
+      // Percentile{child = 1, percentage = 2, datatype = 3} (expr.proto:266-271)
+      ExprP child;
+      while (!b.done()) {
+        int wt2, f2 = b.tag(wt2);
+        if (f2 == 1 && wt2 == 2) child = decode_expr(b.sub());
+        else if (f2 == 2 && wt2 == 2) a.percentage = decode_expr(b.sub());
+        else if (f2 == 3 && wt2 == 2) a.dtype = decode_datatype(b.sub());
         else b.skip(wt2);
       }
       if (child) a.children.push_back(child);

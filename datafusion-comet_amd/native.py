@@ -1400,3 +1400,18 @@ def spark_bloom_build(values, num_items: int, num_bits: int, version: int = 0) -
     out = ctypes.create_string_buffer(need)
     f(vp, bp, n, num_items, num_bits, version, ctypes.cast(out, ctypes.c_void_p), need)
     return out.raw
+
+
+def spark_percentile_sorted(sorted_values, p: float):
+    """Spark's exact percentile of `sorted_values` (non-NULL floats in ascending order, NaN last) by the device's code on the host
+    (comet_spark_percentile_sorted): the value, None for no values (the aggregate's NULL); ValueError for a p outside [0, 1]"""
+    n = len(sorted_values)
+    arr = (ctypes.c_double * max(n, 1))(*sorted_values)
+    out = ctypes.c_double(0.0)
+    f = lib().comet_spark_percentile_sorted
+    f.restype = ctypes.c_int32
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]
+    rc = f(ctypes.cast(arr, ctypes.c_void_p), n, p, ctypes.byref(out))
+    if rc < 0:
+        raise ValueError(f"percentile: p = {p!r} is outside [0, 1]")
+    return out.value if rc else None

@@ -476,7 +476,7 @@ class AggExpr:
     stats_type: int = 0             # variance | stddev | covariance: SAMPLE (0) or POPULATION (1); bloom_filter: BloomFilterVersion
     null_on_divide_by_zero: bool = True      # variance | stddev | covariance | corr
 
-    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, bit_and=9, bit_or=10, bit_xor=11, covariance=12, variance=13, stddev=14, corr=15, bloom_filter=16)
+    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, bit_and=9, bit_or=10, bit_xor=11, covariance=12, variance=13, stddev=14, corr=15, bloom_filter=16, percentile=18)
 
     def encode(self) -> bytes:
         if self.kind == "count":
@@ -506,6 +506,8 @@ class AggExpr:
             body = b"".join(_f_msg(i + 1, c.encode()) for i, c in enumerate(self.children)) + _f_msg(4, self.dtype.encode())
             if self.stats_type:
                 body += _f_varint(5, self.stats_type)
+        elif self.kind == "percentile":      # Percentile{child=1, percentage=2, datatype=3} (expr.proto:266-271); children = [child, percentage]
+            body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.children[1].encode()) + _f_msg(3, self.dtype.encode())
         else:
             raise ValueError(self.kind)
         out = _f_msg(self.TAGS[self.kind], body)
@@ -558,6 +560,13 @@ def bit_xor_agg(child: Expr, dtype: DataType, filter: Optional[Expr] = None) -> 
 def bloom_filter_agg(child: Expr, num_items: int, num_bits: int, version: int = 0, filter: Optional[Expr] = None) -> AggExpr:
     """bloom_filter_agg(child, numItems, numBits): the two sizes travel as Int64 literals; version: BloomFilterVersion 0 unspecified (V1), 1 V1, 2 V2 (Spark 4.1+)"""
     return AggExpr("bloom_filter", [child, lit(num_items, T_INT64), lit(num_bits, T_INT64)], dtype=T_BINARY, stats_type=version, filter=filter)
+
+
+def percentile(child: Expr, p, filter: Optional[Expr] = None) -> AggExpr:
+    """percentile(child, p) / median / percentile_cont: the child already cast to Float64, p a Float64 literal in [0, 1] (a float, or an Expr to send
+    something else); the state is one List<Float64> of the group's non-NULL values"""
+    pe = p if isinstance(p, Expr) else lit(float(p), T_DOUBLE)
+    return AggExpr("percentile", [child, pe], dtype=T_DOUBLE, filter=filter)
 
 
 SAMPLE, POPULATION = 0, 1      # StatisticsType (expr.proto:178-181)

@@ -240,6 +240,10 @@ int comet_launch_utf8_uniform(const int32_t* offsets, int64_t n, int32_t L, uint
  * planner refuses. */
 int32_t comet_spark_bloom_might_contain(const uint8_t* bytes, size_t len, int64_t value);
 int64_t comet_spark_bloom_build(const int64_t* values, const uint8_t* valid, int64_t n, int64_t num_items, int64_t num_bits, int32_t version, uint8_t* out, int64_t cap);
+/* Spark's exact percentile (csrc/device/percentile.hpp: the pick the kernel runs) on the host — a diagnostic entry, no GPU.  `sorted`: n non-NULL doubles in
+ * ascending order, NaN last; p in [0, 1] → 1 and *out = the percentile (one or two order statistics, interpolated with two rounded products and one rounded sum),
+ * 0 for n = 0 (the aggregate's NULL), -1 for a p outside [0, 1] or missing arguments. */
+int32_t comet_spark_percentile_sorted(const double* sorted, int64_t n, double p, double* out);
 #endif /* COMET_TEST_ABI */
 
 /* ---- scalar subqueries (expr.proto:513-516 Subquery{id, datatype}; native/core/src/execution/expressions/subquery.rs:72-180) ------------------------------

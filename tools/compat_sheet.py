@@ -195,7 +195,9 @@ ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64
                        "StddevSamp": "Float64, not over window frames (exact moments, order independent)", "StddevPop": "Float64, not over window frames (exact moments, order independent)",
                        "CovSample": "Float64, not over window frames (exact moments, order independent)", "CovPopulation": "Float64, not over window frames (exact moments, order independent)",
                        "Corr": "Float64, not over window frames (exact moments, order independent)",
-                       "BloomFilterAggregate": "Byte / Short / Int / Long child, without grouping keys and alone in its HashAggregate (the shape InjectRuntimeFilter plans), Partial / PartialMerge / Final, V1 and V2"}
+                       "BloomFilterAggregate": "Byte / Short / Int / Long child, without grouping keys and alone in its HashAggregate (the shape InjectRuntimeFilter plans), Partial / PartialMerge / Final, V1 and V2",
+                       "Percentile": "alone in its HashAggregate — any number of percentiles, none of another function —, grouped or not, Partial / PartialMerge / Final; Float64 child "
+                                     "(Spark casts it), bit-equal to the reference"}
 
 
 def probe_plan(expr):
@@ -278,6 +280,10 @@ def render() -> str:
     w("  longs only, so such a filter could not be used natively); numItems <= 0, numBits <= 0, numBits that round up to 2^31 bits or more; more than 255 hash functions")
     w("  (numBits / numItems * ln 2 — the cap bounds a kernel's per-row loop, Spark has none).  A merging aggregate fails the task with the reference's messages when a state")
     w("  does not match (`BloomFilter merge: version mismatch`, `num_hash_functions mismatch`, `seed mismatch`, `num_words mismatch`, `truncated bit array`).")
+    w("* `Percentile` (`median`, `percentile`, `percentile_cont`): mixed with other aggregate functions in one HashAggregate, mixed per-expression modes, more than four")
+    w("  distinct value columns (child, FILTER) in one HashAggregate — any number of percentages may share one —, a Float32 / Float64 grouping key, a percentage that is not a")
+    w("  non-NULL Float64 literal, a child that is not Float64 (`SparkPercentile expects Float64 input, got …`); a percentage outside [0, 1] fails with the reference's")
+    w("  `Percentile value must be between 0.0 and 1.0 inclusive, got …`.  2^31 rows or kept values in one partition fail the task.")
     w("* `BloomFilterMightContain`: a filter argument that is neither a Binary literal nor a Binary scalar subquery, a value that is not Int64, more than four probes in one")
     w("  fused chain, no kernel-argument slot left beside 24 columns; filter bytes with an unknown version, numHashFunctions outside 1 … 255, no words, 2^31 bits or more, or")
     w("  shorter than their header says fail by name (a literal at `createPlan`, a subquery's value at the first `executePlan`, before anything is launched).")
