@@ -275,6 +275,10 @@ ExecutionContext::ExecutionContext(OperatorP plan, uint64_t plan_hash, std::vect
       percentile_spec(op);     // (refuses mixed aggregates / modes, percentages that are no literal in [0, 1] and too many value columns, by name)
       has_join_ = true;        // runs as an operator over its materialised child
     }
+    if (!is_percentile_agg(op) && is_collect_agg(op)) {
+      collect_spec(op);        // (refuses other aggregate functions beside a collect, mixed modes, float sets, nested elements and too many value columns, by name)
+      has_join_ = true;        // runs as an operator over its materialised child
+    }
     if (op.kind == OpKind::HashAgg && &op != plan_.get()) {
       // an aggregate below other operators: materialised too, unless it is the sink of the root chain (checked below)
       nested_aggs_.push_back(&op);
@@ -360,7 +364,7 @@ ExecutionContext::ExecutionContext(OperatorP plan, uint64_t plan_hash, std::vect
 bool ExecutionContext::is_source(const Operator& op, const Operator* chain_top) {
   switch (op.kind) {
     case OpKind::Explode: case OpKind::Scan: case OpKind::HashJoin: case OpKind::NativeScan: case OpKind::Sort: case OpKind::Limit: case OpKind::ShuffleWriter: case OpKind::Expand: case OpKind::Window: return true;
-    case OpKind::HashAgg: return &op != chain_top || is_bloom_agg(op) || is_percentile_agg(op);
+    case OpKind::HashAgg: return &op != chain_top || is_bloom_agg(op) || is_percentile_agg(op) || is_collect_agg(op);
     default: return false;
   }
 }
@@ -800,6 +804,7 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
     return {DType::of(TypeId::Bytes)};
   }
   if (is_percentile_agg(op)) return plan_percentile(op);
+  if (is_collect_agg(op)) return plan_collect(op);
   if (op.kind == OpKind::NativeScan) {
     std::vector<DType> out;
     for (auto& f : op.required_schema) out.push_back(f.dtype);
@@ -1744,6 +1749,10 @@ DevTable ExecutionContext::materialize(const Operator& op) {
   if (is_percentile_agg(op)) {
     DevTable in = materialize(*op.children[0]);
     return percentile_aggregate(op, in);
+  }
+  if (is_collect_agg(op)) {
+    DevTable in = materialize(*op.children[0]);
+    return collect_aggregate(op, in);
   }
   if (op.kind == OpKind::HashAgg) return nested_aggregate(op);   // an aggregate below other operators
   // Filter / Projection chain: fused over its source

@@ -159,6 +159,7 @@ struct PercentileSpec {
   std::vector<std::pair<ExprP, ExprP>> values;      // the distinct (child, FILTER) pairs
 };
 PercentileSpec percentile_spec(const Operator& hash_agg);      // refuses, by name, what this engine does not run
+bool same_expr(const ExprP& a, const ExprP& b);      // structural equality of two expressions as far as the plan can tell (exec_percentile.cpp): shares a value column
 struct PercentilePlan {
   PercentileSpec spec;
   std::vector<DType> key_types;
@@ -166,6 +167,26 @@ struct PercentilePlan {
   OperatorP key_proj;                  // PartialMerge / Final: Projection(keys) over a Scan of the child's schema (none without keys)
   std::vector<int> state_col;          // … per aggregate: its state column's index in the child
   OperatorP sort, key_sort;            // Sort by (keys, value) over (keys, value) rows; the keys alone (group boundaries)
+};
+// collect_list / collect_set (exec_collect.cpp): a HashAggregate all of whose aggregate functions are collects runs the same way, for any element type
+bool is_collect_agg(const Operator& op);         // a HashAggregate that holds a collect_list or a collect_set
+struct CollectSpec {
+  struct Value { ExprP child, filter; bool set = false; DType elem; };      // elem: the element type the aggregate's datatype declares
+  std::vector<int> value_of;                        // per aggregate: its entry of `values`
+  std::vector<Value> values;                        // the distinct (function, child, FILTER) triples
+};
+CollectSpec collect_spec(const Operator& hash_agg);      // refuses, by name, what this engine does not run
+struct CollectPlan {
+  CollectSpec spec;
+  std::vector<DType> key_types;
+  std::vector<DType> elem_types;       // per value column (Partial) / per aggregate (merging)
+  OperatorP proj;                      // Partial: Projection(keys ++ per value column its child and, where it has one, its FILTER) over a Scan of the child's schema
+  std::vector<int> val_col, flt_col;   // … per value column: where they stand in the projection's output (flt_col: -1 = no FILTER)
+  OperatorP key_proj;                  // PartialMerge / Final: Projection(keys) over a Scan of the child's schema (none without keys)
+  std::vector<int> state_col;          // … per aggregate: its state column's index in the child
+  // per value column, over its (keys, value) rows: the sort — by the keys alone for a list (stable: arrival order survives), by (keys, value) for a set —,
+  // the keys alone (group boundaries; none without keys) and, for a set, the value alone (its key bytes tell two values apart)
+  std::vector<OperatorP> sort, key_sort, val_sort;
 };
 // The Bloom filters a plan's might_contain expressions probe, resident for the plan's life: uploaded once (device/bloom.hpp's layout), shared with
 // the sub-contexts of nested aggregates.  subquery_nodes: subquery id → the node that became a Literal (resolve_subqueries)
@@ -270,6 +291,12 @@ class ExecutionContext {
   std::vector<DType> plan_percentile(const Operator& agg);                 // exec_percentile.cpp (createPlan: derived operators, types)
   DevTable percentile_aggregate(const Operator& agg, const DevTable& in);
   DevTable percentile_flatten(const DevTable& in, int state_col, const DevTable& keys);      // a List<Float64> state column → (keys, value) rows
+  // group boundaries of a table sorted by its keys (exec_percentile.cpp; both aggregates): first[g] = the first row of group g, first[G] = n; → G.
+  // key_sort: the keys alone (nullptr: no keys, one group); peer_sort + fpeer (both or neither): also, per row, 1 where a new (group, peer key) run starts
+  int64_t group_starts(const Operator* key_sort, const DevTable& sorted, std::shared_ptr<DevBuf>& first, const char* who, const Operator* peer_sort = nullptr, DevBuf* fpeer = nullptr);
+  std::vector<DType> plan_collect(const Operator& agg);                    // exec_collect.cpp
+  DevTable collect_aggregate(const Operator& agg, const DevTable& in);
+  DevTable collect_flatten(const DevTable& in, int state_col, const DType& elem, const DevTable& keys);      // a List<element> state column → (keys, value) rows
   const void* bloom_buffer(const PipelineDesc::BloomRef& ref);
   void bind_blooms(const PipelineDesc& d, CometKParams& prm);            // might_contain's filters → the kernel-argument slots the pipeline names
   void prepare_dict_keys(DevTable& src);
@@ -376,6 +403,7 @@ class ExecutionContext {
   std::map<const Operator*, OperatorP> bloom_proj_;     // bloom_filter_agg (Partial) → the synthetic Projection that evaluates its child into one integer column
   std::shared_ptr<BloomRegistry> blooms_;
   std::map<const Operator*, PercentilePlan> pct_plans_;   // a percentile HashAggregate → its derived operators
+  std::map<const Operator*, CollectPlan> collect_plans_;  // a collect_list / collect_set HashAggregate → its derived operators
   std::map<const Operator*, OperatorP> explode_proj_;   // Explode → the synthetic Projection of the columns it carries alongside
   std::map<const Operator*, OperatorP> window_psort_, window_osort_;   // Window → synthetic Sorts describing its partition / order keys
   std::map<const Operator*, OperatorP> range_sort_, range_bsort_;   // ShuffleWriter(range) → synthetic Sort over its rows / its boundary rows

@@ -19,7 +19,7 @@
 #include "../../include/comet_amd.h"
 
 extern "C" int comet_launch_pct_flatten(const int32_t* offs, const uint8_t* list_valid, const double* elems, const uint8_t* elem_valid, int64_t n, const int32_t* out_offs, int64_t total,
-                                        uint32_t* row_idx, double* vals, uint8_t* ok, void* stream);
+                                        uint32_t* row_idx, double* vals, uint32_t* elem_idx, uint8_t* ok, void* stream);
 extern "C" int comet_launch_pct_offsets(const uint32_t* first, const int32_t* C, int64_t G, int32_t* offs, void* stream);
 extern "C" int comet_launch_pct_compact(const double* vals, const uint8_t* valid_bits, const int32_t* C, int64_t n, double* out, void* stream);
 extern "C" int comet_launch_pct_pick(const double* vals, const uint32_t* first, const int32_t* offs, int64_t G, const double* pcts, int nq, double* out, uint8_t* ok, void* stream);
@@ -46,6 +46,8 @@ bool comparable_kind(ExprKind k) {
     default: return false;
   }
 }
+}  // namespace
+
 bool same_expr(const ExprP& a, const ExprP& b) {
   if (!a || !b) return !a && !b;
   if (!comparable_kind(a->kind) || a->kind != b->kind || a->proto_tag != b->proto_tag || a->children.size() != b->children.size()) return false;
@@ -61,6 +63,8 @@ bool same_expr(const ExprP& a, const ExprP& b) {
     if (!same_expr(a->children[i], b->children[i])) return false;
   return true;
 }
+
+namespace {
 
 // a double the way Rust's `{}` prints it (the shortest digits that read back; "NaN", "inf")
 std::string rust_display(double v) {
@@ -259,7 +263,7 @@ DevTable ExecutionContext::percentile_flatten(const DevTable& in, int sc, const 
   ok->ensure((size_t)total + 16);
   bits->ensure((size_t)((total + 7) / 8) + 16);
   if (comet_launch_pct_flatten((const int32_t*)lv.data, lvalid, (const double*)lv.kids[0].data, evalid, n, (const int32_t*)out_offs.p, total, (uint32_t*)row_idx->p, (double*)vals->p,
-                               (uint8_t*)ok->p, stream_) != 0)
+                               nullptr, (uint8_t*)ok->p, stream_) != 0)
     throw CometError("percentile: launch failed");
   if (total > 0) pq_launch_pack((const uint8_t*)ok->p, (uint8_t*)bits->p, total, stream_);
   DevTable out;
@@ -280,6 +284,55 @@ DevTable ExecutionContext::percentile_flatten(const DevTable& in, int sc, const 
   out.owners.push_back(bits);
   HIP_CHECK(hipStreamSynchronize(stream_));      // counts / offsets / indices go back to their pools
   return out;
+}
+
+// The group boundaries of `sorted`, a table ordered by its grouping keys: the keys' order-preserving bytes as planes (key_sort: a Sort by the keys alone), a flag
+// where a row's bytes differ from the row's before it (window_flags_kernel), the flags' scan, and first[g] = the first row of group g, first[G] = n
+// (window_first_kernel).  Without keys there is one group, whatever the row count; with keys and no rows there is none.  With peer_sort — a Sort by further
+// columns of the same table — fpeer[i] is 1 where row i starts a new run of equal (keys, peer key) bytes.  Shared by the percentile and the collect aggregates.
+int64_t ExecutionContext::group_starts(const Operator* key_sort, const DevTable& sorted, std::shared_ptr<DevBuf>& first, const char* who, const Operator* peer_sort, DevBuf* fpeer_out) {
+  const int64_t n = sorted.rows;
+  const std::string name = who;
+  first = std::make_shared<DevBuf>();
+  if (n == 0 || (!key_sort && !peer_sort)) {
+    // no keys: one group, whatever the row count (Final over no rows: one NULL; Partial: one empty list)
+    first->ensure(16);
+    const uint32_t fl[2] = {0, (uint32_t)n};
+    write_small(first->p, fl, sizeof fl);
+    return key_sort ? 0 : 1;
+  }
+  int Wp = 0, Wo = 0;
+  std::shared_ptr<DevBuf> planes, oplanes;
+  if (key_sort) planes = sort_key_planes(*key_sort, sorted, Wp);
+  if (peer_sort) oplanes = sort_key_planes(*peer_sort, sorted, Wo);
+  DevBuf fpart, fpeer_own, tiles, sp;
+  DevBuf& fpeer = fpeer_out ? *fpeer_out : fpeer_own;
+  fpart.ensure((size_t)n * 4 + 16);
+  fpeer.ensure((size_t)n * 4 + 16);
+  if (comet_launch_window_flags(planes ? (const uint8_t*)planes->p : nullptr, Wp, oplanes ? (const uint8_t*)oplanes->p : nullptr, Wo, n, (uint32_t*)fpart.p, (uint32_t*)fpeer.p, stream_) != 0)
+    throw CometError(name + ": launch failed");
+  int64_t groups = 1;
+  if (!key_sort) {
+    first->ensure(16);
+    const uint32_t fl[2] = {0, (uint32_t)n};
+    write_small(first->p, fl, sizeof fl);
+  } else {
+    tiles.ensure((size_t)((n + 1023) / 1024 + 2) * 8);
+    sp.ensure((size_t)(n + 2) * 4);
+    pq_launch_u32_scan((const uint32_t*)fpart.p, n, (uint64_t*)tiles.p, (int32_t*)sp.p, stream_);
+    int32_t g32 = 0;
+    read_small(&g32, (const char*)sp.p + (size_t)n * 4, 4);
+    if (g32 < 1 || (int64_t)g32 > n) throw CometError("internal: " + name + ": " + std::to_string(g32) + " groups over " + std::to_string(n) + " rows");
+    groups = g32;
+    first->ensure((size_t)(groups + 1) * 4 + 16);
+    // (the peer starts are not wanted: both outputs of window_first_kernel are fed the partition flags and their scan)
+    DevBuf first_peer;
+    first_peer.ensure((size_t)(groups + 1) * 4 + 16);
+    if (comet_launch_window_first((const uint32_t*)fpart.p, (const int32_t*)sp.p, (const uint32_t*)fpart.p, (const int32_t*)sp.p, n, (uint32_t*)first->p, (uint32_t*)first_peer.p, stream_) != 0)
+      throw CometError(name + ": launch failed");
+  }
+  HIP_CHECK(hipStreamSynchronize(stream_));      // planes, flags and sums go back to their pools
+  return groups;
 }
 
 DevTable ExecutionContext::percentile_aggregate(const Operator& op, const DevTable& in) {
@@ -349,40 +402,8 @@ DevTable ExecutionContext::percentile_aggregate(const Operator& op, const DevTab
     tv[v] = DevTable();
     const DeviceColumnView& val = sorted.cols[K];
     if (n > 0 && val.offset != 0) throw CometError("internal: percentile: a sorted column with an Arrow offset");
-    auto first = std::make_shared<DevBuf>();
-    int64_t groups = 0;
-    if (K == 0) {
-      // no keys: one group, whatever the row count (Final over no rows: one NULL; Partial: one empty list)
-      first->ensure(16);
-      const uint32_t fl[2] = {0, (uint32_t)n};
-      write_small(first->p, fl, sizeof fl);
-      groups = 1;
-    } else if (n > 0) {
-      int Wp = 0;
-      auto planes = sort_key_planes(*pl.key_sort, sorted, Wp);
-      DevBuf fpart, fpeer, tiles, sp;
-      fpart.ensure((size_t)n * 4 + 16);
-      fpeer.ensure((size_t)n * 4 + 16);
-      tiles.ensure((size_t)((n + 1023) / 1024 + 2) * 8);
-      sp.ensure((size_t)(n + 2) * 4);
-      if (comet_launch_window_flags((const uint8_t*)planes->p, Wp, nullptr, 0, n, (uint32_t*)fpart.p, (uint32_t*)fpeer.p, stream_) != 0) throw CometError("percentile: launch failed");
-      pq_launch_u32_scan((const uint32_t*)fpart.p, n, (uint64_t*)tiles.p, (int32_t*)sp.p, stream_);
-      int32_t g32 = 0;
-      read_small(&g32, (const char*)sp.p + (size_t)n * 4, 4);
-      if (g32 < 1 || (int64_t)g32 > n) throw CometError("internal: percentile: " + std::to_string(g32) + " groups over " + std::to_string(n) + " rows");
-      groups = g32;
-      first->ensure((size_t)(groups + 1) * 4 + 16);
-      // (no order keys: the peer flags window_flags_kernel wrote equal the partition flags, and so do their scans; the peer starts are not wanted)
-      DevBuf first_peer;
-      first_peer.ensure((size_t)(groups + 1) * 4 + 16);
-      if (comet_launch_window_first((const uint32_t*)fpart.p, (const int32_t*)sp.p, (const uint32_t*)fpeer.p, (const int32_t*)sp.p, n, (uint32_t*)first->p, (uint32_t*)first_peer.p, stream_) != 0)
-        throw CometError("percentile: launch failed");
-      HIP_CHECK(hipStreamSynchronize(stream_));      // planes, flags and sums go back to their pools
-    } else {
-      first->ensure(16);
-      const uint32_t fl[2] = {0, 0};
-      write_small(first->p, fl, sizeof fl);
-    }
+    std::shared_ptr<DevBuf> first;
+    const int64_t groups = group_starts(K ? pl.key_sort.get() : nullptr, sorted, first, "percentile");
     if (G < 0) G = groups;
     else if (G != groups) throw CometError("internal: percentile: the value columns disagree on the number of groups (" + std::to_string(G) + " and " + std::to_string(groups) + ")");
     // kept values before each row (NULLs sort last inside a group: a group's kept values are the head of its run)

@@ -4,7 +4,8 @@
 // values stand before row i (an exclusive scan, C[n] = all of them).
 //   pct_flatten_kernel   PartialMerge / Final: the incoming List<Float64> states as (input row, value) rows, one per element, and one NULL row for an empty or
 //                        NULL list — per OUTPUT row, so a single state that holds every value of a partition (an ungrouped Partial's) is spread over the whole
-//                        grid; consecutive lanes read consecutive elements
+//                        grid; consecutive lanes read consecutive elements.  The collect aggregates (exec_collect.cpp) flatten their List<any type> states with
+//                        it too: they ask for the element's index instead of its value and take the element column by it
 //   pct_offsets_kernel   the List<Float64> state's offsets: offs[g] = kept values before group g (G + 1 entries)
 //   pct_compact_kernel   the state's values: the kept values in sorted order, NULLs squeezed out — lane i reads row i and writes slot C[i], both ascending
 //                        with i, so a wave reads 512 contiguous bytes and writes one contiguous run (a group's NULL tail only shortens the run)
@@ -32,10 +33,12 @@ int grid_for(i64 n) {
 }
 
 // out_offs: the exclusive scan (n + 1 entries) of each state row's output rows — its elements, or one for an empty / NULL list — so it ascends strictly and
-// output row i belongs to the last input row r with out_offs[r] <= i.  ok[i]: there is an element and it is not NULL
+// output row i belongs to the last input row r with out_offs[r] <= i.  ok[i]: there is an element and it is not NULL.  vals (with elems) and elem_idx are
+// optional: the element's value as a double, and its index in the element column — 0 where there is none: the gather that follows reads that slot and ok[i]
+// discards what it read (the caller gathers only from an element column that holds at least one element)
 __global__ __launch_bounds__(256) void pct_flatten_kernel(const i32* __restrict__ offs, const u8* __restrict__ list_valid, const double* __restrict__ elems,
                                                           const u8* __restrict__ elem_valid, i64 n, const i32* __restrict__ out_offs, i64 total, u32* __restrict__ row_idx,
-                                                          double* __restrict__ vals, u8* __restrict__ ok) {
+                                                          double* __restrict__ vals, u32* __restrict__ elem_idx, u8* __restrict__ ok) {
   for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < total; i += (i64)gridDim.x * 256) {
     i64 lo = 0, hi = n - 1;      // out_offs[lo] <= i < out_offs[hi + 1]
     while (lo < hi) {
@@ -50,7 +53,8 @@ __global__ __launch_bounds__(256) void pct_flatten_kernel(const i32* __restrict_
     bool keep = j < len;
     if (keep && elem_valid) keep = (elem_valid[e >> 3] >> (e & 7)) & 1;
     row_idx[i] = (u32)r;
-    vals[i] = keep ? elems[e] : 0.0;
+    if (vals) vals[i] = keep ? elems[e] : 0.0;
+    if (elem_idx) elem_idx[i] = j < len ? (u32)e : 0u;
     ok[i] = keep ? 1 : 0;
   }
 }
@@ -86,9 +90,10 @@ __global__ __launch_bounds__(256) void pct_pick_kernel(const double* __restrict_
 extern "C" {
 
 int comet_launch_pct_flatten(const int32_t* offs, const uint8_t* list_valid, const double* elems, const uint8_t* elem_valid, int64_t n, const int32_t* out_offs, int64_t total,
-                             uint32_t* row_idx, double* vals, uint8_t* ok, void* stream) {
+                             uint32_t* row_idx, double* vals, uint32_t* elem_idx, uint8_t* ok, void* stream) {
   if (n > 0 && total > 0)
-    hipLaunchKernelGGL(pct_flatten_kernel, grid_for(total), 256, 0, (hipStream_t)stream, offs, list_valid, elems, elem_valid, (i64)n, out_offs, (i64)total, row_idx, vals, ok);
+    hipLaunchKernelGGL(pct_flatten_kernel, grid_for(total), 256, 0, (hipStream_t)stream, offs, list_valid, elems, elem_valid, (i64)n, out_offs, (i64)total, row_idx, elems ? vals : nullptr,
+                       elem_idx, ok);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -121,14 +121,16 @@ struct Expr {
 // AggExpr.expr_struct oneof tags (expr.proto:143-176)
 enum class AggKind : int { Count = 2, Sum = 3, Min = 4, Max = 5, Avg = 6, First = 7, Last = 8, BitAnd = 9, BitOr = 10, BitXor = 11, Covariance = 12, Variance = 13, Stddev = 14, Correlation = 15,
                            BloomFilter = 16,      // expr.proto:289-299: child = 1, numItems = 2, numBits = 3, datatype = 4, version = 5
+                           CollectSet = 17,       // expr.proto:307-310: child = 1, datatype = 2 (the result type, List<element>)
                            Percentile = 18,       // expr.proto:266-271: child = 1, percentage = 2, datatype = 3
+                           CollectList = 21,      // expr.proto:312-315: child = 1, datatype = 2
                            Unsupported = -1 };
 
 struct AggExpr {
   AggKind kind = AggKind::Unsupported;
   int proto_tag = 0;
   std::vector<ExprP> children;    // Count.children, the single child, or Covariance / Correlation (child1, child2)
-  DType dtype;                    // Sum/Min/Max/Avg/Variance/Stddev/Covariance/Correlation.datatype (result type)
+  DType dtype;                    // Sum/Min/Max/Avg/Variance/Stddev/Covariance/Correlation/CollectList/CollectSet.datatype (result type)
   DType sum_dtype;                // Avg.sum_datatype
   EvalMode eval_mode = EvalMode::Legacy;
   ExprP filter;                   // AggExpr.filter = 89
@@ -179,6 +181,8 @@ inline const char* agg_name(const AggExpr& a) {
     case AggKind::Avg: return "avg";
     case AggKind::BloomFilter: return "bloom_filter_agg";
     case AggKind::Percentile: return "percentile";
+    case AggKind::CollectSet: return "collect_set";
+    case AggKind::CollectList: return "collect_list";
     default: return nullptr;
   }
 }

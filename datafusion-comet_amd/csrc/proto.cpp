@@ -372,7 +372,7 @@ AggExpr decode_agg_expr(Reader r) {
     if (f == 90 || wt != 2) { r.skip(wt); continue; }
     a.proto_tag = f;
     Reader b = r.sub();
-    if ((f >= 2 && f <= 16) || f == 18) a.kind = (AggKind)f;      // (9-11: BitAndAgg / BitOrAgg / BitXorAgg{child = 1, datatype = 2}, expr.proto:222-235)
+    if ((f >= 2 && f <= 18) || f == 21) a.kind = (AggKind)f;      // (9-11: BitAndAgg / BitOrAgg / BitXorAgg, 17 / 21: CollectSet / CollectList — all {child = 1, datatype = 2}, expr.proto:222-235, 307-315)
     else { a.kind = AggKind::Unsupported; continue; }
     if (f == 16) {
       // BloomFilterAgg{child = 1, numItems = 2, numBits = 3, datatype = 4, version = 5} (expr.proto:289-305)

@@ -466,7 +466,7 @@ def in_(value: Expr, items: Sequence[Expr], negated: bool = False) -> Expr:
 
 @dataclass
 class AggExpr:
-    kind: str                       # count | sum | min | max | avg | first | last
+    kind: str                       # count | sum | min | max | avg | first | last | … (TAGS)
     children: List[Expr]
     dtype: Optional[DataType] = None      # result type
     sum_dtype: Optional[DataType] = None  # avg
@@ -476,7 +476,7 @@ class AggExpr:
     stats_type: int = 0             # variance | stddev | covariance: SAMPLE (0) or POPULATION (1); bloom_filter: BloomFilterVersion
     null_on_divide_by_zero: bool = True      # variance | stddev | covariance | corr
 
-    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, bit_and=9, bit_or=10, bit_xor=11, covariance=12, variance=13, stddev=14, corr=15, bloom_filter=16, percentile=18)
+    TAGS = dict(count=2, sum=3, min=4, max=5, avg=6, first=7, last=8, bit_and=9, bit_or=10, bit_xor=11, covariance=12, variance=13, stddev=14, corr=15, bloom_filter=16, collect_set=17, percentile=18, collect_list=21)
 
     def encode(self) -> bytes:
         if self.kind == "count":
@@ -485,7 +485,7 @@ class AggExpr:
             body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.dtype.encode())
             if self.eval_mode:
                 body += _f_varint(3, self.eval_mode)
-        elif self.kind in ("min", "max", "bit_and", "bit_or", "bit_xor"):      # BitAndAgg / BitOrAgg / BitXorAgg{child=1, datatype=2} (expr.proto:222-235)
+        elif self.kind in ("min", "max", "bit_and", "bit_or", "bit_xor", "collect_list", "collect_set"):      # BitAndAgg / BitOrAgg / BitXorAgg / CollectList / CollectSet{child=1, datatype=2} (expr.proto:222-235, 307-315)
             body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.dtype.encode())
         elif self.kind in ("first", "last"):      # First / Last{child=1, datatype=2, ignore_nulls=3} (expr.proto:210-220)
             body = _f_msg(1, self.children[0].encode()) + _f_msg(2, self.dtype.encode()) + (_f_varint(3, 1) if self.ignore_nulls else b"")
@@ -567,6 +567,17 @@ def percentile(child: Expr, p, filter: Optional[Expr] = None) -> AggExpr:
     something else); the state is one List<Float64> of the group's non-NULL values"""
     pe = p if isinstance(p, Expr) else lit(float(p), T_DOUBLE)
     return AggExpr("percentile", [child, pe], dtype=T_DOUBLE, filter=filter)
+
+
+def collect_list(child: Expr, elem_type: DataType, filter: Optional[Expr] = None) -> AggExpr:
+    """collect_list(child) / array_agg(child): datatype is the result type, ArrayType(element, containsNull = false); state and result are one List<element>
+    of the group's non-NULL values"""
+    return AggExpr("collect_list", [child], dtype=list_type(elem_type, False), filter=filter)
+
+
+def collect_set(child: Expr, elem_type: DataType, filter: Optional[Expr] = None) -> AggExpr:
+    """collect_set(child): as collect_list, one of each distinct value"""
+    return AggExpr("collect_set", [child], dtype=list_type(elem_type, False), filter=filter)
 
 
 SAMPLE, POPULATION = 0, 1      # StatisticsType (expr.proto:178-181)

@@ -197,7 +197,11 @@ ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64
                        "Corr": "Float64, not over window frames (exact moments, order independent)",
                        "BloomFilterAggregate": "Byte / Short / Int / Long child, without grouping keys and alone in its HashAggregate (the shape InjectRuntimeFilter plans), Partial / PartialMerge / Final, V1 and V2",
                        "Percentile": "alone in its HashAggregate — any number of percentiles, none of another function —, grouped or not, Partial / PartialMerge / Final; Float64 child "
-                                     "(Spark casts it), bit-equal to the reference"}
+                                     "(Spark casts it), bit-equal to the reference",
+                       "CollectList": "`collect_list` / `array_agg`; alone in its HashAggregate — any mix of collect_list and collect_set, none of another function —, grouped or not, "
+                                      "Partial / PartialMerge / Final; Boolean, integers, Date, Timestamp, TimestampNTZ, Decimal, Utf8, and Float32 / Float64 copied bit for bit; "
+                                      "elements in arrival order, the same for every batch size (§5)",
+                       "CollectSet": "as CollectList, without Float32 / Float64; elements in ascending order of the engine's sort key (the reference's order is hash order)"}
 
 
 def probe_plan(expr):
@@ -284,6 +288,12 @@ def render() -> str:
     w("  distinct value columns (child, FILTER) in one HashAggregate — any number of percentages may share one —, a Float32 / Float64 grouping key, a percentage that is not a")
     w("  non-NULL Float64 literal, a child that is not Float64 (`SparkPercentile expects Float64 input, got …`); a percentage outside [0, 1] fails with the reference's")
     w("  `Percentile value must be between 0.0 and 1.0 inclusive, got …`.  2^31 rows or kept values in one partition fail the task.")
+    w("* `CollectList` / `CollectSet`: beside any other aggregate function in one HashAggregate (a percentile included), mixed per-expression modes, more than four distinct")
+    w("  value columns (function, child, FILTER) in one HashAggregate, a Float32 / Float64 grouping key, Binary, struct, list and map children, a merging aggregate whose")
+    w("  state column is not a `List` of the element type.  `collect_set` over Float32 / Float64 is refused: whether the reference's set keeps -0.0 beside 0.0 and one NaN")
+    w("  payload beside another cannot be read from its planner (its serde calls the float set incompatible with Spark for NaN anyway); `collect_list` copies floats bit for bit.")
+    w("  2^31 rows or elements in one partition, a Utf8 element column beyond 2 GiB and a `collect_set` sort key wider than the Sort operator's 1000 bytes (Utf8 keys and")
+    w("  values are padded to their longest value) fail the task by name.  `RESPECT NULLS` (Spark 4.2) never reaches the library: the JVM does not send it.")
     w("* `BloomFilterMightContain`: a filter argument that is neither a Binary literal nor a Binary scalar subquery, a value that is not Int64, more than four probes in one")
     w("  fused chain, no kernel-argument slot left beside 24 columns; filter bytes with an unknown version, numHashFunctions outside 1 … 255, no words, 2^31 bits or more, or")
     w("  shorter than their header says fail by name (a literal at `createPlan`, a subquery's value at the first `executePlan`, before anything is launched).")
@@ -336,6 +346,10 @@ def render() -> str:
     w("  Within one native plan the input order is defined — batches in the order `executePlan` pulls them, rows in batch order, behind the chain's Filters and the")
     w("  aggregate's own FILTER — and this implementation is a pure function of that order: the same bits for every batch size, chunking, grid size and table path")
     w("  (`tests/test_first_last_bit_agg_gpu.py`).  Above a join the order is the join's output order, which is unspecified on both sides.")
+    w("* `collect_list` / `collect_set`: the ORDER of the elements is unspecified in the reference (its own SQL tests wrap every result in `sort_array`).  Here it is")
+    w("  defined: a `collect_list`'s elements stand in the plan's input order — Partial: batches in the order pulled, rows in batch order; merging: state rows in input")
+    w("  order, each list's elements in list order —, a `collect_set`'s in ascending order of the engine's sort key (value order; Utf8 by bytes, then length).  Both are the")
+    w("  same bits for every batch size and grid (`tests/test_collect_gpu.py`).  A set's equality is equality of those key bytes, which is value equality for every type it takes.")
     w("* Join and hash-aggregate OUTPUT ORDER is unspecified in the reference (hash-table order per batch); tests compare multisets.  A sort-merge join's output is")
     w("  ordered by its keys only where that order is observable (plan output, Limit, shuffle file).")
     w("* Everything else on the path — integers, decimals (HALF_UP, overflow → NULL / ANSI error), dates, timestamps, strings, hashes (murmur3 / xxhash64), partition")
