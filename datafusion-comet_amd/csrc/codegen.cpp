@@ -3097,6 +3097,10 @@ struct AggLowering {
   std::string pv_code;                     // grouped: per-row limb contributions (pv[j] = …)
   std::string fold_code;                   // grouped: limb words pw[] → canonical contribution val[]
   std::string kfeed_code;                  // grouped: per-row kernel-level updates
+  // grouped min / max of a 128-bit value (comet_device.hpp "wide min / max"): words (L, H, Hseen) at `word`; the row offers x where cond holds
+  struct WideReq { int word; bool mn; std::string cond, x; };
+  std::vector<WideReq> wide_reqs;
+  bool part_records = false;               // grouped: the plan may run partitioned (template C''): a row's record carries lo as well, in a private word no accumulation touches
 
   AggLowering(Gen& gen, bool grp) : g(gen), grouped(grp) {}
 
@@ -3386,7 +3390,31 @@ struct AggLowering {
         break;
       }
       case Prim::MinI128: case Prim::MaxI128: {
-        if (grouped) throw CometError("min/max of a decimal wider than 18 digits is not supported in a grouped GPU aggregate yet");
+        if (grouped) {
+          // high word, then low word: only H = min / max(hi) is accumulated (hi never equals INT64_MIN: |v| < 10^38 < 2^127).  L and Hseen are G_CONT — a slot that is
+          // inserted anywhere starts with Hseen = the sentinel, "L not valid yet"; P::wide_reset and P::wide_tile settle L behind the pass that survived
+          nw += 1;
+          s.nwords = 3;
+          slots[key] = s;
+          const std::string w2 = std::to_string(s.word + 2);
+          const char* lid = mn ? "0xffffffffffffffffull" : "0ull";
+          const char* hid = mn ? imin : imax;
+          init_code += "    a[" + w + "] = " + lid + "; a[" + w1 + "] = " + hid + "; a[" + w2 + "] = " + imax + ";\n";
+          combine_code += "    " + acc_call(mn ? "imin128" : "imax128") + "\n";
+          for (auto* q : {"G_CONT", mn ? "G_IMIN64" : "G_IMAX64", "G_CONT"}) gops.push_back(q);
+          for (auto* q : {lid, hid, imax}) gident.push_back(q);
+          const std::string j = std::to_string(pword(mn ? "G_IMIN64" : "G_IMAX64", hid));
+          pv_code += "        pv[" + j + "] = (" + c + ") ? comet::hi64(" + x + ") : " + hid + ";\n";
+          std::string lo_word = lid;
+          if (part_records) {
+            const std::string jl = std::to_string(pword("G_CONT", "0ull"));
+            pv_code += "        pv[" + jl + "] = (" + c + ") ? comet::lo64(" + x + ") : 0ull;\n";
+            lo_word = "pw[" + jl + "]";
+          }
+          fold_code += "    val[" + w + "] = " + lo_word + "; val[" + w1 + "] = pw[" + j + "]; val[" + w2 + "] = " + imax + ";\n";
+          wide_reqs.push_back({s.word, mn, c, x});
+          break;
+        }
         const std::string fn = mn ? "imin128" : "imax128";
         init_code += mn ? "    a[" + w + "] = ~0ull; a[" + w1 + "] = 0x7fffffffffffffffull;\n" : "    a[" + w + "] = 0; a[" + w1 + "] = 0x8000000000000000ull;\n";
         combine_code += "    " + acc_call(fn) + "\n";
@@ -4436,6 +4464,9 @@ struct AggSink {
     src << "  static constexpr bool PIPELINED = true;\n";
     src << "  struct L {\n" << g.ldecls << "  };\n";
     src << "  static __device__ __forceinline__ void tile_load(const CometKParams& prm, i64 base, i64 n, L& ld) {\n" << kRowInit << g.prefetch_body() << "  }\n";
+    emit_compute_half(src, name, params, tail);
+  }
+  void emit_compute_half(std::ostringstream& src, const char* name, const char* params, const std::string& tail) {
     src << "  static __device__ __forceinline__ void " << name << "(const CometKParams& prm, i64 base, i64 n, L& ld, " << params << ") {\n" << kRowInit << g.laliases
         << g.decls << g.body("", true) << tail;
   }
@@ -4471,6 +4502,29 @@ struct AggSink {
     src << "  static __device__ __forceinline__ void pick(const CometKParams& prm, u64* acc) {\n    const i64 b_ = prm.iarg[" << kRowBaseArg << "];\n" << calls << "  }\n";
   }
 
+  // P::wide_reset: one slot's (L, H, Hseen) triples after a pass — an L gathered under another H is stale.  P::wide_tile: the rows of the chunk once more, the same
+  // per-row code as tile_grouped (Filters, keys, values, FILTER clauses; what only the other aggregates read is dead code here): find the row's group, offer lo where hi == H
+  void emit_wide(std::ostringstream& src) {
+    src << "  static __device__ __forceinline__ void wide_reset(u64* acc) {\n";
+    std::string any, offers, merges;
+    for (auto& rq : al.wide_reqs) {
+      merges += "    comet::wide_offer_lds<" + std::string(rq.mn ? "true" : "false") + ">(acc + " + std::to_string(rq.word) + ", val[" + std::to_string(rq.word + 1) + "], val[" + std::to_string(rq.word) + "]);\n";
+      src << "    comet::wide_reset_words(acc + " << rq.word << ", " << (rq.mn ? "0xffffffffffffffffull" : "0ull") << ");\n";
+      any += (any.empty() ? "(" : " || (") + rq.cond + ")";
+      offers += "      { const bool on_ = s_ != nullptr && (" + rq.cond + "); const i128 v_ = on_ ? (i128)(" + rq.x + ") : (i128)0; comet::wide_offer_wave<" + (rq.mn ? "true" : "false") +
+                ">(on_ ? s_->acc + " + std::to_string(rq.word) + " : nullptr, comet::hi64(v_), comet::lo64(v_)); }\n";
+    }
+    src << "  }\n";
+    // the partitioned merge's second sweep: a record (val) offers its lo to the slot (acc, in LDS) its key found
+    if (al.part_records) src << "  static __device__ __forceinline__ void wide_merge(u64* acc, const u64* val) {\n" << merges << "  }\n";
+    // (every lane reaches the offers, with or without a row: comet::wide_offer_wave reduces over the wave)
+    const std::string tail = "    _Pragma(\"unroll\") for (int r = 0; r < R; r++) {\n      comet::Slot<NK, NW>* s_ = nullptr;\n      if (k[r] && (" + any + ")) {\n        u64 key[NK];\n" + key_code +
+                             "        s_ = comet::table_find<NK, NW>(tbl, cap, key);\n      }\n" + offers + "    }\n  }\n";
+    emit_compute_half(src, "wide_tile", "comet::Slot<NK, NW>* tbl, u64 cap", tail);
+  }
+
+  bool may_run_partitioned(bool materialised_source) const { return d.merges_states || (materialised_source && d.str_key_cols.empty()); }
+
   void emit_grouped(std::ostringstream& src, const GenMaker& make_gen, bool materialised_source) {
     // LDS budget: private copies [GC][NPW][COPIES] + table slots ≈ 20 KiB per block (8 blocks = 32 waves per CU)
     d.NPW = al.npw;
@@ -4500,11 +4554,16 @@ struct AggSink {
     const std::string update = "    _Pragma(\"unroll\") for (int r = 0; r < R; r++) {\n      if (k[r]) {\n        u64 key[NK]; u64 pv[NPW];\n" + key_code + al.pv_code +
                                al.kfeed_code + "        comet::group_update<P>(grp, true, key, pv);\n      }\n    }\n  }\n";
     emit_tile(src, "tile_grouped", "const comet::GroupCtx<P>& grp, u64* kacc", update);
-    const bool picks = !al.pick_reqs.empty();
+    const bool picks = !al.pick_reqs.empty(), wide = !al.wide_reqs.empty();
     if (picks) emit_pick(src, make_gen);
+    if (wide) emit_wide(src);
     src << "  static __device__ __forceinline__ void emit_group(const CometKParams& prm, const u64* key, const u64* acc, i64 pos) {\n"
         << key_emit << fin << "  }\n};\n";
     if (picks) src << "extern \"C\" __global__ __launch_bounds__(256) void k_gpick(const CometKParams prm) { comet::agg_grouped_pick_body<P>(prm); }\n";
+    if (wide) {
+      src << "extern \"C\" __global__ __launch_bounds__(256) void k_gwreset(const CometKParams prm) { comet::agg_grouped_wide_reset_body<P>(prm); }\n";
+      src << "extern \"C\" __global__ __launch_bounds__(256) void k_gwlow(const CometKParams prm) { comet::agg_grouped_wide_low_body<P>(prm); }\n";
+    }
     src << "extern \"C\" __global__ __launch_bounds__(256, COMET_WAVES_GAGG) void k_gagg(const CometKParams prm) { comet::agg_grouped_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_gemit(const CometKParams prm) { comet::agg_grouped_emit_body<P>(prm); }\n";
     src << "extern \"C\" __global__ __launch_bounds__(256) void k_grehash(const CometKParams prm) { comet::agg_grouped_rehash_body<P>(prm); }\n";
@@ -4512,7 +4571,7 @@ struct AggSink {
     // (only where the path can apply — a merging aggregate, or one over a materialised source such as a join's output: a Partial aggregate over a Scan sees chunks
     // of a stream, and its three extra kernels would only lengthen the cold compile: SF100 Q1's plan 497 → 680 ms)
     // (… a Partial aggregate keyed by Utf8 columns is "materialised" only so that long strings can be swapped for row indices — TPC-H Q1's shape: four groups)
-    const bool part_kernels = d.merges_states || (materialised_source && d.str_key_cols.empty());
+    const bool part_kernels = may_run_partitioned(materialised_source);
     if (part_kernels) {
       // a grouped aggregate over one chunk may run partitioned (comet_device.hpp template C''): count / scatter passes over the rows, an LDS merge + emit per partition
       src << "extern \"C\" __global__ __launch_bounds__(256) void k_gphist(const CometKParams prm) { comet::agg_part_pass_body<P, 1>(prm); }\n";
@@ -4521,6 +4580,10 @@ struct AggSink {
     }
     d.kernels = {"k_gagg", "k_gemit", "k_grehash", "k_pack"};
     if (picks) d.kernels.push_back("k_gpick");
+    if (wide) {
+      d.kernels.push_back("k_gwreset");
+      d.kernels.push_back("k_gwlow");
+    }
     if (part_kernels) {
       d.kernels.push_back("k_gphist");
       d.kernels.push_back("k_gpscat");
@@ -4592,6 +4655,7 @@ PipelineDesc generate_pipeline(const Operator& root, const std::vector<bool>& in
   } else {
     AggSink sink(d, g, !f.group_exprs.empty(), ex);
     if (sink.grouped) sink.lower_group_keys(f.group_exprs, dict_id_col);
+    sink.al.part_records = sink.grouped && sink.may_run_partitioned(source_types != nullptr);
     sink.lower_aggregates(f.agg_ins);
     sink.finish(src, make_gen, source_types != nullptr);
   }

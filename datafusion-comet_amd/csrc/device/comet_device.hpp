@@ -2633,6 +2633,112 @@ CDEV void agg_grouped_pick_body(const CometKParams& prm) {
   }
 }
 
+// wide min / max (high word, then low word).  The extreme of a 128-bit value v = (hi signed, lo unsigned) is the lexicographic extreme of the pair, and no memory
+// has an atomic that wide.  A group keeps three words (L, H, Hseen).  Only H = min / max(hi) is accumulated, by the G_IMIN64 / G_IMAX64 word every table of the grouped
+// path already knows how to merge; L and Hseen are G_CONT.  |v| < 10^38 < 2^127, so hi is never INT64_MIN: a slot that is inserted anywhere starts with Hseen =
+// INT64_MIN, "L belongs to no H yet".  Behind the k_gagg pass that survived:
+//   k_gwreset, one lane per slot, plain stores: H != Hseen → L = identity, Hseen = H (H moved in this chunk, or the slot is new: what L held was gathered under another H);
+//   k_gwlow, one lane per row of the chunk: a read-only find of the row's group, and where hi == H an unsigned 64-bit atomic min / max of lo into L.
+// Rows of earlier chunks need no second look: had one of them held the new H, H would not have moved.  No lock, nobody waits for anybody, and min / max commute: the
+// words depend on the multiset of rows alone.  A plan without a wide grouped min / max has neither P::wide_reset nor P::wide_tile: no word, no launch, nothing compiled.
+CDEV void wide_reset_words(u64* w, u64 l_identity) {
+  if (w[1] != w[2]) { w[0] = l_identity; w[2] = w[1]; }
+}
+// the slot of a key that is in the table (every row of a chunk is, behind the pass that kept it); no insert, no store: plain loads.  A rehashed table may hold a
+// key any number of probes from its home, an empty slot ends the search
+template <int NK, int NW>
+CDEV Slot<NK, NW>* table_find(Slot<NK, NW>* tbl, u64 cap, const u64* key) {
+  u64 h = hash_key<NK>(key) & (cap - 1);
+  for (u64 probes = 0; probes < cap; probes++) {
+    Slot<NK, NW>* s = &tbl[h];
+    if (s->state != kSlotReady) return nullptr;
+    bool eq = true;
+#pragma unroll
+    for (int k = 0; k < NK; k++) eq &= (s->key[k] == key[k]);
+    if (eq) return s;
+    h = (h + 1) & (cap - 1);
+  }
+  return nullptr;
+}
+template <bool MN>
+CDEV void wide_atomic(u64* w, u64 lo) {
+  if (MN) __hip_atomic_fetch_min(w, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else __hip_atomic_fetch_max(w, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// w = (L, H, Hseen) of the row's slot, H settled; nullptr: the lane has nothing to offer.  EVERY lane of the wave calls this (the wave operations below read all of
+// them).  Test before the atomic: L only ever improves, so a value that does not beat the L read here beats no later one — on rows in no particular order nearly
+// every lane is done there.  On rows SORTED by the value every row beats what it reads, and with few groups the atomics of all rows queue on a handful of addresses
+// (64 M rows, 5 groups: 17.5 ms, profiles/wide_min_max_bench.md).  So the lanes that are still alive and share a slot send ONE atomic: up to kWideRounds times the first
+// live lane leads, its slot's lanes reduce their lo over the wave and leave.  A leader with fewer than kWideShare lanes behind it says that the wave's rows are spread
+// over many groups: everybody left sends its own atomic, as without this step.  The branches are wave-uniform (ballots), the shuffles outside lane-dependent control flow.
+constexpr int kWideRounds = 8, kWideShare = 4;
+template <bool MN>
+CDEV void wide_offer_wave(u64* w, u64 hi, u64 lo) {
+  bool live = false;
+  if (w != nullptr) {
+    if (w[1] == hi) {
+      const u64 cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      live = MN ? lo < cur : lo > cur;
+    }
+  }
+  const u64 me = (u64)w;
+  for (int round = 0; round < kWideRounds; round++) {
+    const u64 alive = __ballot(live);
+    if (alive == 0) return;
+    const int leader = __ffsll((unsigned long long)alive) - 1;
+    const u32 lead_lo = (u32)__shfl((int)(u32)me, leader, kWave);
+    const u32 lead_hi = (u32)__shfl((int)(u32)(me >> 32), leader, kWave);
+    const bool same = live && me == (((u64)lead_hi << 32) | lead_lo);
+    const u64 sharing = __ballot(same);
+    if (__popcll(sharing) < kWideShare) break;
+    u64 best = same ? lo : (MN ? ~0ull : 0ull);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const u64 o = shfl_xor_u64(best, m);
+      if (MN) best = o < best ? o : best;
+      else best = o > best ? o : best;
+    }
+    if (lane_id() == leader) wide_atomic<MN>(w, best);
+    live = live && !same;
+  }
+  if (live) wide_atomic<MN>(w, lo);
+}
+// The partitioned merge (template C'', one chunk, LDS only) does the same inside k_gpmerge: a record carries (lo, hi) of its row, the first sweep settles H per LDS
+// slot, then every slot's L is reset and the partition's records are swept a second time, each offering its lo where its hi == H
+template <bool MN>
+CDEV void wide_offer_lds(u64* w, u64 hi, u64 lo) {
+  if (w[1] != hi) return;
+  if (MN) __hip_atomic_fetch_min(w, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else __hip_atomic_fetch_max(w, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+template <class P, class = void> struct has_wide { static constexpr bool value = false; };
+template <class P> struct has_wide<P, decltype((void)&P::wide_merge)> { static constexpr bool value = true; };
+// k_gwreset: out[0] = the global table, iarg[0] = its slots
+template <class P>
+CDEV void agg_grouped_wide_reset_body(const CometKParams& prm) {
+  typedef Slot<P::NK, P::NW> S;
+  S* tbl = (S*)prm.out[0];
+  const i64 cap = prm.iarg[0];
+  for (i64 i = (i64)blockIdx.x * kBlock + threadIdx.x; i < cap; i += (i64)gridDim.x * kBlock) {
+    S* sl = tbl + i;
+    if (sl->state == kSlotReady) P::wide_reset(sl->acc);
+  }
+}
+// k_gwlow: in[] / n are the chunk's, the table as for k_gwreset
+template <class P>
+CDEV void agg_grouped_wide_low_body(const CometKParams& prm) {
+  typedef Slot<P::NK, P::NW> S;
+  S* tbl = (S*)prm.out[0];
+  const u64 cap = (u64)prm.iarg[0];
+  const i64 n = prm.n;
+  const i64 tile = (i64)P::R * kBlock;
+  for (i64 base = (i64)blockIdx.x * tile; base < n; base += (i64)gridDim.x * tile) {
+    typename P::L ld;
+    P::tile_load(prm, base, n, ld);
+    P::wide_tile(prm, base, n, ld, tbl, cap);
+  }
+}
+
 template <class P>
 CDEV void agg_part_merge_body(const CometKParams& prm) {
   typedef Slot<P::NK, P::NW> S;
@@ -2664,6 +2770,22 @@ CDEV void agg_part_merge_body(const CometKParams& prm) {
       else if (!fresh) slot_apply<P, __HIP_MEMORY_SCOPE_WORKGROUP>(&gs->acc[0], val);
     }
     __syncthreads();
+    if constexpr (has_wide<P>::value) {      // wide min / max: H is settled, now the low words
+      for (int i = threadIdx.x; i < kCap; i += kBlock)
+        if (s_tbl[i].state == kSlotReady) P::wide_reset(s_tbl[i].acc);
+      __syncthreads();
+      for (u32 r = r0 + threadIdx.x; r < r1; r += kBlock) {
+        const u64* rec = recs + (u64)r * (u64)(P::NK + P::NW);
+        u64 key[P::NK], val[P::NW];
+#pragma unroll
+        for (int k = 0; k < P::NK; k++) key[k] = rec[k];
+#pragma unroll
+        for (int k = 0; k < P::NW; k++) val[k] = rec[P::NK + k];
+        S* gs = table_find<P::NK, P::NW>((S*)s_tbl, (u64)kCap, key);
+        if (gs) P::wide_merge(gs->acc, val);
+      }
+      __syncthreads();
+    }
     // emit: this partition's groups in slot order, ONE atomic for their rows
     u32 before[kPer], ready = 0, run = 0;
 #pragma unroll

@@ -1813,6 +1813,7 @@ DevTable ExecutionContext::nested_aggregate(const Operator& agg) {
   mark("groups emitted");
   input_rows += sub.input_rows;
   part_merges_ += sub.part_merges_;
+  wide_passes_ += sub.wide_passes_;
   sub.collect_timings();
   last_kernel_ms += sub.last_kernel_ms;
   last_kernel_launches += sub.last_kernel_launches;
@@ -2277,6 +2278,7 @@ std::string ExecutionContext::metrics_proto() {
       n.metrics.emplace_back("page_index_rows_pruned", rows_pruned_page_index_);
     }
     if (root && (op.kind == OpKind::HashAgg || part_merges_ > 0)) n.metrics.emplace_back("agg_partitioned_merges", part_merges_);      // merging aggregates run as partition → LDS merge → emit
+    if (root && (op.kind == OpKind::HashAgg || wide_passes_ > 0)) n.metrics.emplace_back("agg_wide_min_max_passes", wide_passes_);      // low-word passes of grouped min / max over wide decimals
     if (op.kind == OpKind::HashJoin && root) {      // (the plan's joins together: the counters are the context's)
       n.metrics.emplace_back("join_build_rows", join_build_rows_);
       n.metrics.emplace_back("join_probe_rows", join_probe_rows_);

@@ -430,6 +430,7 @@ class ExecutionContext {
   bool single_chunk_hint_ = false, part_result_ready_ = false;
   DevTable part_result_;
   int64_t part_merges_ = 0;
+  int64_t wide_passes_ = 0;      // k_gwlow launches (grouped min / max of a decimal wider than 18 digits)
   bool try_partitioned_merge(Variant& v, CometKParams& prm, int64_t n);
   struct DevPending {      // a device batch pulled one ahead of its turn
     std::vector<DeviceColumnView> views;

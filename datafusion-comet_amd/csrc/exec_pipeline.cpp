@@ -232,6 +232,17 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
     }
     fix_attempts_ = 0;
     fix_has_state_ = fix_has_state_ || !d.fix_sums.empty();
+    if (std::find(d.kernels.begin(), d.kernels.end(), std::string("k_gwlow")) != d.kernels.end()) {
+      // min / max of a wide decimal: the pass settled the high words; the low words follow from the chunk's rows (comet_device.hpp "wide min / max").  Like k_gpick
+      // behind the pass that survived and on the table that may have replaced the old one
+      prm.out[0] = group_table_.p;
+      prm.iarg[0] = group_cap_;
+      timed_begin();
+      launch(v, "k_gwreset", (int)std::min<int64_t>((group_cap_ + 255) / 256, 256 * 8), prm);
+      launch(v, "k_gwlow", grid, prm);
+      timed_end();
+      wide_passes_++;
+    }
     if (std::find(d.kernels.begin(), d.kernels.end(), std::string("k_gpick")) != d.kernels.end()) {
       // first / last: the groups whose winning ordinal lies in this chunk take their value from that row (comet_device.hpp "first / last").  Behind the pass
       // that survived — a voided pass went back to the checkpoint, and the table may have been swapped for a larger one — and on the chunk's own stream: the
@@ -506,6 +517,7 @@ bool ExecutionContext::try_partitioned_merge(Variant& v, CometKParams& prm, int6
   part_result_.owners.push_back(v.mod);
   part_result_ready_ = true;
   part_merges_++;
+  if (std::find(d.kernels.begin(), d.kernels.end(), std::string("k_gwlow")) != d.kernels.end()) wide_passes_++;      // (the merge kernel swept the records a second time)
   groups_committed_ = ngroups;
   // (the records and the partition counters go back to the pool with this frame: the merge kernel that read them was waited for by the read-back above, and what
   // outputs_to_table queued behind it touches the output's own buffers only)

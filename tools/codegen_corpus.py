@@ -3,10 +3,11 @@
 source, kernels, output descriptors, fix_sums, R) with every input column's validity off and on, and comet_check_plan's text.  A refused plan is recorded with its
 refusal.  tests/golden/codegen_corpus.json is this tool's output at the commit before the generator was restructured; tests/test_codegen_corpus_cpu.py compares.
 That file is a record of the past and is not rewritten: plans for what the generator has learnt since go into a corpus of their own (--ansi-try-sum →
-tests/golden/ansi_try_sum_codegen.json, compared by tests/test_ansi_try_sum_cpu.py), and an entry whose recorded refusal has been lifted since is RETIRED below:
+tests/golden/ansi_try_sum_codegen.json, compared by tests/test_ansi_try_sum_cpu.py; --wide-min-max → tests/golden/wide_min_max_codegen.json, compared by
+tests/test_wide_min_max_agg_cpu.py), and an entry whose recorded refusal has been lifted since is RETIRED below:
 it is no longer generated, its record is carried over as it stands, and the plan moves into the newer corpus under its new behaviour.
 
-  python tools/codegen_corpus.py [--ansi-try-sum] [--out f.json]      (no COMET_* generator variable set)"""
+  python tools/codegen_corpus.py [--ansi-try-sum | --wide-min-max] [--out f.json]      (no COMET_* generator variable set)"""
 import argparse
 import hashlib
 import json
@@ -65,7 +66,7 @@ def aggregate_kinds():
         "min_f32": (lambda: S.min_(FF, F32), [F32], False),
         "max_f64": (lambda: S.max_(F, F64), [F64], True),
         "min_d12": (lambda: S.min_(DD12, D12), [D12], True),
-        "max_d38": (lambda: S.max_(DD38, D38), [D38], False),                        # grouped: refused
+        "max_d38": (lambda: S.max_(DD38, D38), [D38], False),                        # (grouped: RETIRED below)
         "min_date": (lambda: S.min_(DT, DATE), [DATE], False),
         "var_samp": (lambda: S.variance(F), [F64] * 3, True),
         "var_pop": (lambda: S.variance(F, S.POPULATION), [F64] * 3, False),
@@ -98,11 +99,14 @@ def aggregate_plans(kinds=None):
         for grouped in (False, True):
             g = "grouped" if grouped else "ungrouped"
             keys = [K] if grouped else []
-            yield f"agg/{name}/partial/{g}", S.hash_agg(S.scan(FIELDS), keys, [mk()])
+            plans = [(f"agg/{name}/partial/{g}", S.hash_agg(S.scan(FIELDS), keys, [mk()]))]
             if with_filter:
-                yield f"agg/{name}/partial_filter/{g}", S.hash_agg(S.scan(FIELDS), keys, [filtered(mk())])
-            yield f"agg/{name}/final/{g}", state_plan(mk(), state, grouped, S.FINAL)
-            yield f"agg/{name}/partial_merge/{g}", state_plan(mk(), state, grouped, S.PARTIAL_MERGE)
+                plans.append((f"agg/{name}/partial_filter/{g}", S.hash_agg(S.scan(FIELDS), keys, [filtered(mk())])))
+            plans.append((f"agg/{name}/final/{g}", state_plan(mk(), state, grouped, S.FINAL)))
+            plans.append((f"agg/{name}/partial_merge/{g}", state_plan(mk(), state, grouped, S.PARTIAL_MERGE)))
+            for n, plan in plans:
+                if kinds is not None or n not in retired():
+                    yield n, plan
 
 
 def shared_and_mixed_plans():
@@ -283,6 +287,17 @@ def join_plans():
 RETIRED = {
     "refuse/ansi_integer_sum": ("refused: ANSI/TRY integer sum is not supported in the GPU pipeline yet", "ansi_try_sum_plans: lifted/ansi_integer_sum"),
 }
+# (a table of its own: tests/test_ansi_try_sum_cpu.py pins RETIRED to the entry its pull request retired; retired() is both)
+WIDE_MIN_MAX_REFUSAL = "refused: min/max of a decimal wider than 18 digits is not supported in a grouped GPU aggregate yet"
+RETIRED_WIDE_MIN_MAX = {
+    "agg/max_d38/partial/grouped": (WIDE_MIN_MAX_REFUSAL, "wide_min_max_plans: agg/max_d38/partial/grouped"),
+    "agg/max_d38/partial_merge/grouped": (WIDE_MIN_MAX_REFUSAL, "wide_min_max_plans: agg/max_d38/partial_merge/grouped"),
+    "agg/max_d38/final/grouped": (WIDE_MIN_MAX_REFUSAL, "wide_min_max_plans: agg/max_d38/final/grouped"),
+}
+
+
+def retired() -> dict:
+    return {**RETIRED, **RETIRED_WIDE_MIN_MAX}
 
 
 def ansi_try_sum_plans():
@@ -312,6 +327,20 @@ def ansi_try_sum_plans():
     yield "refuse/unscaled_value_of_a_wide_decimal", S.hash_agg(S.scan([D38]), [], [S.sum_(S.unscaled_value(S.col(0, D38)), I64, S.ANSI)])
     yield "refuse/make_decimal_of_an_int", S.project(S.scan([I32]), [S.make_decimal(S.col(0, I32), 17, 2)])
     yield "refuse/final_try_sum_without_its_flag", S.hash_agg(S.scan([I64, I64]), [], [S.sum_(S.col(0, I64), I64, S.TRY)], S.FINAL)
+
+
+def wide_min_max_plans():
+    """grouped min / max of a decimal wider than 18 digits in every mode (the three RETIRED plans and a min twin), beside other aggregates, and the cast of a narrow
+    decimal whose bound keeps it on the one-word min / max: the corpus of tests/golden/wide_min_max_codegen.json"""
+    kinds = {
+        "max_d38": (lambda: S.max_(DD38, D38), [D38], True),
+        "min_d38": (lambda: S.min_(DD38, D38), [D38], True),
+    }
+    for name, plan in aggregate_plans(kinds):
+        if name.endswith("/grouped"):
+            yield name, plan
+    yield "mixed/max_d38_first_sum_count/grouped", S.hash_agg(S.scan(FIELDS), [K], [S.max_(DD38, D38), S.first_(X, I64), S.sum_(DD38, D38), S.count(DD38), S.min_(DD38, D38)])
+    yield "shortcut/max_cast_d12_as_d22/grouped", S.hash_agg(S.scan(FIELDS), [K], [S.max_(S.cast(DD12, D22), D22)])
 
 
 def all_plans():
@@ -345,7 +374,7 @@ def corpus() -> dict:
     switches = sorted(v for v in os.environ if v.startswith("COMET_") and v != "COMET_JIT_CACHE_DIR")
     assert not switches, f"{switches} set: the corpus records what the generator makes by default"
     out = {name: record(plan) for name, plan in all_plans()}
-    for name, (recorded, _) in RETIRED.items():
+    for name, (recorded, _) in retired().items():
         assert name not in out, name
         out[name] = {"check": recorded, "valid_off": recorded, "valid_on": recorded}
     return out
@@ -355,12 +384,18 @@ def ansi_try_sum_corpus() -> dict:
     return {name: record(plan) for name, plan in ansi_try_sum_plans()}
 
 
+def wide_min_max_corpus() -> dict:
+    return {name: record(plan) for name, plan in wide_min_max_plans()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--ansi-try-sum", action="store_true", help="the corpus of tests/golden/ansi_try_sum_codegen.json instead")
+    ap.add_argument("--wide-min-max", action="store_true", help="the corpus of tests/golden/wide_min_max_codegen.json instead")
     a = ap.parse_args()
-    text = json.dumps(ansi_try_sum_corpus() if a.ansi_try_sum else corpus(), indent=0, sort_keys=True) + "\n"
+    made = ansi_try_sum_corpus() if a.ansi_try_sum else wide_min_max_corpus() if a.wide_min_max else corpus()
+    text = json.dumps(made, indent=0, sort_keys=True) + "\n"
     if a.out:
         with open(a.out, "w") as f:
             f.write(text)

@@ -186,8 +186,8 @@ def probes():
 
 ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64 / Float32 (exact, order independent; over window frames too)",
                        "Average": "decimals and Float64 / Float32, in aggregates and over window frames", "Count": "",
-                       "Min": "not decimal(>18) in grouped aggregates; over window frames integers, decimals, dates and timestamps (not floats)",
-                       "Max": "not decimal(>18) in grouped aggregates; over window frames integers, decimals, dates and timestamps (not floats)", "First": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
+                       "Min": "over window frames integers, decimals, dates and timestamps (not floats)",
+                       "Max": "over window frames integers, decimals, dates and timestamps (not floats)", "First": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
                        "Last": "Boolean, integers, floats, Date, Timestamp, Decimal; in HashAggregate and over window frames",
                        "BitAndAgg": "Byte / Short / Int / Long, not over window frames", "BitOrAgg": "Byte / Short / Int / Long, not over window frames",
                        "BitXorAgg": "Byte / Short / Int / Long, not over window frames",
@@ -273,7 +273,7 @@ def render() -> str:
     w("")
     w("* `Cast`: timestamp -> float / decimal / boolean, binary, casts of a COMPUTED string; a cast to string is an output column (not an operand); on a")
     w("  device-resident input ANY type mismatch with the declared Scan fields.  Time zones come from the system's database ($TZDIR, /usr/share/zoneinfo).")
-    w("* `Min` / `Max` of decimal(> 18) in grouped aggregates; more than eight Float64 sums / averages in one aggregate (a variance or stddev takes two,")
+    w("* More than eight Float64 sums / averages in one aggregate (a variance or stddev takes two,")
     w("  a covariance three, a corr five; in a Partial aggregate functions over the same columns share theirs); statistical aggregates over window frames.")
     w("* `Sum` of integers under ANSI / TRY (`try_sum`): where the positive addends of a group sum beyond 2^63 − 1 or the negative ones below −2^63 while the total fits,")
     w("  the reference's answer depends on the row order; the task fails with \"… sum overflow cannot be decided order-independently …\" (as a decimal sum with mixed")
