@@ -28,6 +28,7 @@ extern const char* const kEmbeddedRegexVmHeader;
 namespace comet_strfn_host_ns {
 #include "device/strfn.hpp"
 }
+#include "device/list_fn.hpp"      // (array_sort / array_distinct's per-element code, as the host sees it: comet_list_fn_host below)
 #include "row_shuffle.hpp"
 #include "tz.hpp"
 
@@ -725,6 +726,24 @@ int64_t comet_strfn_host(int32_t op, const uint8_t* value, int32_t n, const uint
     const int64_t len = sf_len(op, value, n, a, na, b, nb, k);
     if (len <= cap && out) sf_write(op, value, n, a, na, b, nb, k, out);
     return len;
+  });
+}
+
+int32_t comet_list_fn_host(int32_t kind, const void* data, const uint8_t* aux, const uint8_t* valid, int64_t n, int32_t op, int32_t flags, uint32_t* out) {
+  return guarded(nullptr, (int32_t)-2, [&]() -> int32_t {
+    if (kind != LF_BOOL && kind != LF_I8 && kind != LF_I16 && kind != LF_I32 && kind != LF_I64 && kind != LF_I128 && kind != LF_STR) throw CometError("comet_list_fn_host: unknown element kind");
+    if ((op != LF_OP_SORT && op != LF_OP_DISTINCT) || n < 0 || (n > 0 && (!data || !out))) throw CometError("comet_list_fn_host: bad arguments");
+    LfCol col;
+    col.data = data;
+    col.aux = aux;
+    col.valid = valid;
+    col.offset = 0;
+    col.kind = kind;
+    for (int64_t e = 0; e < n; e++) {
+      if (op == LF_OP_SORT) out[lf_rank(col, 0, n, e, flags)] = (uint32_t)e;
+      else out[e] = lf_keep(col, 0, e) ? 1u : 0u;
+    }
+    return 0;
   });
 }
 

@@ -384,6 +384,72 @@ ExprP lower_regexp_replace(const ExprP& e) {
   b->has_dtype = true;
   return b;
 }
+// array_sort(arr, 'ASC' | 'DESC', 'NULLS FIRST' | 'NULLS LAST') and array_distinct(arr) (serde/arrays.scala: what Spark's SortArray and ArrayDistinct are sent as):
+// a derived list column of kind 4 — the executor orders / de-duplicates each list's element row numbers (device/list_fn.hpp) and takes the element column by them.
+// The argument is a list column of the chain's source or an earlier derived list (split, regexp_extract_all, another of these): g_derived is ordered, so a
+// derived column may read one before it.
+bool is_list_fn(const std::string& f) { return f == "array_sort" || f == "array_distinct"; }
+// the element types the list functions order and compare; the rest is refused by name
+void check_list_fn_elem(const std::string& f, const DType& t, bool allow_str) {
+  switch (t.id) {
+    case TypeId::Bool: case TypeId::Int8: case TypeId::Int16: case TypeId::Int32: case TypeId::Int64: case TypeId::Date: case TypeId::Timestamp: case TypeId::TimestampNtz: case TypeId::Decimal:
+      return;
+    case TypeId::String:
+      if (allow_str) return;
+      throw CometError(f + " over Utf8 elements is not supported by the MI355X native engine yet (sort_array(x)[0] serves array_min)");
+    case TypeId::Float: case TypeId::Double:
+      throw CometError(f + " over " + t.str() + " elements is not supported by the MI355X native engine (Spark and the reference disagree on signed zeros there)");
+    case TypeId::Bytes: throw CometError(f + " over Binary elements is not supported by the MI355X native engine yet");
+    default: throw CometError(f + " over " + t.str() + " elements is not supported by the MI355X native engine yet");
+  }
+}
+ExprP lower_list_fn(const ExprP& e) {
+  const std::string& f = e->func;
+  const bool sort = f == "array_sort";
+  // (a join folds its sides' chains only to fuse them and materialises a side whose fold throws, so there this wording never reaches a user: the side's
+  // Projection runs as a chain of its own, list function and all; an aggregate's own chain is refused in append_derived_columns)
+  if (!g_derived || !g_source_cols)
+    throw CometError(f + " inside a join's or an aggregate's fused chain is not supported by the MI355X native engine yet (a derived list is computed over the source of a Projection / Filter chain)");
+  if (e->children.size() != (sort ? 3u : 1u)) throw CometError(f + " expects " + (sort ? "3 arguments (array, 'ASC' | 'DESC', 'NULLS FIRST' | 'NULLS LAST')" : "one argument") + ", got " + std::to_string(e->children.size()));
+  const ExprP& subject = e->children[0];
+  const int nsrc = (int)g_source_cols->size();
+  if (subject->has_dtype && subject->dtype.id == TypeId::Map) throw CometError(f + " of a map is not supported by the MI355X native engine");
+  bool ok = subject->kind == ExprKind::Bound && subject->has_dtype && subject->dtype.id == TypeId::List && subject->dtype.kids.size() == 1 && subject->bound_index >= 0;
+  if (ok && subject->bound_index >= nsrc) {      // … a derived list: the index of one's first column
+    ok = false;
+    for (size_t k = 0; k < g_derived->size(); k++) ok |= (*g_derived)[k].kind != 3 && derived_index(nsrc, k) == subject->bound_index;
+  }
+  if (!ok) throw CometError(f + " is supported over a list COLUMN of the source or a derived list (split, array_sort …), not over a computed array, by the MI355X native engine");
+  check_list_fn_elem(f, subject->dtype.kids[0], true);
+  DerivedCol dc;
+  dc.kind = 4;
+  dc.op = sort ? 0 : 1;      // (device/list_fn.hpp LF_OP_SORT / LF_OP_DISTINCT)
+  dc.src = subject->bound_index;
+  if (sort) {
+    auto word = [&](size_t i, const char* a, const char* b) -> bool {
+      const ExprP& x = e->children[i];
+      if (x->kind != ExprKind::Literal || x->lit_null || x->dtype.id != TypeId::String || (x->lit_bytes != a && x->lit_bytes != b))
+        throw CometError(std::string("array_sort: argument ") + std::to_string(i + 1) + " must be the literal '" + a + "' or '" + b + "'");
+      return x->lit_bytes == b;
+    };
+    dc.arg_k = (word(1, "ASC", "DESC") ? 1 : 0) | (word(2, "NULLS FIRST", "NULLS LAST") ? 2 : 0);      // (LF_DESC | LF_NULLS_LAST)
+  }
+  dc.type = subject->dtype;
+  dc.type.virt_parent = dc.type.virt_kid = -1;
+  size_t k = 0;
+  for (; k < g_derived->size(); k++) {
+    const DerivedCol& o = (*g_derived)[k];
+    if (o.kind == 4 && o.src == dc.src && o.op == dc.op && o.arg_k == dc.arg_k) break;
+  }
+  if (k == g_derived->size()) g_derived->push_back(dc);
+  auto b = std::make_shared<Expr>();
+  b->kind = ExprKind::Bound;
+  b->proto_tag = 3;
+  b->bound_index = derived_index(nsrc, k);
+  b->dtype = dc.type;
+  b->has_dtype = true;
+  return b;
+}
 ExprP lower_struct_field(const ExprP& e, const ExprP& child) {
   if (child->kind != ExprKind::Bound || !child->has_dtype || child->dtype.id != TypeId::Struct)
     throw CometError("GetStructField of anything but a struct COLUMN is not supported yet");
@@ -412,6 +478,10 @@ ExprP substitute(const ExprP& e, const std::vector<ExprP>& cols, std::map<const 
     auto n = std::make_shared<Expr>(*e);
     for (auto& c : n->children) c = substitute(c, cols, memo);
     out = lower_regexp_replace(n);
+  } else if (e->kind == ExprKind::ScalarFunc && is_list_fn(e->func)) {
+    auto n = std::make_shared<Expr>(*e);
+    for (auto& c : n->children) c = substitute(c, cols, memo);
+    out = lower_list_fn(n);
   } else if (e->kind == ExprKind::Bound) {
     if (e->bound_index < 0 || (size_t)e->bound_index >= cols.size())
       throw CometError("Column index " + std::to_string(e->bound_index) + " is out of bound. Schema has " +
@@ -2223,6 +2293,59 @@ struct Gen {
       r.ok = ok;
       return r;
     }
+    if (f == "array_min" || f == "array_max") {
+      // Spark's ArrayMin / ArrayMax: the least / greatest non-NULL element; NULL for a NULL list, an empty list and a list of NULL elements only
+      if (e.children.size() != 1) throw CometError(f + " expects one argument");
+      if (e.children[0]->has_dtype && e.children[0]->dtype.id == TypeId::Map) throw CometError(f + " of a map is not supported by the MI355X native engine");
+      ListRef l = list_ref(e.children[0], f.c_str(), true);
+      check_list_fn_elem(f, l.etype, false);
+      r.t = l.etype;
+      r.t.virt_parent = r.t.virt_kid = -1;
+      r.rep = rep_for_type(r.t);
+      r.maxabs = type_maxabs(r.t);
+      const std::string j = newvar("i32"), has = newvar("bool"), best = newvar(rep_ctype(r.rep));
+      const std::string row = "(i64)" + l.off + " + " + j;
+      const std::string ev = in_valid[(size_t)l.elem] ? "comet::ld_valid(" + l.ecol + ", " + row + ")" : "true";
+      stmt(has + " = false; " + best + " = (" + rep_ctype(r.rep) + ")0; if (" + (l.ok.empty() ? "true" : l.ok) + ") for (" + j + " = 0; " + j + " < " + l.len + "; " + j + "++) { if (!" + ev +
+           ") continue; const " + rep_ctype(r.rep) + " ev_ = " + load_of(l.etype, l.ecol, row) + "; if (!" + has + " || ev_ " + (f == "array_min" ? "<" : ">") + " " + best + ") { " + best + " = ev_; " + has +
+           " = true; } }");
+      r.v = best;
+      r.ok = has;
+      return r;
+    }
+    if (f == "spark_array_position") {
+      // array_funcs/array_position.rs (Spark's ArrayPosition): the one-based position of the first non-NULL element equal to the key, 0 when there is none,
+      // NULL for a NULL list or key.  Keys as array_contains takes them
+      if (e.children.size() != 2) throw CometError("spark_array_position expects two arguments");
+      if (e.children[0]->has_dtype && e.children[0]->dtype.id == TypeId::Map) throw CometError("spark_array_position of a map is not supported by the MI355X native engine");
+      ListRef l = list_ref(e.children[0], "spark_array_position", true);
+      check_list_fn_elem("spark_array_position", l.etype, true);
+      std::string keyok, cmp;
+      const std::string j = newvar("i32");
+      const std::string row = "(i64)" + l.off + " + " + j;
+      if (l.etype.id == TypeId::String) {
+        if (!is_str_lit(e.children[1]) && !(e.children[1]->kind == ExprKind::Literal && e.children[1]->lit_null)) throw CometError("spark_array_position over a list of strings is supported with a literal key");
+        if (e.children[1]->lit_null) keyok = "false";
+        cmp = "comet::utf8_eq_lit(" + l.ecol + ", " + row + ", " + c_bytes(e.children[1]->lit_bytes) + ", " + std::to_string(e.children[1]->lit_bytes.size()) + ")";
+      } else {
+        Val key = named(gen(e.children[1]));
+        DType kt = key.t, et = l.etype;
+        kt.virt_parent = kt.virt_kid = et.virt_parent = et.virt_kid = -1;
+        if (!(kt == et)) throw CometError("spark_array_position: the key's type " + key.t.str() + " is not the elements' " + l.etype.str());
+        keyok = key.ok;
+        cmp = "(" + load_of(l.etype, l.ecol, row) + " == " + key.v + ")";
+      }
+      const std::string pos = newvar("i64");
+      const std::string ev = in_valid[(size_t)l.elem] ? "comet::ld_valid(" + l.ecol + ", " + row + ")" : "true";
+      const std::string both = and_ok(l.ok, keyok);
+      stmt(pos + " = 0; if (" + (both.empty() ? "true" : both) + ") for (" + j + " = 0; " + j + " < " + l.len + "; " + j + "++) if (" + ev + " && " + cmp + ") { " + pos + " = (i64)" + j + " + 1; break; }");
+      r.t = DType::of(TypeId::Int64);
+      r.rep = Rep::I64;
+      r.maxabs = (u128)1 << 31;
+      r.v = pos;
+      r.ok = both;
+      return r;
+    }
     // ---- Float64 functions the reference hands to DataFusion / datafusion-spark (QueryPlanSerde.scala:117-174 CometScalarFunction(name); Spark casts the
     // argument to double): the device's libm (ocml) stands where Rust's std — the platform's libm — stands in the reference; both are within an
     // ulp or two of the exact value, the GPU tests state the tolerance.  cot = 1 / tan, csc = 1 / sin, sec = 1 / cos (datafusion-spark), degrees /
@@ -3570,14 +3693,21 @@ std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool
   std::vector<bool> valid_all = in_has_validity;
   for (auto& dc : d.derived) {
     d.in_types.push_back(dc.type);
-    valid_all.push_back(in_has_validity[(size_t)dc.src]);
+    valid_all.push_back(valid_all.at((size_t)dc.src));      // (a kind 4 column's source may be a derived column before it)
     if (dc.kind == 3) continue;
+    bool elem_valid = false;      // split's pieces are never NULL; a sorted / distinct list's elements are NULL where its source's are
+    if (dc.kind == 4)
+      for (size_t j = 0; j + 1 < d.in_types.size(); j++)
+        if (d.in_types[j].virt_parent == dc.src && d.in_types[j].virt_kid == 0) elem_valid = valid_all[j];
     DType et = dc.type.kids[0];      // … and its element column behind it, addressable like the element column of a source list (list_ref)
     et.virt_parent = (int)d.in_types.size() - 1;
     et.virt_kid = 0;
     d.in_types.push_back(et);
-    valid_all.push_back(false);
+    valid_all.push_back(elem_valid);
   }
+  for (auto& dc : d.derived)
+    if (dc.kind == 4 && under_agg)
+      throw CometError(std::string(dc.op == 0 ? "array_sort" : "array_distinct") + " inside an aggregate's chain is not supported by the MI355X native engine yet (project it below the aggregate)");
   if (!d.derived.empty() && under_agg) throw CometError("split inside an aggregate's chain is not supported by the MI355X native engine yet");
   if (d.in_types.size() > COMET_MAX_IN) throw CometError("too many scan columns for one GPU pipeline");
   return valid_all;

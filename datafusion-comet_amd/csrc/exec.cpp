@@ -1512,12 +1512,175 @@ void ExecutionContext::extend_derived_strfn(DevTable& in, const DerivedCol& dc) 
   strfn_rows_ += rows;
 }
 
+// A derived list column of kind 4: array_sort / array_distinct of a list column of the extended table — a source list, a collect's result, or an earlier
+// derived list (device/list_fn.hpp, list_kernels.hip).  The kernels answer with element row numbers; one take_column of the element column by them gives
+// values, validity and Utf8 bytes.  sort: the list keeps the source's offsets and validity, only the element column is new.  distinct: keep flags, their
+// scan, new offsets = the scan read at the old offsets.  Every producer of a list column in this engine — a Scan leaf (it rebases what it uploads), the Parquet
+// scan, a collect aggregate, split, take_column — delivers offsets that start at 0 over columns without an Arrow offset; anything else is refused by name.
+// Lists of up to kListFnMaxElements elements are ranked (list_rank_kernel); a column with a longer list takes list_fn_sort_route below.
+int list_fn_elem_kind(const DType& t) {
+  switch (t.id) {
+    case TypeId::Bool: return LF_BOOL;
+    case TypeId::Int8: return LF_I8;
+    case TypeId::Int16: return LF_I16;
+    case TypeId::Int32: case TypeId::Date: return LF_I32;
+    case TypeId::Int64: case TypeId::Timestamp: case TypeId::TimestampNtz: return LF_I64;
+    case TypeId::Decimal: return LF_I128;
+    case TypeId::String: return LF_STR;
+    default: return -1;
+  }
+}
+// The sort route: what the rank kernel answers, by the engine's radix sort — for columns that hold a list too long to rank.  The element rows [0, hi) as a table
+// (list row, element, element row) are sorted by (list row, element in the wanted direction and NULL order); the sort is stable, so equal elements keep their
+// position order, and because the lists tile [0, hi) in row order the sorted table's k-th row IS output slot k: its element-row column is sort's answer.
+// distinct sorts ascending and marks the first row of every run of equal (list row, element) key bytes — group_starts' peer flags, as a merging collect_set does —,
+// then scatters the flags back to the elements' own rows.  Brings the Sort operator's limits with it (a Utf8 key padded to the column's longest value: 1000 bytes).
+void ExecutionContext::list_fn_sort_route(const DerivedCol& dc, const int32_t* offs, int64_t rows, int64_t hi, const DeviceColumnView& ec, bool ehv, uint32_t* out) {
+  const bool distinct = dc.op == LF_OP_DISTINCT;
+  const int flags = distinct ? 0 : (int)dc.arg_k;
+  const DType& et = dc.type.kids[0];
+  // what the generated key kernel depends on: the element's type — for a decimal its precision too (up to 18 digits it is read as one word) — and the flags
+  const int key = (((int)et.id * 64 + (et.id == TypeId::Decimal ? et.precision : 0)) << 2) | (flags & 3);
+  auto it = list_fn_sorts_.find(key);
+  if (it == list_fn_sorts_.end()) {
+    auto so = std::make_shared<Operator>();
+    so->kind = OpKind::Sort;
+    so->proto_tag = 103;
+    Operator::SortKey by_list, by_value;
+    by_list.child = bound(0, DType::of(TypeId::Int32));
+    by_value.child = bound(1, et);
+    by_value.descending = (flags & LF_DESC) != 0;
+    by_value.nulls_last = (flags & LF_NULLS_LAST) != 0;
+    so->sort_orders = {by_list, by_value};
+    // (the planned-variant cache is keyed by plan and node id: one id per element type and flags, the same in every task of the plan, clear of the plan's own nodes)
+    node_id_[so.get()] = 0x40000000 + key;
+    it = list_fn_sorts_.emplace(key, so).first;
+  }
+  const Operator& sop = *it->second;
+  auto lrow = std::make_shared<DevBuf>(), iota = std::make_shared<DevBuf>();
+  lrow->ensure((size_t)hi * 4 + 16);
+  iota->ensure((size_t)hi * 4 + 16);
+  if (comet_launch_list_rows(offs, rows, hi, (int32_t*)lrow->p, stream_) != 0 || comet_launch_sort_iota((uint32_t*)iota->p, hi, 0, stream_) != 0) throw CometError("array_sort: launch failed");
+  DevTable t;
+  t.rows = hi;
+  DeviceColumnView lc, ic;
+  lc.data = lrow->p;
+  ic.data = iota->p;
+  t.types = {DType::of(TypeId::Int32), et, DType::of(TypeId::Int32)};
+  t.types[1].virt_parent = t.types[1].virt_kid = -1;
+  t.cols = {lc, ec, ic};
+  t.has_valid = {false, ehv, false};
+  DevTable sorted = sort_table(sop, t);      // (synchronises the stream)
+  const uint32_t* src = (const uint32_t*)sorted.cols[2].data;
+  if (!distinct) {
+    HIP_CHECK(hipMemcpyAsync(out, src, (size_t)hi * 4, hipMemcpyDeviceToDevice, stream_));
+  } else {
+    std::shared_ptr<DevBuf> first;
+    DevBuf fpeer;
+    group_starts(nullptr, sorted, first, "array_distinct", &sop, &fpeer);
+    if (comet_launch_list_scatter_keep(src, (const uint32_t*)fpeer.p, hi, out, stream_) != 0) throw CometError("array_distinct: launch failed");
+  }
+  HIP_CHECK(hipStreamSynchronize(stream_));      // the sorted table and the flags may go
+}
+
+void ExecutionContext::extend_derived_list_fn(DevTable& in, const DerivedCol& dc) {
+  const std::string who = dc.op == LF_OP_SORT ? "array_sort" : "array_distinct";
+  if (dc.src < 0 || (size_t)dc.src >= in.cols.size() || in.types[(size_t)dc.src].id != TypeId::List || dc.type.kids.size() != 1) throw CometError("internal: unknown derived column");
+  int se = -1;
+  for (size_t j = 0; j < in.types.size(); j++)
+    if (in.types[j].virt_parent == dc.src && in.types[j].virt_kid == 0) se = (int)j;
+  const int kind = list_fn_elem_kind(dc.type.kids[0]);
+  if (se < 0 || kind < 0) throw CometError("internal: " + who + ": the list's elements are not a column of the chain's table");
+  const DeviceColumnView sc = in.cols[(size_t)dc.src], ec = in.cols[(size_t)se];
+  const bool hv = in.has_valid[(size_t)dc.src], ehv = in.has_valid[(size_t)se];
+  const int64_t rows = in.rows;
+  int32_t lo = 0, hi = 0;
+  const int32_t* offs = sc.data ? (const int32_t*)sc.data + sc.offset : nullptr;
+  if (rows > 0) {
+    if (!offs) throw CometError(who + " over a list column without offsets is not supported");
+    read_small(&lo, offs, 4);
+    read_small(&hi, offs + rows, 4);
+    if (sc.offset != 0 || lo != 0 || (hi > 0 && ec.offset != 0))
+      throw CometError(who + " over a sliced list column (a non-zero Arrow offset, or element offsets that do not start at 0) is not supported by the MI355X native engine");
+    if (hi < 0) throw CometError(who + ": the list column's offsets do not ascend (0 … " + std::to_string(hi) + ")");
+  }
+  if (hi > 0) {
+    if (!ec.data) throw CometError(who + " over an element column without buffers is not supported");
+    if (ehv && !ec.valid) throw CometError("internal: " + who + ": an element column marked nullable without validity bits");
+  }
+  const bool distinct = dc.op == LF_OP_DISTINCT;
+  DeviceColumnView el = ec;
+  bool el_hv = ehv;
+  DeviceColumnView lv = sc;
+  if (hi > 0) {
+    DevBuf flag;
+    auto rowsbuf = std::make_shared<DevBuf>();      // sort: the source row of every slot; distinct: the keep flags
+    flag.ensure(16);
+    HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, stream_));
+    rowsbuf->ensure((size_t)hi * 4 + 16);
+    // COMET_LIST_FN_TIER=rank | sort forces a route (tests, measurements): rank on a long list is quadratic but correct
+    const char* tier = getenv("COMET_LIST_FN_TIER");
+    const bool force_rank = tier && !strcmp(tier, "rank"), force_sort = tier && !strcmp(tier, "sort");
+    uint32_t too_long = 0;
+    if (!force_sort) {
+      if (comet_launch_list_rank(kind, ec.data, (const uint8_t*)ec.aux, ehv ? ec.valid : nullptr, offs, rows, hi, dc.op, (int)dc.arg_k,
+                                 force_rank ? (int64_t)0x7fffffff : kListFnMaxElements, (uint32_t*)rowsbuf->p, (uint32_t*)flag.p, stream_) != 0)
+        throw CometError(who + ": launch failed");
+      read_small(&too_long, flag.p, 4);
+    }
+    if (force_sort || too_long) list_fn_sort_route(dc, offs, rows, hi, ec, ehv, (uint32_t*)rowsbuf->p);      // a list beyond the rank kernel's: the whole column takes the sort
+    (force_sort || too_long ? list_fn_sort_lists_ : list_fn_rank_lists_) += rows;
+    const uint32_t* take = (const uint32_t*)rowsbuf->p;
+    int64_t taken = hi;
+    std::shared_ptr<DevBuf> idx;
+    if (distinct) {
+      DevBuf tiles, C;
+      tiles.ensure((size_t)((hi + 1023) / 1024 + 2) * 8);
+      C.ensure((size_t)(hi + 2) * 4);
+      HIP_CHECK(hipMemsetAsync(C.p, 0, 8, stream_));
+      pq_launch_u32_scan((const uint32_t*)rowsbuf->p, hi, (uint64_t*)tiles.p, (int32_t*)C.p, stream_);
+      int32_t kept = 0;
+      read_small(&kept, (const char*)C.p + (size_t)hi * 4, 4);
+      if (kept < 0 || kept > hi) throw CometError("internal: array_distinct: " + std::to_string(kept) + " kept elements of " + std::to_string(hi));
+      idx = std::make_shared<DevBuf>();
+      idx->ensure((size_t)std::max<int32_t>(kept, 1) * 4 + 16);
+      auto noffs = std::make_shared<DevBuf>();
+      noffs->ensure((size_t)(rows + 1) * 4 + 16);
+      if (comet_launch_collect_index((const uint32_t*)rowsbuf->p, (const int32_t*)C.p, hi, (uint32_t*)idx->p, stream_) != 0 ||
+          comet_launch_list_offsets(offs, (const int32_t*)C.p, rows, (int32_t*)noffs->p, stream_) != 0)
+        throw CometError("array_distinct: launch failed");
+      HIP_CHECK(hipStreamSynchronize(stream_));      // the tiles and the scan go back to the pool
+      take = (const uint32_t*)idx->p;
+      taken = kept;
+      lv.data = noffs->p;
+      lv.offset = 0;
+      in.owners.push_back(noffs);
+    }
+    el = take_column(ec, dc.type.kids[0], ehv, take, nullptr, taken, el_hv, in.owners);
+    HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
+    if (el_hv != ehv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
+    lv.kid_rows = taken;
+  }
+  lv.kids.assign(1, el);
+  lv.kid_has_valid.assign(1, el_hv ? 1 : 0);
+  in.types.push_back(dc.type);
+  in.cols.push_back(lv);
+  in.has_valid.push_back(hv);
+  DType et = dc.type.kids[0];      // the elements as a column of their own, as split's are
+  et.virt_parent = (int)in.types.size() - 1;
+  et.virt_kid = 0;
+  in.types.push_back(et);
+  in.cols.push_back(el);
+  in.has_valid.push_back(el_hv);
+}
+
 // The chain's derived columns (codegen.hpp DerivedCol) computed over its source table and appended to it.  split: two passes of the matcher per
 // row (regex_kernels.hip) — the pieces counted, a prefix sum, every piece described as a view of its source value — and the element column
 // assembled from the views like every string view's result.
 void ExecutionContext::extend_derived(DevTable& in, const std::vector<DerivedCol>& derived) {
   for (const DerivedCol& dc : derived) {
     if (dc.kind == 3) { extend_derived_strfn(in, dc); continue; }
+    if (dc.kind == 4) { extend_derived_list_fn(in, dc); continue; }
     if ((dc.kind != 1 && dc.kind != 2) || dc.src < 0 || (size_t)dc.src >= in.cols.size()) throw CometError("internal: unknown derived column");
     const DeviceColumnView sc = in.cols[(size_t)dc.src];
     const bool hv = in.has_valid[(size_t)dc.src];
@@ -2277,6 +2440,8 @@ std::string ExecutionContext::metrics_proto() {
       n.metrics.emplace_back("pages_decompressed_on_device", pages_inflated_on_device_);
       n.metrics.emplace_back("page_index_rows_pruned", rows_pruned_page_index_);
     }
+    if (root && list_fn_rank_lists_ > 0) n.metrics.emplace_back("list_fn_rank_lists", list_fn_rank_lists_);      // lists array_sort / array_distinct ranked (only when there are any)
+    if (root && list_fn_sort_lists_ > 0) n.metrics.emplace_back("list_fn_sort_lists", list_fn_sort_lists_);      // … and lists that took the radix sort
     if (root && (op.kind == OpKind::HashAgg || part_merges_ > 0)) n.metrics.emplace_back("agg_partitioned_merges", part_merges_);      // merging aggregates run as partition → LDS merge → emit
     if (root && (op.kind == OpKind::HashAgg || wide_passes_ > 0)) n.metrics.emplace_back("agg_wide_min_max_passes", wide_passes_);      // low-word passes of grouped min / max over wide decimals
     if (op.kind == OpKind::HashJoin && root) {      // (the plan's joins together: the counters are the context's)

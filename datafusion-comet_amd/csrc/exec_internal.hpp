@@ -24,6 +24,15 @@ extern "C" int comet_launch_dict_gather_str_len(const void* idx, int iw, const u
                                                 int64_t n, uint32_t* lengths, uint8_t* out_valid_bytes, void* stream);
 extern "C" int comet_launch_dict_gather_str_copy(const void* idx, int iw, const uint8_t* valid_bytes, const int32_t* dict_offs, const uint8_t* dict_bytes,
                                                  int64_t n, const int32_t* out_offs, uint8_t* out_bytes, void* stream);
+// array_sort / array_distinct (device/list_fn.hpp, list_kernels.hip); collect_kernels.hip's index kernel serves distinct's kept rows too
+#include "device/list_fn.hpp"
+extern "C" int comet_launch_list_rank(int kind, const void* data, const uint8_t* aux, const uint8_t* valid, const int32_t* offs, int64_t rows, int64_t hi, int op,
+                                      int flags, int64_t cap, uint32_t* out, uint32_t* too_long, void* stream);
+extern "C" int comet_launch_list_rows(const int32_t* offs, int64_t rows, int64_t hi, int32_t* out, void* stream);
+extern "C" int comet_launch_list_scatter_keep(const uint32_t* src, const uint32_t* fpeer, int64_t hi, uint32_t* keep, void* stream);
+extern "C" int comet_launch_list_offsets(const int32_t* offs, const int32_t* C, int64_t rows, int32_t* out, void* stream);
+extern "C" int comet_launch_collect_index(const uint32_t* keep, const int32_t* C, int64_t n, uint32_t* idx, void* stream);
+constexpr int64_t kListFnMaxElements = 256;       // the longest list the rank kernel takes (every lane of a list walks all of it); beyond, the radix sort is faster
 extern "C" void pq_launch_u32_scan(const uint32_t* in, int64_t n, uint64_t* tiles, int32_t* out, void* st);
 extern "C" void pq_launch_pack(const uint8_t* bytes, uint8_t* bitmap, int64_t n, void* st);
 extern "C" int comet_launch_window_default(int width, const uint8_t* inside, int64_t n, const void* value, void* data, uint8_t* ok_bytes, void* stream);

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 import sys
 from typing import Iterator, List, Optional, Sequence
 
@@ -158,6 +159,8 @@ def _load() -> ctypes.CDLL:
     lib.comet_extract_all_host.argtypes = [c.c_char_p, c.c_int32, c.c_char_p, c.c_size_t, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.c_int32]
     lib.comet_strfn_host.restype = c.c_int64
     lib.comet_strfn_host.argtypes = [c.c_int32, c.c_char_p, c.c_int32, c.c_char_p, c.c_int32, c.c_char_p, c.c_int32, c.c_int64, c.c_void_p, c.c_int64]
+    lib.comet_list_fn_host.restype = c.c_int32
+    lib.comet_list_fn_host.argtypes = [c.c_int32, c.c_char_p, c.c_char_p, c.c_void_p, c.c_int64, c.c_int32, c.c_int32, c.c_void_p]
     lib.comet_plan_codegen.restype = c.c_int64
     lib.comet_plan_codegen.argtypes = [c.c_char_p, c.c_size_t, c.c_char_p, c.c_int32, c.c_void_p, c.c_int64]
     lib.comet_error_site_json.restype = c.c_int64
@@ -1248,6 +1251,37 @@ def strfn_host(op: int, value: bytes, a: bytes = b"", b: bytes = b"", k: int = 0
     buf = ctypes.create_string_buffer(max(n, 1))
     lib().comet_strfn_host(op, value, len(value), a, len(a), b, len(b), k, buf, n)
     return buf.raw[:n]
+
+
+def list_fn_host(kind: int, values: Sequence, op: int, flags: int = 0) -> List[int]:
+    """csrc/device/list_fn.hpp on the host over ONE list (comet_list_fn_host).  kind: 0 Boolean, 1 / 2 / 4 / 8 / 16 signed integers of that many bytes, 32 Utf8
+    (bytes values); None is a NULL element.  op 0 sort (flags: 1 descending | 2 NULLs last) → the element index that stands in every slot; op 1 distinct →
+    a keep flag per element"""
+    n = len(values)
+    valid = bytearray((n + 7) // 8 + 1)
+    for i, v in enumerate(values):
+        if v is not None:
+            valid[i >> 3] |= 1 << (i & 7)
+    aux = b""
+    if kind == 0:
+        data = bytearray((n + 7) // 8 + 1)
+        for i, v in enumerate(values):
+            if v:
+                data[i >> 3] |= 1 << (i & 7)
+        data = bytes(data)
+    elif kind == 32:
+        offs, parts = [0], []
+        for v in values:
+            parts.append(v or b"")
+            offs.append(offs[-1] + len(parts[-1]))
+        data, aux = struct.pack("<%di" % len(offs), *offs), b"".join(parts)
+    else:
+        data = b"".join(int(v or 0).to_bytes(kind, "little", signed=True) for v in values)
+    out = (ctypes.c_uint32 * max(n, 1))()
+    vbuf = (ctypes.c_uint8 * len(valid)).from_buffer(valid)
+    if lib().comet_list_fn_host(kind, data or b"\0", aux or b"\0", vbuf, n, op, flags, out) != 0:
+        _raise_last(0)
+    return list(out[:n])
 
 
 def plan_codegen(plan: bytes, has_valid: Sequence[bool]) -> dict:

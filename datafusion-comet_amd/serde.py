@@ -426,6 +426,32 @@ def regexp_replace(subject: Expr, pattern: str, replacement: str) -> Expr:
     return scalar_func("regexp_replace", [subject, lit(pattern, T_STRING), lit(replacement, T_STRING), lit("g", T_STRING)], T_STRING)
 
 
+def sort_array(child: Expr, ascending: bool = True) -> Expr:
+    """SortArray(arr, ascending) as the JVM sends it (arrays.scala:154-174): ScalarFunc array_sort with the direction and the NULL ordering as Utf8 literals —
+    ascending puts NULL elements first, descending puts them last — and no return type"""
+    return scalar_func("array_sort", [child, lit("ASC" if ascending else "DESC", T_STRING), lit("NULLS FIRST" if ascending else "NULLS LAST", T_STRING)])
+
+
+def array_distinct(child: Expr) -> Expr:
+    """ArrayDistinct(arr): ScalarFunc array_distinct"""
+    return scalar_func("array_distinct", [child])
+
+
+def array_min(child: Expr) -> Expr:
+    """ArrayMin(arr): ScalarFunc array_min (arrays.scala:231-241)"""
+    return scalar_func("array_min", [child])
+
+
+def array_max(child: Expr) -> Expr:
+    """ArrayMax(arr): ScalarFunc array_max (arrays.scala:218-229)"""
+    return scalar_func("array_max", [child])
+
+
+def array_position(child: Expr, key: Expr) -> Expr:
+    """ArrayPosition(arr, key): ScalarFunc spark_array_position → Int64, 0 when there is none (arrays.scala:742-755)"""
+    return scalar_func("spark_array_position", [child, key])
+
+
 def unscaled_value(child: Expr) -> Expr:
     """UnscaledValue(decimal(p <= 18, s)) -> Long, what Spark's DecimalAggregates rule puts under sum / avg of short decimals (decimalExpressions.scala:27-45)."""
     return scalar_func("unscaled_value", [child], T_INT64)

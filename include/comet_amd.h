@@ -262,6 +262,14 @@ int32_t comet_plan_set_subquery_provider(int64_t handle, comet_subquery_provider
  * 22 ascii: the value.  Needs no GPU. */
 int64_t comet_strfn_host(int32_t op, const uint8_t* value, int32_t n, const uint8_t* a, int32_t na, const uint8_t* b, int32_t nb, int64_t k, uint8_t* out, int64_t cap);
 
+#ifdef COMET_TEST_ABI
+/* (TEST ABI) array_sort / array_distinct of ONE list by csrc/device/list_fn.hpp's key, compare, rank and keep code on the host — diagnostic entry.  kind: the element layout
+ * (0 Boolean bits, 1 / 2 / 4 / 8 / 16: little-endian integers of that many bytes, 32: Utf8 — `data` its n + 1 int32 offsets, `aux` its bytes); valid: the
+ * elements' validity bits or NULL; op 0 sort (flags: 1 descending | 2 NULLs last) → out[slot] = the element that stands there; op 1 distinct → out[i] = 1 when
+ * element i stays.  out holds n entries.  0, or -2 and comet_last_error(0).  Needs no GPU. */
+int32_t comet_list_fn_host(int32_t kind, const void* data, const uint8_t* aux, const uint8_t* valid, int64_t n, int32_t op, int32_t flags, uint32_t* out);
+#endif /* COMET_TEST_ABI */
+
 /* regexp_extract_all(value, pattern, group) (string_funcs/regexp_extract_all.rs) by the device's two passes (rx_find_all) on the host: the number of matches,
  * the group's (start, length) per match written while they fit `cap`; -2 and comet_last_error(0).  Needs no GPU. */
 int32_t comet_extract_all_host(const char* pattern, int32_t group, const uint8_t* value, size_t value_len, int32_t* starts, int32_t* lens, int32_t cap);

@@ -129,6 +129,13 @@ def probes():
         "GetArrayItem": (S.list_extract(S.col(7, S.list_type(S.T_INT64)), L(0, S.T_INT32)), "ListExtract over a list COLUMN of flat elements (a split's result too); string elements as output columns; ANSI errors as the reference's"),
         "ElementAt": (S.list_extract(S.col(7, S.list_type(S.T_INT64)), L(-1, S.T_INT32), one_based=True), "arrays (ListExtract, one-based, negative from the end); maps are refused"),
         "ArrayContains": (f("array_contains", [S.col(7, S.list_type(S.T_INT64)), L(3, S.T_INT64)], S.T_BOOL), "list COLUMN of integers / dates / decimals(<= 18) / booleans with a key of that type; lists of strings with a literal key"),
+        "SortArray": (S.sort_array(S.col(7, S.list_type(S.T_INT64))),
+                      "`array_sort(arr, 'ASC' | 'DESC', 'NULLS FIRST' | 'NULLS LAST')`: of a list COLUMN or a derived list (a split's, a collect's, another list function's result) of Boolean / integers / "
+                      "Date / Timestamp / TimestampNTZ / Decimal / Utf8 elements, lists of any length; a derived list column of the chain's source (§4)"),
+        "ArrayDistinct": (S.array_distinct(S.col(7, S.list_type(S.T_INT64))), "as SortArray: the first occurrence of every value in position order, NULL elements as one value"),
+        "ArrayMin": (S.array_min(S.col(7, S.list_type(S.T_INT64))), "of a list COLUMN or a derived list of Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal elements, any length; Utf8 is refused (`sort_array(x)[0]` serves)"),
+        "ArrayMax": (S.array_max(S.col(7, S.list_type(S.T_INT64))), "as ArrayMin"),
+        "ArrayPosition": (S.array_position(S.col(7, S.list_type(S.T_INT64)), L(3, S.T_INT64)), "`spark_array_position` → Int64: elements of Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal of any precision (beyond 18 digits compared as 128-bit values) with a key of the element's type, literal or column; lists of strings with a literal key"),
         "Reverse": (f("reverse", [s], S.T_STRING), "of a Utf8 COLUMN: a derived column of the chain's source (usable as an operand, any length); arrays are refused"),
         "StringRepeat": (f("repeat", [s, L(2, S.T_INT64)], S.T_STRING), "literal count >= 0; derived column"), "StringReplace": (f("replace", [s, L("a", S.T_STRING), L("b", S.T_STRING)], S.T_STRING), "under allowIncompatible (Rust's str::replace for an empty search string); literal arguments; derived column"),
         "SubstringIndex": (f("substring_index", [s, L(".", S.T_STRING), L(2, S.T_INT64)], S.T_STRING), "literal delimiter and count; derived column"),
@@ -308,9 +315,19 @@ def render() -> str:
     w("  than 4096 rows, lag / lead defaults of Utf8 / Boolean type.")
     w("* Nested types: struct-of-flat, list-of-flat, list-of-flat-struct and map columns are read from Parquet, passed through Filter / Projection / Sort /")
     w("  Limit / ShuffleWriter, taken apart by `GetStructField` and exported; struct / list columns of any depth arrive through Scan / ShuffleScan inputs;")
-    w("  `Explode` of a list column runs; `size`, `arr[i]` / `element_at`, `array_contains` over a list COLUMN of flat elements run; deeper trees in the Parquet scan, `Explode` of a map,")
+    w("  `Explode` of a list column runs; `size`, `arr[i]` / `element_at`, `array_contains`, `sort_array`, `array_distinct`, `array_min` / `array_max` and `array_position` over a")
+    w("  list COLUMN of flat elements run; deeper trees in the Parquet scan, `Explode` of a map,")
     w("  the other array / map functions and everything that builds a struct / an array / a map are refused.")
     w("  Parquet: TIMESTAMP(NANOS) / TIME, encrypted files.")
+    w("* `SortArray`, `ArrayDistinct`, `ArrayMin`, `ArrayMax`, `ArrayPosition`: Float32 / Float64 elements (Spark and the reference disagree on signed zeros there, the")
+    w("  reference's own `sort_array.sql` ignores those cases); Binary, struct, list and map elements; a map argument; an argument that is neither a list COLUMN of the")
+    w("  chain's source nor a derived list (a computed `array(...)`); `array_min` / `array_max` over Utf8 elements; `array_position` over Utf8 elements with a key that is")
+    w("  not a literal; `array_sort` whose second or third argument is not one of the literals `'ASC'` / `'DESC'` and `'NULLS FIRST'` / `'NULLS LAST'`; `sort_array` /")
+    w("  `array_distinct` inside an aggregate's fused chain (project them below it; under a join the side that holds them is materialised instead of fused, and runs).  Lists of up to 256 elements are ranked element by element, with Utf8")
+    w("  elements of any length; a column that holds a longer list goes through the Sort operator's radix sort and brings its limits with it: a Utf8 element beyond the")
+    w("  1000-byte sort key (values are padded to the column's longest) fails the task with that operator's message.  Both refuse a sliced list column — a non-zero Arrow offset on")
+    w("  the list or its elements, or element offsets that do not start at 0 — at run time, by name; no producer in this engine delivers one (a Scan leaf rebases what it")
+    w("  uploads, device-resident inputs carry no lists), so no plan meets this today.")
     w("* ShuffleWriter with more than 4096 partitions.")
     w("")
     w("## 5. Results that are not bit-equal to the reference's (and how far apart they may be)")
