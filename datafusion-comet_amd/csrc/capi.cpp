@@ -511,7 +511,13 @@ int64_t comet_plan_codegen(const uint8_t* plan, size_t plan_len, const uint8_t* 
       const std::vector<DType> types = nested ? extend_struct_field_types(leaf->scan_fields) : leaf->scan_fields;
       std::vector<bool> hv(types.size(), false);
       for (int32_t k = 0; k < n_valid && (size_t)k < hv.size(); k++) hv[(size_t)k] = has_valid && has_valid[k] != 0;
-      d = nested ? generate_pipeline(*op, hv, &types) : generate_pipeline(*op, hv);
+      if (op->kind == OpKind::Sort) {
+        // the sort-key kernel of a Sort directly over the Scan (tests/emu: the key bytes of every row, evaluated on the host)
+        if (op->children.size() != 1 || op->children[0]->kind != OpKind::Scan) throw CometError("comet_plan_codegen: a Sort root is expected directly over its Scan leaf");
+        d = generate_sort_keys(*op, types, hv);
+      } else {
+        d = nested ? generate_pipeline(*op, hv, &types) : generate_pipeline(*op, hv);
+      }
     }
     std::string j = "{\"sink\":" + std::to_string((int)d.sink) + ",\"has_filter\":" + (d.has_filter ? "true" : "false") + ",\"R\":" + std::to_string(d.R) + ",\"derived\":" + std::to_string(d.derived.size()) +
                     ",\"kernels\":[";
@@ -527,7 +533,13 @@ int64_t comet_plan_codegen(const uint8_t* plan, size_t plan_len, const uint8_t* 
     j += "],\"fix_sums\":[";      // exact Float64 sums: the accumulator word and the aux words (exponent range seen) of each, for the scale pass (exec_pipeline.cpp adjust_fix_scales)
     for (size_t k = 0; k < d.fix_sums.size(); k++)
       j += std::string(k ? "," : "") + "{\"word\":" + std::to_string(d.fix_sums[k].word) + ",\"aux_hi\":" + std::to_string(d.fix_sums[k].aux_hi) + ",\"aux_lo\":" + std::to_string(d.fix_sums[k].aux_lo) + "}";
-    j += "],\"source\":" + json_str(d.source) + "}";
+    j += "]";
+    if (op->kind == OpKind::Sort) {      // (only for a Sort root: the other roots' JSON is pinned by tests/golden/codegen_corpus.json)
+      j += ",\"sort_key_bytes\":" + std::to_string(d.sort_key_bytes) + ",\"sort_str_cols\":[";
+      for (size_t k = 0; k < d.sort_str_cols.size(); k++) j += (k ? "," : "") + std::to_string(d.sort_str_cols[k]);
+      j += "]";
+    }
+    j += ",\"source\":" + json_str(d.source) + "}";
     if (out && cap > (int64_t)j.size()) memcpy(out, j.c_str(), j.size() + 1);
     return (int64_t)j.size();
   });

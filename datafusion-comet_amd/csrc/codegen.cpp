@@ -5297,7 +5297,8 @@ PipelineDesc generate_join(const Operator& j, const std::vector<DType>& lt_in, c
 // Sort keys (Sort operator, planner.rs:1488-1522 → DataFusion SortExec): every row gets an order-preserving byte string —
 // per sort expression one NULL-ordering byte (NULLS FIRST: NULL = 0x00 < 0x01; NULLS LAST: NULL = 0x01 > 0x00) followed by the
 // value big-endian with the sign bit flipped (floats through the IEEE totalOrder key), inverted for DESC; NULL rows carry zero
-// value bytes.  The bytes are stored as PLANES (plane b = byte b of every row) so that the executor's LSD radix sort reads one
+// value bytes.  Value bytes per key: the type's own width (Boolean and Int8 1, Int16 2, Int32 / Date / Float32 4, Int64 / Timestamp / Float64 8), 16 for
+// every decimal and for a computed string, the column's longest value + 4 for a Utf8 column.  The bytes are stored as PLANES (plane b = byte b of every row) so that the executor's LSD radix sort reads one
 // plane per pass.  prm.out[0] = planes (W × n bytes), prm.n = rows.
 // ---------------------------------------------------------------------------------------------
 PipelineDesc generate_sort_keys(const Operator& sort, const std::vector<DType>& types, const std::vector<bool>& valid) {
@@ -5350,7 +5351,11 @@ PipelineDesc generate_sort_keys(const Operator& sort, const std::vector<DType>& 
     std::string word;   // unsigned order-preserving word(s)
     switch (v.rep) {
       case Rep::B: nb = 1; word = "(u64)(" + v.v + " ? 1 : 0)"; break;
-      case Rep::I32: nb = 4; word = "(u64)((u32)(i32)" + v.v + " ^ 0x80000000u)"; break;
+      case Rep::I32:
+        // (Int8 / Int16 live sign-extended in an i32: their own 1 / 2 bytes order them, and the extension's bytes would only add planes that vary with the sign)
+        nb = v.t.id == TypeId::Int8 ? 1 : v.t.id == TypeId::Int16 ? 2 : 4;
+        word = "(u64)((u32)(i32)" + v.v + " ^ " + (nb == 1 ? "0x80u" : nb == 2 ? "0x8000u" : "0x80000000u") + ")";
+        break;
       case Rep::I64: nb = v.t.id == TypeId::Decimal ? 16 : 8; word = "((u64)(i64)" + v.v + " ^ 0x8000000000000000ull)"; break;
       case Rep::F32: nb = 4; word = "(u64)((u32)comet::f32_total_key(" + v.v + ") ^ 0x80000000u)"; break;
       case Rep::F64: nb = 8; word = "((u64)comet::f64_total_key(" + v.v + ") ^ 0x8000000000000000ull)"; break;

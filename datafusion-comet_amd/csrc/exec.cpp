@@ -1977,6 +1977,11 @@ DevTable ExecutionContext::nested_aggregate(const Operator& agg) {
   input_rows += sub.input_rows;
   part_merges_ += sub.part_merges_;
   wide_passes_ += sub.wide_passes_;
+  sort_runs_ += sub.sort_runs_;
+  sort_select_passes_ += sub.sort_select_passes_;
+  sort_small_sorts_ += sub.sort_small_sorts_;
+  sort_radix_passes_ += sub.sort_radix_passes_;
+  sort_rows_sorted_ += sub.sort_rows_sorted_;
   sub.collect_timings();
   last_kernel_ms += sub.last_kernel_ms;
   last_kernel_launches += sub.last_kernel_launches;
@@ -2442,6 +2447,12 @@ std::string ExecutionContext::metrics_proto() {
     }
     if (root && list_fn_rank_lists_ > 0) n.metrics.emplace_back("list_fn_rank_lists", list_fn_rank_lists_);      // lists array_sort / array_distinct ranked (only when there are any)
     if (root && list_fn_sort_lists_ > 0) n.metrics.emplace_back("list_fn_sort_lists", list_fn_sort_lists_);      // … and lists that took the radix sort
+    if (root && sort_runs_ > 0) {      // the paths sort_table took (only when the plan sorted at all): see DESIGN.md, Sort
+      n.metrics.emplace_back("sort_select_passes", sort_select_passes_);
+      n.metrics.emplace_back("sort_small_sorts", sort_small_sorts_);
+      n.metrics.emplace_back("sort_radix_passes", sort_radix_passes_);
+      n.metrics.emplace_back("sort_rows_sorted", sort_rows_sorted_);
+    }
     if (root && (op.kind == OpKind::HashAgg || part_merges_ > 0)) n.metrics.emplace_back("agg_partitioned_merges", part_merges_);      // merging aggregates run as partition → LDS merge → emit
     if (root && (op.kind == OpKind::HashAgg || wide_passes_ > 0)) n.metrics.emplace_back("agg_wide_min_max_passes", wide_passes_);      // low-word passes of grouped min / max over wide decimals
     if (op.kind == OpKind::HashJoin && root) {      // (the plan's joins together: the counters are the context's)

@@ -436,6 +436,9 @@ class ExecutionContext {
   DevTable part_result_;
   int64_t part_merges_ = 0;
   int64_t wide_passes_ = 0;      // k_gwlow launches (grouped min / max of a decimal wider than 18 digits)
+  // sort_table, summed over every sort the plan ran (Window, SortMergeJoin, percentile, … included): TopK radix-select passes, sorts done by the
+  // one-workgroup bitonic kernel, LSD radix passes, and the rows that took part in the full sort (ns)
+  int64_t sort_runs_ = 0, sort_select_passes_ = 0, sort_small_sorts_ = 0, sort_radix_passes_ = 0, sort_rows_sorted_ = 0;
   bool try_partitioned_merge(Variant& v, CometKParams& prm, int64_t n);
   struct DevPending {      // a device batch pulled one ahead of its turn
     std::vector<DeviceColumnView> views;

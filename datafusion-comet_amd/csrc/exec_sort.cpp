@@ -315,6 +315,10 @@ DevTable ExecutionContext::sort_table(const Operator& sop, const DevTable& in) {
     if (comet_launch_sort_small((const uint8_t*)planes->p, n, (const uint32_t*)perm->p, (int)ns, vplanes.data(), (int)vplanes.size(), (uint32_t*)perm2->p, stream_) != 0)
       throw CometError("sort: launch failed");
     timed_end();
+    sort_runs_++;
+    sort_select_passes_ += select_passes;
+    sort_small_sorts_++;
+    sort_rows_sorted_ += ns;
     if (getenv("COMET_TRACE_STAGES"))
       fprintf(stderr, "[comet] sort: %lld rows, key %d bytes, %d select passes -> %lld rows sorted by one workgroup\n", (long long)n, W, select_passes, (long long)ns);
     return take_rows(in, (const uint32_t*)perm2->p, skip, out_rows, perm2);   // synchronises the stream
@@ -339,6 +343,10 @@ DevTable ExecutionContext::sort_table(const Operator& sop, const DevTable& in) {
     passes++;
   }
   timed_end();
+  sort_runs_++;
+  sort_select_passes_ += select_passes;
+  sort_radix_passes_ += passes;
+  sort_rows_sorted_ += ns;
   if (getenv("COMET_TRACE_STAGES"))
     fprintf(stderr, "[comet] sort: %lld rows, key %d bytes, %d select passes -> %lld rows sorted in %d radix passes\n", (long long)n, W, select_passes,
             (long long)ns, passes);

@@ -221,6 +221,8 @@ int32_t comet_regexp_extract_host(const char* pattern, int32_t group, const uint
  * bitmap), or for a HashJoin over two Scan leaves or Filter / Projection chains over them (fused as createPlan decides; has_valid: the left source's columns, then the
  * right source's), and what the executor needs to read its outputs, as JSON {"sink", "has_filter", "R", "kernels": [...], "out": [{"type", "precision", "scale", "nullable",
  * "gather_src", "view_src", "fmt_kind", "packed_string", "concat", "case_mode", "pad", "pad_left"}], "source"}: the length, the text written when it fits `cap`.
+ * A Sort directly over its Scan leaf yields the sort-key kernel's source, and two more fields: "sort_key_bytes" (the fixed part of a row's key) and
+ * "sort_str_cols" (the Utf8 columns among the keys, in key order: each adds its longest value + 4 bytes, passed in iarg[1 + position]).
  * comet_embedded_header: the text of a header hiprtc compiles that source against ("comet_device.hpp", "kparams.h", "comet_ryu.hpp", "comet_strtod.hpp",
  * "comet_strts.hpp", "comet_regex_vm.hpp").  -2 and comet_last_error(0) on failure.  Neither needs a GPU. */
 int64_t comet_plan_codegen(const uint8_t* plan, size_t plan_len, const uint8_t* has_valid, int32_t n_valid, char* out, int64_t cap);

@@ -1512,6 +1512,10 @@ def run_plan(S, op, table) -> List[Col]:
         def cell(c, i):
             if not c.ok()[i]:
                 return None
+            if c.dtype.type_id in (S.FLOAT, S.DOUBLE):
+                # arrow-ord's partition() tells neighbours apart with `distinct`, which compares floats under IEEE totalOrder — by their bits: −0.0 and 0.0 are two
+                # partitions, NaNs of one bit pattern are one (Python's == would join the zeros and put every NaN row alone)
+                return int(np.array([c.values[i]]).view(np.int64 if c.values.dtype.itemsize == 8 else np.int32)[0])
             return dec_to_int(c.values, i) if c.dtype.type_id == S.DECIMAL else (c.values[i].item() if hasattr(c.values[i], "item") else c.values[i])
         ptuple = [tuple(cell(c, i) for c in pk) for i in range(n)]
         otuple = [tuple(cell(c, i) for c in okeys) for i in range(n)]

@@ -141,12 +141,27 @@ static long long emu_impl(const CometKParams* prm_in) {
       }
     }
     return total;
-  } else {
+  } else if constexpr (requires { P::emit(prm, (i64)0, (i64)0); }) {
     threadIdx.x = 0;
     for (i64 i = 0; i < n; i++) P::emit(prm, i, i);
     return n;
+  } else {
+    return -1;
   }
 }
+// generate_sort_keys' source: P::keys writes one row's key bytes into the planes at prm.out[0] (what k_sortkey does for every row)
+template <class P>
+static long long emu_keys_impl(const CometKParams* prm_in) {
+  if constexpr (requires(const CometKParams& q) { P::keys(q, (i64)0); }) {
+    CometKParams prm = *prm_in;
+    threadIdx.x = 0;
+    for (i64 i = 0; i < prm.n; i++) P::keys(prm, i);
+    return prm.n;
+  } else {
+    return -1;
+  }
+}
+extern "C" __attribute__((visibility("default"))) long long emu_keys(const CometKParams* prm_in) { return emu_keys_impl<P>(prm_in); }
 // (every plan's library defines a struct P, its statics and emu_run: hidden visibility, no unique symbols, symbolic binding keep each library to itself)
 extern "C" __attribute__((visibility("default"))) long long emu_run(const CometKParams* prm_in) { return emu_impl<P>(prm_in); }
 """
@@ -202,6 +217,8 @@ def _compiled(source: str):
         lib = ctypes.CDLL(so)
         lib.emu_run.restype = ctypes.c_longlong
         lib.emu_run.argtypes = [ctypes.c_void_p]
+        lib.emu_keys.restype = ctypes.c_longlong
+        lib.emu_keys.argtypes = [ctypes.c_void_p]
         _CACHE[key] = lib
     return _CACHE[key]
 
@@ -222,6 +239,31 @@ _PA = {S.BOOL: pa.bool_(), S.INT8: pa.int8(), S.INT16: pa.int16(), S.INT32: pa.i
 
 def _addr(buf):
     return buf.address if buf is not None else None
+
+
+def _bind_inputs(prm, bound, has_valid):
+    """the input columns' buffers into prm.inp, as the executor's bind_inputs does; → what must stay alive while prm is used"""
+    keep = []
+    if len(bound) > 24:
+        raise Unsupported("more than COMET_MAX_IN columns")
+    for i, c in enumerate(bound):
+        bufs = c.buffers()
+        t = c.type
+        prm.inp[i].offset = c.offset
+        prm.inp[i].valid = _addr(bufs[0]) if has_valid[i] else None
+        if pa.types.is_string(t) or pa.types.is_binary(t):
+            prm.inp[i].data = _addr(bufs[1])
+            prm.inp[i].aux = _addr(bufs[2]) if bufs[2] is not None else ctypes.addressof(ctypes.create_string_buffer(1))
+        elif pa.types.is_list(t):
+            prm.inp[i].data = _addr(bufs[1])      # the offsets; the elements are a column of their own
+        elif pa.types.is_struct(t):
+            prm.inp[i].data = None
+        elif pa.types.is_nested(t) or pa.types.is_dictionary(t):
+            raise Unsupported("map / dictionary inputs")
+        else:
+            prm.inp[i].data = _addr(bufs[1])
+        keep.append((c, bufs))
+    return keep
 
 
 def run_chain(plan, table: pa.Table) -> pa.Table:
@@ -251,26 +293,7 @@ def run_chain(plan, table: pa.Table) -> pa.Table:
     n = table.num_rows
     prm = _Params()
     prm.n = n
-    keep = []
-    if len(bound) > 24:
-        raise Unsupported("more than COMET_MAX_IN columns")
-    for i, c in enumerate(bound):
-        bufs = c.buffers()
-        t = c.type
-        prm.inp[i].offset = c.offset
-        prm.inp[i].valid = _addr(bufs[0]) if has_valid[i] else None
-        if pa.types.is_string(t) or pa.types.is_binary(t):
-            prm.inp[i].data = _addr(bufs[1])
-            prm.inp[i].aux = _addr(bufs[2]) if bufs[2] is not None else ctypes.addressof(ctypes.create_string_buffer(1))
-        elif pa.types.is_list(t):
-            prm.inp[i].data = _addr(bufs[1])      # the offsets; the elements are a column of their own
-        elif pa.types.is_struct(t):
-            prm.inp[i].data = None
-        elif pa.types.is_nested(t) or pa.types.is_dictionary(t):
-            raise Unsupported("map / dictionary inputs")
-        else:
-            prm.inp[i].data = _addr(bufs[1])
-        keep.append((c, bufs))
+    keep = _bind_inputs(prm, bound, has_valid)
     cols = bound
     errbuf = np.zeros(512, np.uint8)
     scratch0, scratch1 = np.zeros(8 * (n // 2048 + 4), np.uint8), np.zeros(64, np.uint8)
@@ -342,6 +365,38 @@ def run_chain(plan, table: pa.Table) -> pa.Table:
             a = pa.array(x, base or _PA[oc["type"]], mask=mask)
             arrays.append(a.cast(_PA[oc["type"]]) if base else a)
     return pa.table(arrays, names=[f"col_{i}" for i in range(len(arrays))])
+
+
+def run_sort_keys(plan, table: pa.Table) -> np.ndarray:
+    """The order-preserving key bytes of every row of `table` under a Sort directly over its Scan, through the generated code (generate_sort_keys):
+    an (n, W) uint8 array, row i = the W key bytes of row i.  Utf8 sort columns are padded to their longest value + 4 bytes of length, measured here the way
+    the executor's sort_key_planes measures them."""
+    cols = [table.column(i).combine_chunks() if isinstance(table.column(i), pa.ChunkedArray) else table.column(i) for i in range(table.num_columns)]
+    has_valid = [c.null_count > 0 for c in cols]
+    desc = native.plan_codegen(plan if isinstance(plan, (bytes, bytearray)) else plan.encode(), has_valid)
+    lib = _compiled(desc["source"])
+    n = table.num_rows
+    prm = _Params()
+    prm.n = n
+    keep = _bind_inputs(prm, cols, has_valid)
+    W = desc["sort_key_bytes"]
+    for s, c in enumerate(desc["sort_str_cols"]):
+        offs = np.frombuffer(cols[c].buffers()[1], dtype=np.int32)[cols[c].offset:cols[c].offset + n + 1]
+        longest = int(np.diff(offs).max()) if n else 0
+        prm.iarg[1 + s] = longest + 4
+        W += longest + 4
+    planes = np.full(W * max(n, 1) + 16, 0xA5, np.uint8)      # (every byte of every row must be WRITTEN: a plane the code skips shows)
+    errbuf = np.zeros(512, np.uint8)
+    prm.out[0], prm.out[2] = planes.ctypes.data, errbuf.ctypes.data
+    with _RUN_LOCK:
+        rows = lib.emu_keys(ctypes.byref(prm))
+    if rows != n:
+        raise Unsupported("the source has no P::keys")
+    flags = int(errbuf[:4].view(np.uint32)[0])
+    if flags:
+        _raise_like_the_executor(flags, errbuf, plan)
+    del keep
+    return np.ascontiguousarray(planes[:W * n].reshape(W, n).T) if n else np.zeros((0, W), np.uint8)
 
 
 _FLAG_JSON = [(1, '{"errorType":"ArithmeticOverflow","errorClass":"ARITHMETIC_OVERFLOW","params":{"fromType":"decimal"}}'),
