@@ -13,7 +13,7 @@
 #include "parquet_meta.hpp"
 #include "regex.hpp"
 namespace comet {
-std::vector<DType> extend_struct_field_types(const std::vector<DType>& types);      // exec.cpp
+std::vector<DType> extend_struct_field_types(const std::vector<DType>& types, bool with_maps);      // exec.cpp
 }
 // (jit.cpp: the header texts hiprtc compiles against)
 namespace comet {
@@ -23,6 +23,7 @@ extern const char* const kEmbeddedRyuHeader;
 extern const char* const kEmbeddedStrtodHeader;
 extern const char* const kEmbeddedStrtsHeader;
 extern const char* const kEmbeddedRegexVmHeader;
+extern const char* const kEmbeddedMapFnHeader;
 }
 // (device/strfn.hpp, as the host sees it: comet_strfn_host below)
 namespace comet_strfn_host_ns {
@@ -508,7 +509,7 @@ int64_t comet_plan_codegen(const uint8_t* plan, size_t plan_len, const uint8_t* 
       // (a source with struct / list columns: the chain sees their fields and elements as columns behind the real ones, like over a materialised source)
       bool nested = false;
       for (auto& t : leaf->scan_fields) nested = nested || t.is_nested();
-      const std::vector<DType> types = nested ? extend_struct_field_types(leaf->scan_fields) : leaf->scan_fields;
+      const std::vector<DType> types = nested ? extend_struct_field_types(leaf->scan_fields, op->looks_into_maps) : leaf->scan_fields;
       std::vector<bool> hv(types.size(), false);
       for (int32_t k = 0; k < n_valid && (size_t)k < hv.size(); k++) hv[(size_t)k] = has_valid && has_valid[k] != 0;
       if (op->kind == OpKind::Sort) {
@@ -557,7 +558,7 @@ int64_t comet_embedded_header(const char* name, char* out, int64_t cap) {
   return guarded(nullptr, (int64_t)-2, [&]() -> int64_t {
     const std::string n = name ? name : "";
     const char* t = n == "comet_device.hpp" ? kEmbeddedDeviceHeader : n == "kparams.h" ? kEmbeddedKParamsHeader : n == "comet_ryu.hpp" ? kEmbeddedRyuHeader : n == "comet_strtod.hpp" ? kEmbeddedStrtodHeader
-                    : n == "comet_strts.hpp" ? kEmbeddedStrtsHeader : n == "comet_regex_vm.hpp" ? kEmbeddedRegexVmHeader : nullptr;
+                    : n == "comet_strts.hpp" ? kEmbeddedStrtsHeader : n == "comet_regex_vm.hpp" ? kEmbeddedRegexVmHeader : n == "comet_map_fn.hpp" ? kEmbeddedMapFnHeader : nullptr;
     if (!t) throw CometError("no embedded header named '" + n + "'");
     const int64_t len = (int64_t)strlen(t);
     if (out && cap > len) memcpy(out, t, (size_t)len + 1);
@@ -664,7 +665,7 @@ int64_t comet_plan_site_error_json(const uint8_t* plan, size_t plan_len, uint32_
     while (!leaf->children.empty()) leaf = leaf->children[0].get();
     bool nested = false;      // (as in comet_plan_codegen: fields and elements are columns behind the real ones)
     for (auto& t : leaf->scan_fields) nested = nested || t.is_nested();
-    const std::vector<DType> types = nested ? extend_struct_field_types(leaf->scan_fields) : leaf->scan_fields;
+    const std::vector<DType> types = nested ? extend_struct_field_types(leaf->scan_fields, op->looks_into_maps) : leaf->scan_fields;
     std::vector<bool> none(types.size(), false);
     const PipelineDesc d = nested ? generate_pipeline(*op, none, &types) : generate_pipeline(*op, none);
     ErrSite site;

@@ -55,6 +55,7 @@ thread_local bool g_uses_ryu = false;      // the source being generated calls i
 thread_local bool g_uses_strtod = false;   // … into comet_strtod.hpp (String → Float / Double)
 thread_local bool g_uses_strts = false;    // … into comet_strts.hpp (String → Timestamp)
 thread_local bool g_uses_regex_vm = false; // … into comet_regex_vm.hpp (regexp_extract)
+thread_local bool g_uses_map_fn = false;   // … into comet_map_fn.hpp (map_extract)
 // the pipeline being generated: where raise sites with a QueryContext are noted, and how many sites of each content it has seen (err_sites.cpp)
 thread_local std::vector<std::pair<uint32_t, std::shared_ptr<QueryContext>>>* g_site_sink = nullptr;
 thread_local std::map<std::string, int>* g_site_ordinals = nullptr;
@@ -66,7 +67,7 @@ struct SiteScope {
   std::map<std::string, int> ordinals;
   std::set<std::string> bloom_seen;
   // (the optional-header flags start clean: a generation that threw after setting one must not make the next, unrelated kernel include the tables)
-  explicit SiteScope(PipelineDesc& d) { g_site_sink = &d.site_contexts; g_site_ordinals = &ordinals; g_bloom_sink = &d.blooms; g_bloom_seen = &bloom_seen; g_uses_ryu = g_uses_strtod = g_uses_strts = g_uses_regex_vm = false; }
+  explicit SiteScope(PipelineDesc& d) { g_site_sink = &d.site_contexts; g_site_ordinals = &ordinals; g_bloom_sink = &d.blooms; g_bloom_seen = &bloom_seen; g_uses_ryu = g_uses_strtod = g_uses_strts = g_uses_regex_vm = g_uses_map_fn = false; }
   ~SiteScope() { g_site_sink = nullptr; g_site_ordinals = nullptr; g_bloom_sink = nullptr; g_bloom_seen = nullptr; }
 };
 // the filters' buffers travel in the kernel-argument slots the columns leave free, from the top down
@@ -96,7 +97,12 @@ std::string with_optional_headers(std::string src) {
     const size_t at = src.find(inc);
     if (at != std::string::npos) src.insert(at + inc.size(), "#include \"comet_regex_vm.hpp\"\n");
   }
-  g_uses_ryu = g_uses_strtod = g_uses_strts = g_uses_regex_vm = false;
+  if (g_uses_map_fn) {
+    const std::string inc = "using namespace comet;\n";
+    const size_t at = src.find(inc);
+    if (at != std::string::npos) src.insert(at + inc.size(), "#include \"comet_map_fn.hpp\"\n");
+  }
+  g_uses_ryu = g_uses_strtod = g_uses_strts = g_uses_regex_vm = g_uses_map_fn = false;
   return src;
 }
 
@@ -450,6 +456,50 @@ ExprP lower_list_fn(const ExprP& e) {
   b->has_dtype = true;
   return b;
 }
+// map_keys(m), map_values(m) and map_entries(m) (serde/maps.scala: Spark's MapKeys / MapValues / MapEntries, sent without a return type): a derived list column
+// of kind 5, a VIEW — a map is laid out as offsets over the entries Struct(key, value), so the list shares the map's offsets and validity and its element column
+// IS the key column, the value column or the entries struct.  Nothing is copied and no kernel runs (exec.cpp extend_derived_map_view).  The argument is a map
+// COLUMN of the chain's source; every consumer of a derived list (size, element_at, array_contains — which is what map_contains_key arrives as —, array_sort,
+// Explode …) then works on the result.
+bool is_map_view_fn(const std::string& f) { return f == "map_keys" || f == "map_values" || f == "map_entries"; }
+ExprP lower_map_view(const ExprP& e) {
+  const std::string& f = e->func;
+  const int op = f == "map_keys" ? 0 : f == "map_values" ? 1 : 2;
+  // (as for array_sort: a join materialises a side whose fold throws, so there this wording never reaches a user)
+  if (!g_derived || !g_source_cols)
+    throw CometError(f + " inside a join's or an aggregate's fused chain is not supported by the MI355X native engine yet (a derived list is computed over the source of a Projection / Filter chain)");
+  if (e->children.size() != 1) throw CometError(f + " expects one argument, got " + std::to_string(e->children.size()));
+  const ExprP& subject = e->children[0];
+  const int nsrc = (int)g_source_cols->size();
+  if (subject->kind != ExprKind::Bound || !subject->has_dtype || subject->dtype.id != TypeId::Map || subject->bound_index < 0 || subject->bound_index >= nsrc || subject->dtype.virt_parent >= 0 ||
+      subject->dtype.kids.size() != 1 || subject->dtype.kids[0].kids.size() != 2)
+    throw CometError(f + " is supported over a map COLUMN of the chain's source (not over a computed map or a map inside a struct) by the MI355X native engine");
+  const DType& entries = subject->dtype.kids[0];
+  if (op != 2 && (entries.kids[0].is_nested() || entries.kids[1].is_nested()))
+    throw CometError(f + " of " + subject->dtype.str() + ": a map with a nested key or a nested value is not supported by the MI355X native engine yet (map_entries passes one through)");
+  DerivedCol dc;
+  dc.kind = 5;
+  dc.op = op;
+  dc.src = subject->bound_index;
+  dc.type = DType::of(TypeId::List);
+  dc.type.kids.assign(1, op == 2 ? entries : entries.kids[(size_t)op]);
+  dc.type.kids[0].virt_parent = dc.type.kids[0].virt_kid = -1;
+  dc.type.kid_names.assign(1, "element");
+  dc.type.kid_nullable.assign(1, op == 1 && entries.kid_nullable.size() == 2 && entries.kid_nullable[1] ? 1 : 0);      // keys and entries are never NULL
+  size_t k = 0;
+  for (; k < g_derived->size(); k++) {
+    const DerivedCol& o = (*g_derived)[k];
+    if (o.kind == 5 && o.src == dc.src && o.op == dc.op) break;
+  }
+  if (k == g_derived->size()) g_derived->push_back(dc);
+  auto b = std::make_shared<Expr>();
+  b->kind = ExprKind::Bound;
+  b->proto_tag = 3;
+  b->bound_index = derived_index(nsrc, k);
+  b->dtype = dc.type;
+  b->has_dtype = true;
+  return b;
+}
 ExprP lower_struct_field(const ExprP& e, const ExprP& child) {
   if (child->kind != ExprKind::Bound || !child->has_dtype || child->dtype.id != TypeId::Struct)
     throw CometError("GetStructField of anything but a struct COLUMN is not supported yet");
@@ -482,6 +532,10 @@ ExprP substitute(const ExprP& e, const std::vector<ExprP>& cols, std::map<const 
     auto n = std::make_shared<Expr>(*e);
     for (auto& c : n->children) c = substitute(c, cols, memo);
     out = lower_list_fn(n);
+  } else if (e->kind == ExprKind::ScalarFunc && is_map_view_fn(e->func)) {
+    auto n = std::make_shared<Expr>(*e);
+    for (auto& c : n->children) c = substitute(c, cols, memo);
+    out = lower_map_view(n);
   } else if (e->kind == ExprKind::Bound) {
     if (e->bound_index < 0 || (size_t)e->bound_index >= cols.size())
       throw CometError("Column index " + std::to_string(e->bound_index) + " is out of bound. Schema has " +
@@ -1877,6 +1931,9 @@ struct Gen {
       for (size_t j = 0; j < in_types.size(); j++)
         if (in_types[j].virt_parent == l.idx && in_types[j].virt_kid == 0 && in_types[(size_t)l.idx].id == TypeId::List) l.elem = (int)j;
       if (l.elem < 0) throw CometError(std::string(who) + ": the elements of " + in_types[(size_t)l.idx].str() + " are not addressable by an expression (lists of flat elements are)");
+      // (map_entries' elements are structs: passed through, exported and exploded, never an operand)
+      if (in_types[(size_t)l.elem].is_nested())
+        throw CometError(std::string(who) + ": the elements of " + in_types[(size_t)l.idx].str() + " are not addressable by an expression by the MI355X native engine (lists of flat elements are)");
       in_used[(size_t)l.elem] = true;
       l.etype = in_types[(size_t)l.elem];
       l.ecol = "prm.in[" + std::to_string(locate(l.elem).first) + "]";
@@ -1929,6 +1986,94 @@ struct Gen {
     stmt(ok + " = " + hit + (in_valid[(size_t)l.elem] ? " && comet::ld_valid(" + l.ecol + ", " + row + ")" : "") + ";");
     std::string v = newvar(rep_ctype(r.rep));
     stmt(v + " = " + ok + " ? " + load_of(l.etype, l.ecol, row) + " : (" + rep_ctype(r.rep) + ")0;");
+    r.v = v;
+    r.ok = ok;
+    return r;
+  }
+
+  // ---- maps: map_extract(m, k) is what m[k] and element_at(m, k) arrive as (serde/maps.scala, planner.rs "map_extract": the reference wraps DataFusion's
+  // one-element list in ListExtract(…, 1, one_based, fail_on_error = false)): the value of the FIRST entry whose key equals k, NULL for a NULL map or key, when no
+  // entry matches and where the value is NULL; it never raises.  The chain's table carries the key and the value column of a map with flat keys and values as
+  // columns of their own (exec.cpp extend_struct_fields: virt_kid 0 and 1 of a Map); device/map_fn.hpp walks row i's entries, one lane per row ----
+  struct MapRef { int idx = -1, key = -1, val = -1; std::string ent, vcol; DType ktype, vtype; };
+  // → `ent`: the entry row (i64) of the hit, -1 when there is none
+  MapRef map_extract_pos(const Expr& e) {
+    if (e.children.size() != 2) throw CometError("map_extract expects two arguments (map, key), got " + std::to_string(e.children.size()));
+    const ExprP& m = e.children[0];
+    if (m->kind != ExprKind::Bound || m->bound_index < 0 || (size_t)m->bound_index >= in_types.size() || in_types[(size_t)m->bound_index].id != TypeId::Map ||
+        in_types[(size_t)m->bound_index].virt_parent >= 0)
+      throw CometError("map_extract is supported over a map COLUMN of the chain's source (not over a computed map or a map inside a struct) by the MI355X native engine");
+    MapRef r;
+    r.idx = m->bound_index;
+    const DType& mt = in_types[(size_t)r.idx];
+    if (mt.kids.size() != 1 || mt.kids[0].kids.size() != 2) throw CometError("map_extract: " + mt.str() + " has no (key, value) entries");
+    const DType &kt = mt.kids[0].kids[0], &vt = mt.kids[0].kids[1];
+    if (kt.is_nested() || vt.is_nested()) throw CometError("map_extract over " + mt.str() + ": a map with a nested key or a nested value is not supported by the MI355X native engine yet");
+    if (kt.is_float())
+      throw CometError("map_extract with " + kt.str() + " keys is not supported by the MI355X native engine (Spark's ordering and an array comparison disagree on -0.0 and NaN keys)");
+    if (kt.id == TypeId::Bytes) throw CometError("map_extract with Binary keys is not supported by the MI355X native engine yet");
+    if (vt.id == TypeId::Bytes) throw CometError("map_extract with Binary values is not supported by the MI355X native engine yet");
+    for (size_t j = 0; j < in_types.size(); j++)
+      if (in_types[j].virt_parent == r.idx && (in_types[j].virt_kid == 0 || in_types[j].virt_kid == 1)) (in_types[j].virt_kid == 0 ? r.key : r.val) = (int)j;
+    if (r.key < 0 || r.val < 0) throw CometError("map_extract: the keys and values of " + mt.str() + " are not addressable by an expression by the MI355X native engine");
+    in_used[(size_t)r.idx] = in_used[(size_t)r.key] = in_used[(size_t)r.val] = true;
+    r.ktype = in_types[(size_t)r.key];
+    r.vtype = in_types[(size_t)r.val];
+    const auto loc = locate(r.idx);
+    const std::string mc = "prm.in[" + std::to_string(loc.first) + "]", kc = "prm.in[" + std::to_string(locate(r.key).first) + "]";
+    r.vcol = "prm.in[" + std::to_string(locate(r.val).first) + "]";
+    const std::string head = mc + ", " + (in_valid[(size_t)r.idx] ? "true" : "false") + ", " + kc + ", " + loc.second + ", ";
+    const ExprP& k = e.children[1];
+    std::string keyok, call;
+    if (kt.id == TypeId::String) {
+      if (k->kind == ExprKind::Literal && k->dtype.id == TypeId::String) {
+        if (k->lit_null) keyok = "false";
+        call = "mf_find_lit(" + head + c_bytes(k->lit_bytes) + ", " + std::to_string(k->lit_bytes.size()) + ")";
+      } else if (is_str_col(k) && in_types[(size_t)k->bound_index].id == TypeId::String) {
+        keyok = str_col_validity(k->bound_index).ok;
+        const auto kloc = locate(k->bound_index);
+        call = "mf_find_row(" + head + "prm.in[" + std::to_string(kloc.first) + "], " + kloc.second + ")";
+      } else if (k->has_dtype && k->dtype.id != TypeId::String && (k->kind == ExprKind::Literal || k->kind == ExprKind::Bound)) {
+        throw CometError("map_extract: the key's type " + k->dtype.str() + " is not the map's key type " + kt.str());
+      } else {
+        throw CometError("map_extract over Utf8 keys is supported with a literal key or a Utf8 COLUMN of the chain's source (not a computed string) by the MI355X native engine");
+      }
+    } else {
+      if (is_str_lit(k) || is_str_col(k)) throw CometError("map_extract: the key's type " + (k->has_dtype ? k->dtype.str() : std::string("Utf8")) + " is not the map's key type " + kt.str());
+      Val key = named(gen(k));
+      DType a = key.t, b = kt;
+      a.virt_parent = a.virt_kid = b.virt_parent = b.virt_kid = -1;
+      if (!(a == b)) throw CometError("map_extract: the key's type " + key.t.str() + " is not the map's key type " + kt.str());
+      const char* how = nullptr;      // device/map_fn.hpp: one instantiation per key representation
+      switch (kt.id) {
+        case TypeId::Bool: how = "MfBool"; break;
+        case TypeId::Int8: how = "MfI8"; break;
+        case TypeId::Int16: how = "MfI16"; break;
+        case TypeId::Int32: case TypeId::Date: how = "MfI32"; break;
+        case TypeId::Int64: case TypeId::Timestamp: case TypeId::TimestampNtz: how = "MfI64"; break;
+        case TypeId::Decimal: how = kt.precision <= 18 ? "MfDec64" : "MfDec128"; break;
+        default: throw CometError("map_extract with " + kt.str() + " keys is not supported by the MI355X native engine yet");
+      }
+      keyok = key.ok;
+      call = std::string("mf_find<") + how + ">(" + head + key.v + ")";
+    }
+    g_uses_map_fn = true;
+    r.ent = newvar("i64");
+    stmt(r.ent + " = " + (keyok.empty() ? call : keyok == "false" ? std::string("(i64)-1") : "(" + keyok + " ? " + call + " : (i64)-1)") + ";");
+    return r;
+  }
+  Val map_extract(const Expr& e) {
+    MapRef m = map_extract_pos(e);
+    if (m.vtype.id == TypeId::String) throw CometError("a Utf8 value of map_extract is supported as an OUTPUT column only (not as an operand) by the MI355X native engine");
+    Val r;
+    r.t = m.vtype;
+    r.t.virt_parent = r.t.virt_kid = -1;
+    r.rep = rep_for_type(r.t);
+    r.maxabs = type_maxabs(r.t);
+    const std::string ok = newvar("bool");
+    stmt(ok + " = " + m.ent + " >= 0" + (in_valid[(size_t)m.val] ? " && comet::ld_valid(" + m.vcol + ", " + m.ent + ")" : "") + ";");
+    const std::string v = newvar(rep_ctype(r.rep));
+    stmt(v + " = " + ok + " ? " + load_of(m.vtype, m.vcol, m.ent) + " : (" + rep_ctype(r.rep) + ")0;");
     r.v = v;
     r.ok = ok;
     return r;
@@ -2293,6 +2438,7 @@ struct Gen {
       r.ok = ok;
       return r;
     }
+    if (f == "map_extract") return map_extract(e);
     if (f == "array_min" || f == "array_max") {
       // Spark's ArrayMin / ArrayMax: the least / greatest non-NULL element; NULL for a NULL list, an empty list and a list of NULL elements only
       if (e.children.size() != 1) throw CometError(f + " expects one argument");
@@ -3696,15 +3842,22 @@ std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool
     valid_all.push_back(valid_all.at((size_t)dc.src));      // (a kind 4 column's source may be a derived column before it)
     if (dc.kind == 3) continue;
     bool elem_valid = false;      // split's pieces are never NULL; a sorted / distinct list's elements are NULL where its source's are
+    // (virt_kid 0 of a List is its element column; of a Map its key column, and virt_kid 1 its value column)
     if (dc.kind == 4)
       for (size_t j = 0; j + 1 < d.in_types.size(); j++)
-        if (d.in_types[j].virt_parent == dc.src && d.in_types[j].virt_kid == 0) elem_valid = valid_all[j];
+        if (d.in_types[j].virt_parent == dc.src && d.in_types[j].virt_kid == 0 && d.in_types[(size_t)dc.src].id == TypeId::List) elem_valid = valid_all[j];
+    // map_values: keys and entries are never NULL; values carry validity bits whenever the map's type lets them be NULL (the plan does not see the value column
+    // itself unless it holds a lookup, so the executor hands the elements over with a bitmap in any case — extend_derived_map_view)
+    if (dc.kind == 5 && dc.op == 1) elem_valid = !dc.type.kid_nullable.empty() && dc.type.kid_nullable[0] != 0;
     DType et = dc.type.kids[0];      // … and its element column behind it, addressable like the element column of a source list (list_ref)
     et.virt_parent = (int)d.in_types.size() - 1;
     et.virt_kid = 0;
     d.in_types.push_back(et);
     valid_all.push_back(elem_valid);
   }
+  for (auto& dc : d.derived)
+    if (dc.kind == 5 && under_agg)
+      throw CometError(std::string(dc.op == 0 ? "map_keys" : dc.op == 1 ? "map_values" : "map_entries") + " inside an aggregate's chain is not supported by the MI355X native engine yet (project it below the aggregate)");
   for (auto& dc : d.derived)
     if (dc.kind == 4 && under_agg)
       throw CometError(std::string(dc.op == 0 ? "array_sort" : "array_distinct") + " inside an aggregate's chain is not supported by the MI355X native engine yet (project it below the aggregate)");
@@ -3758,6 +3911,23 @@ struct OutputSink {
       oc.nullable = true;
       oc.gather_src = l.elem;
       return add(c, v, oc, "Utf8 (an element gathered from column " + std::to_string(l.elem) + ")");
+    }
+    if (c->kind == ExprKind::ScalarFunc && c->func == "map_extract" && !c->children.empty() && is_source(c->children[0], lsrc) && d.in_types[lsrc].id == TypeId::Map &&
+        d.in_types[lsrc].kids.size() == 1 && d.in_types[lsrc].kids[0].kids.size() == 2 && d.in_types[lsrc].kids[0].kids[1].id == TypeId::String) {
+      // m[k] of a map with Utf8 values: the VALUE column's row travels, the executor gathers the string
+      Gen::MapRef m = ge.map_extract_pos(*c);
+      Val v;
+      v.t = DType::of(TypeId::String);
+      v.rep = Rep::I64;
+      const std::string hit = "(" + m.ent + " >= 0" + (valid[(size_t)m.val] ? " && comet::ld_valid(" + m.vcol + ", " + m.ent + ")" : "") + ")";
+      v.v = "(" + m.ent + " >= 0 ? " + m.ent + " : (i64)0)";
+      v.ok = hit;
+      v = ge.named(v);
+      OutCol oc;
+      oc.type = v.t;
+      oc.nullable = true;
+      oc.gather_src = m.val;
+      return add(c, v, oc, "Utf8 (a map's value gathered from column " + std::to_string(m.val) + ")");
     }
     // (… and so is a nested column: its rows are gathered by the executor, children and all — exec.cpp take_nested)
     if (is_source(c, src) && (d.in_types[src].id == TypeId::String || d.in_types[src].id == TypeId::Bytes || d.in_types[src].is_nested())) {

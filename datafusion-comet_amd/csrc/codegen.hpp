@@ -45,8 +45,11 @@ struct OutCol {
 // which the chain passes through by row index like any nested column.
 struct DerivedCol {
   int kind = 0;                     // 1: split, 2: regexp_extract_all (two columns each: the list, then its elements), 3: a string function → Utf8 (one column),
-                                    // 4: array_sort / array_distinct of a list column (two columns, as split)
-  int op = 0;                       // kind 3: device/strfn.hpp's operation (SF_REVERSE …), or kDerivedRegexpReplace; kind 4: device/list_fn.hpp's LF_OP_SORT / LF_OP_DISTINCT
+                                    // 4: array_sort / array_distinct of a list column (two columns, as split),
+                                    // 5: map_keys / map_values / map_entries of a map column of the source — a view: the list shares the map's offsets and validity, its
+                                    //    elements are the key column, the value column or the entries struct (two columns, as split; nothing is copied)
+  int op = 0;                       // kind 3: device/strfn.hpp's operation (SF_REVERSE …), or kDerivedRegexpReplace; kind 4: device/list_fn.hpp's LF_OP_SORT / LF_OP_DISTINCT;
+                                    // kind 5: 0 keys, 1 values, 2 entries
   std::string arg_a, arg_b;         // kind 3: the literal arguments' bytes (regexp_replace: the pattern and the replacement as written)
   long long arg_k = 0;              // kind 3: the integer argument; kind 4 sort: LF_DESC | LF_NULLS_LAST
   int columns() const { return kind == 3 ? 1 : 2; }

@@ -23,10 +23,18 @@ namespace comet {
 // GetStructField folds into (codegen.cpp lower_struct_field).  A field's validity already says NULL where its struct is NULL (the Parquet
 // scan derives both from one definition level), so the field column is the field's view as it is.
 // … and the element column of every List of flat elements (virt_kid 0 of a List: what ListExtract / array_contains address, codegen.cpp list_ref).
+// … and the key and the value column of every Map with a flat key and a flat value (virt_kid 0 and 1 of a Map: what map_extract walks, codegen.cpp
+// map_extract_pos).  Whoever means "a list's elements" by virt_kid 0 checks that the parent is a List.  `with_maps`: only a plan that holds a
+// map_extract (Operator::looks_into_maps) gets them; every other plan sees the table it saw before maps were addressable, so what it leaves free of the kernel's
+// COMET_MAX_IN argument slots for derived columns and bloom filters is unchanged.  Where they are added they come LAST, behind every field and element column, and
+// a map gets its two only while they fit the slots; a lookup in a map that got none is refused by name at createPlan.
 static bool list_of_flat(const DType& t) { return t.id == TypeId::List && t.kids.size() == 1 && !t.kids[0].is_nested(); }
-DevTable extend_struct_fields(const DevTable& in) {
+static bool map_of_flat(const DType& t) {
+  return t.id == TypeId::Map && t.kids.size() == 1 && t.kids[0].id == TypeId::Struct && t.kids[0].kids.size() == 2 && !t.kids[0].kids[0].is_nested() && !t.kids[0].kids[1].is_nested();
+}
+DevTable extend_struct_fields(const DevTable& in, bool with_maps) {
   bool any = false;
-  for (auto& t : in.types) any |= t.id == TypeId::Struct || list_of_flat(t);
+  for (auto& t : in.types) any |= t.id == TypeId::Struct || list_of_flat(t) || (with_maps && map_of_flat(t));
   if (!any) return in;
   DevTable x = in;
   for (size_t i = 0; i < in.types.size(); i++) {
@@ -49,10 +57,25 @@ DevTable extend_struct_fields(const DevTable& in) {
       x.has_valid.push_back(k < in.cols[i].kid_has_valid.size() && in.cols[i].kid_has_valid[k]);
     }
   }
+  for (size_t i = 0; i < in.types.size(); i++) {
+    if (with_maps && map_of_flat(in.types[i]) && x.types.size() + 2 <= COMET_MAX_IN) {
+      // (always two columns, as extend_struct_field_types promises the planner: a map column that came without its entries — an empty table — gets empty ones)
+      const bool shaped = in.cols[i].kids.size() == 1 && in.cols[i].kids[0].kids.size() == 2;
+      if (!shaped && in.rows > 0) throw CometError("internal: a map column without (key, value) entries");
+      for (size_t k = 0; k < 2; k++) {
+        DType kt = in.types[i].kids[0].kids[k];
+        kt.virt_parent = (int)i;
+        kt.virt_kid = (int)k;
+        x.types.push_back(kt);
+        x.cols.push_back(shaped ? in.cols[i].kids[0].kids[k] : DeviceColumnView());
+        x.has_valid.push_back(shaped && k < in.cols[i].kids[0].kid_has_valid.size() && in.cols[i].kids[0].kid_has_valid[k]);
+      }
+    }
+  }
   return x;
 }
 
-std::vector<DType> extend_struct_field_types(const std::vector<DType>& types) {
+std::vector<DType> extend_struct_field_types(const std::vector<DType>& types, bool with_maps) {
   std::vector<DType> x = types;
   for (size_t i = 0; i < types.size(); i++) {
     if (list_of_flat(types[i])) {
@@ -65,6 +88,15 @@ std::vector<DType> extend_struct_field_types(const std::vector<DType>& types) {
     if (types[i].id != TypeId::Struct) continue;
     for (size_t k = 0; k < types[i].kids.size(); k++) {
       DType kt = types[i].kids[k];
+      kt.virt_parent = (int)i;
+      kt.virt_kid = (int)k;
+      x.push_back(kt);
+    }
+  }
+  for (size_t i = 0; i < types.size(); i++) {
+    if (!with_maps || !map_of_flat(types[i]) || x.size() + 2 > COMET_MAX_IN) continue;
+    for (size_t k = 0; k < 2; k++) {
+      DType kt = types[i].kids[0].kids[k];
       kt.virt_parent = (int)i;
       kt.virt_kid = (int)k;
       x.push_back(kt);
@@ -346,7 +378,7 @@ ExecutionContext::ExecutionContext(OperatorP plan, uint64_t plan_hash, std::vect
     // than the packed 15 bytes be swapped for representative row indices (prepare_dict_keys)
     if (sink_ == SinkKind::AggGrouped && !pv->desc.str_key_cols.empty()) has_join_ = true;
   } else {
-    in_types_ = extend_struct_field_types(infer_schema(*root_source_));      // (a struct's fields are columns of their own to the chain above: GetStructField)
+    in_types_ = extend_struct_field_types(infer_schema(*root_source_), plan_->looks_into_maps);      // (a struct's fields are columns of their own to the chain above: GetStructField)
     if (plan_.get() != root_source_) {
       std::vector<bool> none(in_types_.size(), false);
       auto pv = planned_variant(*plan_, plan_hash_, none, false, &in_types_);
@@ -600,7 +632,7 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
       pr->children.push_back(sc);
       pr->project_list = op.project_list;
       node_id_[pr.get()] = (int)node_id_.size();
-      std::vector<DType> ext = extend_struct_field_types(st);
+      std::vector<DType> ext = extend_struct_field_types(st, plan_->looks_into_maps);
       std::vector<bool> none(ext.size(), false);
       PipelineDesc d = generate_pipeline(*pr, none, &ext);
       if (compile_in_infer_) jit_compile(d.source);
@@ -784,7 +816,7 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
       pr->children.push_back(sc);
       pr->project_list = op.agg_exprs[0].children;
       node_id_[pr.get()] = (int)node_id_.size();
-      std::vector<DType> ext = extend_struct_field_types(st);
+      std::vector<DType> ext = extend_struct_field_types(st, plan_->looks_into_maps);
       std::vector<bool> none(ext.size(), false);
       PipelineDesc d = generate_pipeline(*pr, none, &ext);
       const DType& ct = d.out_cols.at(0).type;
@@ -891,7 +923,7 @@ std::vector<DType> ExecutionContext::infer_schema(const Operator& op) {
     if (src->children.size() != 1) throw CometError(std::string(op_name(src->proto_tag)) + " expects exactly one child");
     src = src->children[0].get();
   } while (!is_source(*src, &op));
-  std::vector<DType> st = extend_struct_field_types(infer_schema(*src));      // (as run_chain_to_device will see the source: struct fields as columns of their own)
+  std::vector<DType> st = extend_struct_field_types(infer_schema(*src), plan_->looks_into_maps);      // (as run_chain_to_device will see the source: struct fields as columns of their own)
   std::vector<bool> none(st.size(), false);
   PipelineDesc d = generate_pipeline(op, none, &st);
   if (compile_in_infer_) jit_compile(d.source);
@@ -1588,7 +1620,7 @@ void ExecutionContext::extend_derived_list_fn(DevTable& in, const DerivedCol& dc
   if (dc.src < 0 || (size_t)dc.src >= in.cols.size() || in.types[(size_t)dc.src].id != TypeId::List || dc.type.kids.size() != 1) throw CometError("internal: unknown derived column");
   int se = -1;
   for (size_t j = 0; j < in.types.size(); j++)
-    if (in.types[j].virt_parent == dc.src && in.types[j].virt_kid == 0) se = (int)j;
+    if (in.types[j].virt_parent == dc.src && in.types[j].virt_kid == 0) se = (int)j;      // (dc.src is a List: virt_kid 0 is its element column, not a map's keys)
   const int kind = list_fn_elem_kind(dc.type.kids[0]);
   if (se < 0 || kind < 0) throw CometError("internal: " + who + ": the list's elements are not a column of the chain's table");
   const DeviceColumnView sc = in.cols[(size_t)dc.src], ec = in.cols[(size_t)se];
@@ -1674,6 +1706,51 @@ void ExecutionContext::extend_derived_list_fn(DevTable& in, const DerivedCol& dc
   in.has_valid.push_back(el_hv);
 }
 
+// A derived list column of kind 5: map_keys / map_values / map_entries of a map column of the source.  A view: the list column gets the map's offsets and
+// validity buffers, the element column is the key column, the value column or the entries struct as it stands.  No copy, no kernel, nothing read back (map_values of a batch whose values hold no NULL gets a validity bitmap of all ones, below).
+// The sliced-column rule of kind 4 holds: a non-zero Arrow offset on the map or on the elements is refused by name (no producer in this engine delivers one).
+void ExecutionContext::extend_derived_map_view(DevTable& in, const DerivedCol& dc) {
+  const std::string who = dc.op == 0 ? "map_keys" : dc.op == 1 ? "map_values" : "map_entries";
+  if (dc.src < 0 || (size_t)dc.src >= in.cols.size() || in.types[(size_t)dc.src].id != TypeId::Map || dc.type.kids.size() != 1 || dc.op < 0 || dc.op > 2) throw CometError("internal: unknown derived column");
+  const DeviceColumnView& sc = in.cols[(size_t)dc.src];
+  if (sc.kids.size() != 1 || sc.kids[0].kids.size() != 2) throw CometError("internal: " + who + ": the map column has no (key, value) entries");
+  const DeviceColumnView& entries = sc.kids[0];
+  DeviceColumnView el = dc.op == 2 ? entries : entries.kids[(size_t)dc.op];
+  bool el_hv = dc.op == 2 ? (!sc.kid_has_valid.empty() && sc.kid_has_valid[0]) : ((size_t)dc.op < entries.kid_has_valid.size() && entries.kid_has_valid[(size_t)dc.op]);
+  if (in.rows > 0 && !sc.data) throw CometError(who + " over a map column without offsets is not supported");
+  if (sc.offset != 0 || entries.offset != 0 || el.offset != 0)
+    throw CometError(who + " over a sliced map column (a non-zero Arrow offset on the map or on its entries) is not supported by the MI355X native engine");
+  // map_values of a map whose type lets values be NULL: the chain was planned with validity bits on the elements (append_derived_columns cannot see whether this
+  // batch's value column has any), so a value column without a bitmap gets one of all ones — kid_rows / 8 bytes, the one thing this view ever writes
+  const bool planned_valid = dc.op == 1 && !dc.type.kid_nullable.empty() && dc.type.kid_nullable[0] != 0;
+  if (planned_valid && !el_hv) {
+    auto ones = std::make_shared<DevBuf>();
+    const size_t nb = (size_t)((sc.kid_rows + 7) / 8);
+    ones->ensure(nb + 16);
+    HIP_CHECK(hipMemsetAsync(ones->p, 0xff, nb + 16, stream_));
+    el.valid = (const uint8_t*)ones->p;
+    el_hv = true;
+    in.owners.push_back(ones);
+  } else if (dc.op == 1 && !planned_valid) {
+    el_hv = false;      // (a map whose values cannot be NULL: planned without validity bits)
+  }
+  DeviceColumnView lv;
+  lv.data = sc.data;
+  lv.valid = sc.valid;
+  lv.kids.assign(1, el);
+  lv.kid_has_valid.assign(1, el_hv ? 1 : 0);
+  lv.kid_rows = sc.kid_rows;
+  in.types.push_back(dc.type);
+  in.cols.push_back(lv);
+  in.has_valid.push_back(in.has_valid[(size_t)dc.src]);
+  DType et = dc.type.kids[0];      // the elements as a column of their own, as split's are
+  et.virt_parent = (int)in.types.size() - 1;
+  et.virt_kid = 0;
+  in.types.push_back(et);
+  in.cols.push_back(el);
+  in.has_valid.push_back(el_hv);
+}
+
 // The chain's derived columns (codegen.hpp DerivedCol) computed over its source table and appended to it.  split: two passes of the matcher per
 // row (regex_kernels.hip) — the pieces counted, a prefix sum, every piece described as a view of its source value — and the element column
 // assembled from the views like every string view's result.
@@ -1681,6 +1758,7 @@ void ExecutionContext::extend_derived(DevTable& in, const std::vector<DerivedCol
   for (const DerivedCol& dc : derived) {
     if (dc.kind == 3) { extend_derived_strfn(in, dc); continue; }
     if (dc.kind == 4) { extend_derived_list_fn(in, dc); continue; }
+    if (dc.kind == 5) { extend_derived_map_view(in, dc); continue; }
     if ((dc.kind != 1 && dc.kind != 2) || dc.src < 0 || (size_t)dc.src >= in.cols.size()) throw CometError("internal: unknown derived column");
     const DeviceColumnView sc = in.cols[(size_t)dc.src];
     const bool hv = in.has_valid[(size_t)dc.src];
@@ -1762,7 +1840,7 @@ void ExecutionContext::extend_derived(DevTable& in, const std::vector<DerivedCol
 
 // Filter/Project chain `top` over the resident table `in` → resident table
 DevTable ExecutionContext::run_chain_to_device(const Operator& top, const DevTable& in_plain) {
-  DevTable in = extend_struct_fields(in_plain);
+  DevTable in = extend_struct_fields(in_plain, plan_->looks_into_maps);
   if (in.cols.size() > COMET_MAX_IN) throw CometError("too many columns (struct fields included) for one GPU pipeline");
   auto pv = planned_variant(top, plan_hash_ ^ (0x9E3779B97F4A7C15ull * (uint64_t)(node_id_[&top] + 1)), in.has_valid, true, &in.types);
   if (pv->desc.sink != SinkKind::Output) throw CometError("internal: run_chain_to_device on an aggregate chain");
@@ -2197,7 +2275,7 @@ void ExecutionContext::table_to_host_batches(const DevTable& t) {
 
 void ExecutionContext::run_to_completion() {
   if (has_join_) {
-    DevTable src = extend_struct_fields(materialize(*root_source_));
+    DevTable src = extend_struct_fields(materialize(*root_source_), plan_->looks_into_maps);
     if (plan_.get() == root_source_) throw CometError("internal: bare join root");
     if (sink_ == SinkKind::AggGrouped) prepare_dict_keys(src);
     single_chunk_hint_ = true;      // (the join's output is the aggregate's whole input)

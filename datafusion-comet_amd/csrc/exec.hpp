@@ -270,6 +270,7 @@ class ExecutionContext {
   void extend_derived(DevTable& in, const std::vector<DerivedCol>& derived);
   void extend_derived_strfn(DevTable& in, const DerivedCol& dc);
   void extend_derived_list_fn(DevTable& in, const DerivedCol& dc);
+  void extend_derived_map_view(DevTable& in, const DerivedCol& dc);
   void list_fn_sort_route(const DerivedCol& dc, const int32_t* offs, int64_t rows, int64_t hi, const DeviceColumnView& ec, bool ehv, uint32_t* out);
   DevTable hash_join(const Operator& j, const DevTable& l, const DevTable& r);
   DevTable hash_join_impl(const Operator& node, const Operator& j, const DevTable& l, const DevTable& r, const std::string& key_suffix,

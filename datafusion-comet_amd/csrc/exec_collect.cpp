@@ -29,7 +29,7 @@ extern "C" int comet_launch_collect_index(const uint32_t* keep, const int32_t* C
 
 namespace comet {
 
-std::vector<DType> extend_struct_field_types(const std::vector<DType>& types);      // exec.cpp
+std::vector<DType> extend_struct_field_types(const std::vector<DType>& types, bool with_maps);      // exec.cpp
 
 namespace {
 
@@ -139,7 +139,7 @@ std::vector<DType> ExecutionContext::plan_collect(const Operator& op) {
     pr->children.push_back(sc);
     pr->project_list = list;
     node_id_[pr.get()] = (int)node_id_.size();
-    std::vector<DType> ext = extend_struct_field_types(st);
+    std::vector<DType> ext = extend_struct_field_types(st, plan_->looks_into_maps);
     std::vector<bool> none(ext.size(), false);
     PipelineDesc d = generate_pipeline(*pr, none, &ext);
     if (compile_in_infer_) jit_compile(d.source);

@@ -26,7 +26,7 @@ extern "C" int comet_launch_pct_pick(const double* vals, const uint32_t* first, 
 
 namespace comet {
 
-std::vector<DType> extend_struct_field_types(const std::vector<DType>& types);      // exec.cpp
+std::vector<DType> extend_struct_field_types(const std::vector<DType>& types, bool with_maps);      // exec.cpp
 
 namespace {
 
@@ -155,7 +155,7 @@ std::vector<DType> ExecutionContext::plan_percentile(const Operator& op) {
     pr->children.push_back(scan_of(st));
     pr->project_list = list;
     node_id_[pr.get()] = (int)node_id_.size();
-    std::vector<DType> ext = extend_struct_field_types(st);
+    std::vector<DType> ext = extend_struct_field_types(st, plan_->looks_into_maps);
     std::vector<bool> none(ext.size(), false);
     PipelineDesc d = generate_pipeline(*pr, none, &ext);
     if (compile_in_infer_) jit_compile(d.source);

@@ -224,6 +224,7 @@ struct Operator {
   uint32_t plan_id = 0;
   std::vector<std::string> sql_text_pool;      // (root only) the SQL texts QueryContext.sql_text_idx points into
   std::vector<ExprP> subqueries;               // (root only) every Subquery expression of the plan (resolved into literals at the first executePlan)
+  bool looks_into_maps = false;                 // (every node of a decoded plan) some expression of the plan is a map_extract: the chains' tables then carry the maps' key and value columns (exec.cpp extend_struct_fields)
   bool reader_api = false;                      // NativeScan built by the parquet.Native record-batch reader, not decoded from a plan
   std::vector<OperatorP> children;
   // Scan

@@ -1,6 +1,7 @@
 // Hand-written proto3 wire decoder for Comet's plan messages (no protoc / libprotobuf in this image).
 // Field numbers follow native/proto/src/proto/{operator,expr,types,literal,config,metric}.proto; the
 // reference decodes the same bytes with prost in native/core/src/execution/serde.rs:45-58.
+#include <functional>
 #include <cstdlib>
 #include <cstring>
 
@@ -159,6 +160,8 @@ DType decode_datatype(Reader r) {
   return d;
 }
 
+// whether an expression of the plan being decoded is a map_extract (Operator::looks_into_maps)
+thread_local bool* g_decoded_map_lookup = nullptr;
 ExprP decode_expr(Reader r);
 
 // BigInteger.toByteArray: big-endian two's complement (spark/.../serde/literals.scala:92-95;
@@ -264,7 +267,7 @@ void decode_expr_body(Reader r, Expr& e) {
         break;
       case ExprKind::ScalarFunc:
         // ScalarFunc{func=1, args=2, return_type=3, fail_on_error=4} (expr.proto:466-471)
-        if (f == 1 && wt == 2) { e.func = r.bytes(); handled = true; }
+        if (f == 1 && wt == 2) { e.func = r.bytes(); handled = true; if (g_decoded_map_lookup && e.func == "map_extract") *g_decoded_map_lookup = true; }
         else if (f == 2 && wt == 2) { e.children.push_back(decode_expr(r.sub())); handled = true; }
         else if (f == 3 && wt == 2) { e.dtype = decode_datatype(r.sub()); e.has_dtype = true; handled = true; }
         else if (f == 4 && wt == 0) { e.fail_on_error = r.varint() != 0; handled = true; }
@@ -867,8 +870,15 @@ OperatorP decode_operator(const uint8_t* data, size_t len) {
   std::vector<ExprP> subqueries;
   struct SubScope { std::vector<ExprP>* prev; ~SubScope() { g_decoded_subqueries = prev; } } sub_scope{g_decoded_subqueries};
   g_decoded_subqueries = &subqueries;
+  bool map_lookup = false;
+  struct MapScope { bool* prev; ~MapScope() { g_decoded_map_lookup = prev; } } map_scope{g_decoded_map_lookup};
+  g_decoded_map_lookup = &map_lookup;
   OperatorP root = decode_operator_r(Reader(data, len));
   root->subqueries = std::move(subqueries);
+  if (map_lookup) {      // (on every node: an aggregate below other operators runs as a context of its own over its sub-tree)
+    std::function<void(Operator&)> mark = [&](Operator& op) { op.looks_into_maps = true; for (auto& c : op.children) if (c) mark(*c); };
+    mark(*root);
+  }
   // QueryContext.sql_text_idx → the root's pool (a query text shared by many expressions travels once per plan, expr.proto:137-141).  An index
   // outside the pool keeps the context's own sql_text, as the reference does ("warn rather than fail: a degraded error message is better
   // than a failed query", planner.rs:329-343).

@@ -452,6 +452,27 @@ def array_position(child: Expr, key: Expr) -> Expr:
     return scalar_func("spark_array_position", [child, key])
 
 
+def map_keys(m: Expr) -> Expr:
+    """MapKeys(m): ScalarFunc map_keys, no return type (serde/maps.scala)"""
+    return scalar_func("map_keys", [m])
+
+
+def map_values(m: Expr) -> Expr:
+    """MapValues(m): ScalarFunc map_values"""
+    return scalar_func("map_values", [m])
+
+
+def map_entries(m: Expr) -> Expr:
+    """MapEntries(m): ScalarFunc map_entries → List<Struct<key, value>>"""
+    return scalar_func("map_entries", [m])
+
+
+def map_extract(m: Expr, key: Expr) -> Expr:
+    """GetMapValue (m[k]) and ElementAt over a map: ScalarFunc map_extract(m, k) — the value or NULL, it never raises.  (MapContainsKey never arrives: Spark
+    replaces it with ArrayContains(MapKeys(m), k).)"""
+    return scalar_func("map_extract", [m, key])
+
+
 def unscaled_value(child: Expr) -> Expr:
     """UnscaledValue(decimal(p <= 18, s)) -> Long, what Spark's DecimalAggregates rule puts under sum / avg of short decimals (decimalExpressions.scala:27-45)."""
     return scalar_func("unscaled_value", [child], T_INT64)

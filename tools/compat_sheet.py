@@ -60,7 +60,7 @@ OPERATORS = [
     ("takeOrderedAndProject", True, "Sort with fetch + Projection"), ("collectLimit", True, "Limit"),
     ("broadcastExchange", True, "JVM-side operator (no native plan node)"), ("coalesce", True, "JVM-side operator (no native plan node)"),
     ("union", True, "JVM-side operator: its children are separate native plans"),
-    ("explode", True, "Explode: explode / posexplode [_outer] of a list COLUMN (any element type); computed arrays and maps are refused at createPlan"), ("sample", False, "Sample (Spark's XORShift sequence)"), ("localTableScan", False, "off by default in the reference too"),
+    ("explode", True, "Explode: explode / posexplode [_outer] of a list COLUMN (any element type); computed arrays and maps are refused at createPlan (the JVM never sends an Explode of a map; `explode(map_entries(m))` is an Explode of a list and runs)"), ("sample", False, "Sample (Spark's XORShift sequence)"), ("localTableScan", False, "off by default in the reference too"),
 ]
 OTHER_KEYS = [
     ("spark.comet.scan.icebergNative.enabled", "false", "IcebergScan is not implemented"),
@@ -78,6 +78,7 @@ def probes():
     i32, i64, f64, dec, s, d, b = (S.col(0, S.T_INT32), S.col(1, S.T_INT64), S.col(2, S.T_DOUBLE), S.col(3, D), S.col(4, S.T_STRING), S.col(5, S.T_DATE), S.col(6, S.T_BOOL))
     L = S.lit
     f = S.scalar_func
+    MSL = S.map_type(S.T_STRING, S.T_INT64)      # (the probe plan's ninth Scan field)
     P = {
         "Literal": (L(1, S.T_INT32), ""), "AttributeReference": (i32, "BoundReference"), "Alias": (i32, "serialized as its child"),
         "KnownNotNull": (i32, "serialized as its child"), "KnownNullable": (i32, "serialized as its child"),
@@ -127,7 +128,7 @@ def probes():
         "SortOrder": (i32, "inside Sort / Window / SortMergeJoin / range partitioning"),
         "Size": (f("size", [S.col(7, S.list_type(S.T_INT64))], S.T_INT32), "of a list / map COLUMN (-1 for NULL; the JVM's CASE WHEN around it for sizeOfNull = false runs too)"),
         "GetArrayItem": (S.list_extract(S.col(7, S.list_type(S.T_INT64)), L(0, S.T_INT32)), "ListExtract over a list COLUMN of flat elements (a split's result too); string elements as output columns; ANSI errors as the reference's"),
-        "ElementAt": (S.list_extract(S.col(7, S.list_type(S.T_INT64)), L(-1, S.T_INT32), one_based=True), "arrays (ListExtract, one-based, negative from the end); maps are refused"),
+        "ElementAt": (S.list_extract(S.col(7, S.list_type(S.T_INT64)), L(-1, S.T_INT32), one_based=True), "arrays (ListExtract, one-based, negative from the end); over a map it arrives as `map_extract` and runs as GetMapValue does"),
         "ArrayContains": (f("array_contains", [S.col(7, S.list_type(S.T_INT64)), L(3, S.T_INT64)], S.T_BOOL), "list COLUMN of integers / dates / decimals(<= 18) / booleans with a key of that type; lists of strings with a literal key"),
         "SortArray": (S.sort_array(S.col(7, S.list_type(S.T_INT64))),
                       "`array_sort(arr, 'ASC' | 'DESC', 'NULLS FIRST' | 'NULLS LAST')`: of a list COLUMN or a derived list (a split's, a collect's, another list function's result) of Boolean / integers / "
@@ -136,6 +137,14 @@ def probes():
         "ArrayMin": (S.array_min(S.col(7, S.list_type(S.T_INT64))), "of a list COLUMN or a derived list of Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal elements, any length; Utf8 is refused (`sort_array(x)[0]` serves)"),
         "ArrayMax": (S.array_max(S.col(7, S.list_type(S.T_INT64))), "as ArrayMin"),
         "ArrayPosition": (S.array_position(S.col(7, S.list_type(S.T_INT64)), L(3, S.T_INT64)), "`spark_array_position` → Int64: elements of Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal of any precision (beyond 18 digits compared as 128-bit values) with a key of the element's type, literal or column; lists of strings with a literal key"),
+        "GetMapValue": (S.map_extract(S.col(8, MSL), L("k", S.T_STRING)),
+                        "`map_extract(m, k)` — `m[k]` and `element_at(m, k)`: the value of the first entry whose key equals k, NULL for a NULL map / key and when there is none, never an error; "
+                        "a map COLUMN of the chain's source with Boolean / integer / Date / Timestamp / TimestampNTZ / Decimal (any precision) / Utf8 keys, the key a literal or a column of "
+                        "exactly that type; values of every flat fixed-width type, Utf8 values as output columns (§4)"),
+        "MapKeys": (S.map_keys(S.col(8, MSL)), "of a map COLUMN of the chain's source with flat keys and values: a derived list that shares the map's offsets and validity, nothing is copied; every "
+                                                "list function works on it (`map_contains_key(m, k)` arrives as `array_contains(map_keys(m), k)`) (§4)"),
+        "MapValues": (S.map_values(S.col(8, MSL)), "as MapKeys; floats bit for bit"),
+        "MapEntries": (S.map_entries(S.col(8, MSL)), "as MapKeys, of any map column the engine passes through: `List<Struct<key, value>>`, passed through, exported and exploded"),
         "Reverse": (f("reverse", [s], S.T_STRING), "of a Utf8 COLUMN: a derived column of the chain's source (usable as an operand, any length); arrays are refused"),
         "StringRepeat": (f("repeat", [s, L(2, S.T_INT64)], S.T_STRING), "literal count >= 0; derived column"), "StringReplace": (f("replace", [s, L("a", S.T_STRING), L("b", S.T_STRING)], S.T_STRING), "under allowIncompatible (Rust's str::replace for an empty search string); literal arguments; derived column"),
         "SubstringIndex": (f("substring_index", [s, L(".", S.T_STRING), L(2, S.T_INT64)], S.T_STRING), "literal delimiter and count; derived column"),
@@ -213,7 +222,7 @@ ACCEPTED_AGGREGATES = {"Sum": "integers (LEGACY / ANSI / TRY), decimals, Float64
 
 def probe_plan(expr):
     from datafusion_comet_amd import serde as S
-    fields = [S.T_INT32, S.T_INT64, S.T_DOUBLE, S.decimal(12, 2), S.T_STRING, S.T_DATE, S.T_BOOL, S.list_type(S.T_INT64)]
+    fields = [S.T_INT32, S.T_INT64, S.T_DOUBLE, S.decimal(12, 2), S.T_STRING, S.T_DATE, S.T_BOOL, S.list_type(S.T_INT64), S.map_type(S.T_STRING, S.T_INT64)]
     return S.project(S.scan(fields), [expr])
 
 
@@ -316,8 +325,9 @@ def render() -> str:
     w("* Nested types: struct-of-flat, list-of-flat, list-of-flat-struct and map columns are read from Parquet, passed through Filter / Projection / Sort /")
     w("  Limit / ShuffleWriter, taken apart by `GetStructField` and exported; struct / list columns of any depth arrive through Scan / ShuffleScan inputs;")
     w("  `Explode` of a list column runs; `size`, `arr[i]` / `element_at`, `array_contains`, `sort_array`, `array_distinct`, `array_min` / `array_max` and `array_position` over a")
-    w("  list COLUMN of flat elements run; deeper trees in the Parquet scan, `Explode` of a map,")
-    w("  the other array / map functions and everything that builds a struct / an array / a map are refused.")
+    w("  list COLUMN of flat elements run; `m[k]` / `element_at(m, k)`, `map_keys`, `map_values`, `map_entries` and `map_contains_key` over a map COLUMN run;")
+    w("  deeper trees in the Parquet scan, `Explode` of a map (the JVM never sends one), the other array / map functions (`map_from_arrays`, `map_from_entries`, `map_concat`,")
+    w("  `str_to_map`, the lambda functions) and everything that builds a struct / an array / a map are refused.")
     w("  Parquet: TIMESTAMP(NANOS) / TIME, encrypted files.")
     w("* `SortArray`, `ArrayDistinct`, `ArrayMin`, `ArrayMax`, `ArrayPosition`: Float32 / Float64 elements (Spark and the reference disagree on signed zeros there, the")
     w("  reference's own `sort_array.sql` ignores those cases); Binary, struct, list and map elements; a map argument; an argument that is neither a list COLUMN of the")
@@ -328,6 +338,17 @@ def render() -> str:
     w("  1000-byte sort key (values are padded to the column's longest) fails the task with that operator's message.  Both refuse a sliced list column — a non-zero Arrow offset on")
     w("  the list or its elements, or element offsets that do not start at 0 — at run time, by name; no producer in this engine delivers one (a Scan leaf rebases what it")
     w("  uploads, device-resident inputs carry no lists), so no plan meets this today.")
+    w("* `GetMapValue` / `ElementAt` over a map (`map_extract`), `MapKeys`, `MapValues`, `MapEntries`: a map argument that is not a map COLUMN of the chain's source (a computed")
+    w("  map, a map inside a struct); for `map_extract`, `map_keys` and `map_values` a map with a nested key or a nested value (`map_entries` takes any map the engine passes")
+    w("  through).  `map_extract`: Float32 / Float64 keys (Spark's ordering and an array comparison disagree on -0.0 and NaN keys), Binary keys, Binary values; a key")
+    w("  whose type is not exactly the map's key type (both are named); a Utf8 key that is neither a literal nor a Utf8 COLUMN (a computed string); a Utf8 value used as an")
+    w("  operand — it is an output column, gathered by entry row like a string `arr[i]`.  A duplicate key (a Parquet file or an Arrow input may hold one) answers with its first")
+    w("  entry.  `map_extract` is a per-row loop of the fused kernel like `array_contains`, so a Projection that holds it also runs below a HashAggregate, fused, and under a join,")
+    w("  where the side that holds it is materialised instead of fused; `map_keys` / `map_values` / `map_entries` are derived columns: inside an aggregate's fused chain they are refused (project them below it), under a join the")
+    w("  side that holds them is materialised instead of fused, and runs.  The views refuse a sliced map column — a non-zero Arrow offset on the map or its entries — at run")
+    w("  time, by name; no producer in this engine delivers one.  One lane walks a row's entries: a map of thousands of entries is correct and slow (DESIGN §6c).  In a plan")
+    w("  that holds a lookup a map's keys and values take two of a pipeline's 24 column slots, behind all struct fields and list elements, and only while they fit: a lookup")
+    w("  in a map that got none, and a derived column or bloom filter that finds no slot beside them, are refused by name.  A plan without a lookup binds what it bound before.")
     w("* ShuffleWriter with more than 4096 partitions.")
     w("")
     w("## 5. Results that are not bit-equal to the reference's (and how far apart they may be)")
