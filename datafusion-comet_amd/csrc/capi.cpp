@@ -30,6 +30,7 @@ namespace comet_strfn_host_ns {
 #include "device/strfn.hpp"
 }
 #include "device/list_fn.hpp"      // (array_sort / array_distinct's per-element code, as the host sees it: comet_list_fn_host below)
+#include "device/list_set.hpp"     // (… and the two-list set functions': comet_list_set_host)
 #include "row_shuffle.hpp"
 #include "tz.hpp"
 
@@ -757,6 +758,95 @@ int32_t comet_list_fn_host(int32_t kind, const void* data, const uint8_t* aux, c
       else out[e] = lf_keep(col, 0, e) ? 1u : 0u;
     }
     return 0;
+  });
+}
+
+namespace {
+// one list's elements as buffers the host owns (comet_list_set_host's intermediates: what the executor's take_column delivers on the device)
+struct HostElems {
+  std::vector<uint8_t> data, aux, valid;
+  LfCol col(int kind) const {
+    LfCol c;
+    c.data = data.data();
+    c.aux = aux.data();
+    c.valid = valid.data();
+    c.offset = 0;
+    c.kind = kind;
+    return c;
+  }
+};
+// the rows idx[k] of a's na rows followed by b's: values, Utf8 bytes and validity
+HostElems host_take2(const LfCol& a, int64_t na, const LfCol& b, const std::vector<int64_t>& idx) {
+  HostElems o;
+  const int kind = a.kind;
+  const size_t n = idx.size();
+  o.valid.assign(n / 8 + 2, 0);
+  o.aux.assign(1, 0);
+  if (kind == LF_BOOL) o.data.assign(n / 8 + 2, 0);
+  else if (kind == LF_STR) o.data.assign((n + 1) * 4, 0);
+  else o.data.assign(n * (size_t)kind + 1, 0);
+  std::vector<uint8_t> bytes;
+  for (size_t k = 0; k < n; k++) {
+    const LfCol& s = idx[k] < na ? a : b;
+    const int64_t j = idx[k] < na ? idx[k] : idx[k] - na;
+    if (!lf_is_null(s, j)) o.valid[k >> 3] |= (uint8_t)(1u << (k & 7));
+    if (kind == LF_BOOL) {
+      if ((((const uint8_t*)s.data)[j >> 3] >> (j & 7)) & 1) o.data[k >> 3] |= (uint8_t)(1u << (k & 7));
+    } else if (kind == LF_STR) {
+      const int32_t* off = (const int32_t*)s.data;
+      bytes.insert(bytes.end(), s.aux + off[j], s.aux + off[j + 1]);
+      const int32_t end = (int32_t)bytes.size();
+      memcpy(o.data.data() + (k + 1) * 4, &end, 4);
+    } else {
+      memcpy(o.data.data() + k * (size_t)kind, (const uint8_t*)s.data + (size_t)j * (size_t)kind, (size_t)kind);
+    }
+  }
+  if (!bytes.empty()) o.aux = bytes;
+  return o;
+}
+}  // namespace
+
+int32_t comet_list_set_host(int32_t op, int32_t kind, const void* a_data, const uint8_t* a_aux, const uint8_t* a_valid, int64_t na, const void* b_data, const uint8_t* b_aux,
+                            const uint8_t* b_valid, int64_t nb, uint32_t* out) {
+  return guarded(nullptr, (int32_t)-2, [&]() -> int32_t {
+    if (kind != LF_BOOL && kind != LF_I8 && kind != LF_I16 && kind != LF_I32 && kind != LF_I64 && kind != LF_I128 && kind != LF_STR) throw CometError("comet_list_set_host: unknown element kind");
+    if (op < LS_UNION || op > LS_OVERLAP || na < 0 || nb < 0 || (na > 0 && !a_data) || (nb > 0 && !b_data) || (na + nb > 0 && !out) || na + nb > 0x7fffffffLL)
+      throw CometError("comet_list_set_host: bad arguments");
+    LfCol a, b;
+    a.data = a_data; a.aux = a_aux; a.valid = a_valid; a.offset = 0; a.kind = kind;
+    b.data = b_data; b.aux = b_aux; b.valid = b_valid; b.offset = 0; b.kind = kind;
+    // the steps of exec.cpp extend_derived_list_set over one row: one list on each side, both valid
+    const int64_t offs_a[2] = {0, na}, offs_b[2] = {0, nb};
+    if (op == LS_UNION) {
+      const int64_t total = (int64_t)lf_concat_len(offs_a, offs_b, nullptr, nullptr, 0);
+      const int64_t offs_out[2] = {0, total};
+      std::vector<int64_t> idx((size_t)total);
+      for (int64_t k = 0; k < total; k++) idx[(size_t)k] = lf_concat_src(offs_a, offs_b, offs_out, 1, na, k);
+      const HostElems cat = host_take2(a, na, b, idx);
+      const LfCol c = cat.col(kind);
+      int32_t kept = 0;
+      for (int64_t k = 0; k < total; k++)
+        if (lf_keep(c, 0, k)) out[kept++] = (uint32_t)idx[(size_t)k];
+      return kept;
+    }
+    std::vector<int64_t> perm((size_t)nb);
+    for (int64_t e = 0; e < nb; e++) perm[(size_t)lf_rank(b, 0, nb, e, 0)] = e;      // b ascending, NULLs first
+    const HostElems sorted = host_take2(b, nb, b, perm);
+    const LfCol bs = sorted.col(kind);
+    if (op == LS_OVERLAP) {
+      std::vector<uint32_t> hits((size_t)na + 1, 0u);
+      for (int64_t e = 0; e < na; e++) hits[(size_t)e] = lf_member(a, e, bs, 0, nb, nullptr, nullptr, 0, true, true);
+      return lf_overlap_row(hits.data(), a, 0, na, bs, 0, nb, true);
+    }
+    std::vector<int64_t> first;      // distinct(a) as rows of a
+    for (int64_t e = 0; e < na; e++)
+      if (lf_keep(a, 0, e)) first.push_back(e);
+    const HostElems distinct = host_take2(a, na, a, first);
+    const LfCol da = distinct.col(kind);
+    int32_t kept = 0;
+    for (size_t e = 0; e < first.size(); e++)
+      if (lf_member(da, (int64_t)e, bs, 0, nb, nullptr, nullptr, 0, op == LS_INTERSECT, false)) out[kept++] = (uint32_t)first[e];
+    return kept;
   });
 }
 

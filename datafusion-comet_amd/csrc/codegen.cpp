@@ -423,7 +423,7 @@ ExprP lower_list_fn(const ExprP& e) {
   bool ok = subject->kind == ExprKind::Bound && subject->has_dtype && subject->dtype.id == TypeId::List && subject->dtype.kids.size() == 1 && subject->bound_index >= 0;
   if (ok && subject->bound_index >= nsrc) {      // … a derived list: the index of one's first column
     ok = false;
-    for (size_t k = 0; k < g_derived->size(); k++) ok |= (*g_derived)[k].kind != 3 && derived_index(nsrc, k) == subject->bound_index;
+    for (size_t k = 0; k < g_derived->size(); k++) ok |= (*g_derived)[k].is_list() && derived_index(nsrc, k) == subject->bound_index;
   }
   if (!ok) throw CometError(f + " is supported over a list COLUMN of the source or a derived list (split, array_sort …), not over a computed array, by the MI355X native engine");
   check_list_fn_elem(f, subject->dtype.kids[0], true);
@@ -455,6 +455,64 @@ ExprP lower_list_fn(const ExprP& e) {
   b->dtype = dc.type;
   b->has_dtype = true;
   return b;
+}
+// array_union(a, b), array_intersect(a, b), array_except(a, b) and spark_arrays_overlap(a, b) → Boolean (serde/arrays.scala: what Spark's ArrayUnion, ArrayIntersect,
+// ArrayExcept and ArraysOverlap are sent as): a derived column of kind 6 with TWO sources — for the first three a list column and its elements as kind 4 is, for the
+// overlap one Boolean column.  Each argument is a list column of the chain's source or an earlier derived list, the rule of lower_list_fn; the two element types
+// must be exactly equal (the JVM casts before it sends).  The executor (exec.cpp extend_derived_list_set) builds them from kind 4's distinct and sort and the
+// membership search of device/list_set.hpp; its intermediates are no columns of the chain.
+bool is_list_set_fn(const std::string& f) { return f == "array_union" || f == "array_intersect" || f == "array_except" || f == "spark_arrays_overlap"; }
+ExprP lower_list_set(const ExprP& e) {
+  const std::string& f = e->func;
+  const int op = f == "array_union" ? 0 : f == "array_intersect" ? 1 : f == "array_except" ? 2 : kDerivedListOverlap;      // (device/list_set.hpp LS_UNION …)
+  // (as for array_sort: a join materialises a side whose fold throws, so there this wording never reaches a user)
+  if (!g_derived || !g_source_cols)
+    throw CometError(f + " inside a join's or an aggregate's fused chain is not supported by the MI355X native engine yet (a derived list is computed over the source of a Projection / Filter chain)");
+  if (e->children.size() != 2) throw CometError(f + " expects 2 arguments (array, array), got " + std::to_string(e->children.size()));
+  const int nsrc = (int)g_source_cols->size();
+  for (const ExprP& subject : e->children) {
+    if (subject->has_dtype && subject->dtype.id == TypeId::Map) throw CometError(f + " of a map is not supported by the MI355X native engine");
+    bool ok = subject->kind == ExprKind::Bound && subject->has_dtype && subject->dtype.id == TypeId::List && subject->dtype.kids.size() == 1 && subject->bound_index >= 0;
+    if (ok && subject->bound_index >= nsrc) {      // … a derived list: the index of one's first column
+      ok = false;
+      for (size_t k = 0; k < g_derived->size(); k++) ok |= (*g_derived)[k].is_list() && derived_index(nsrc, k) == subject->bound_index;
+    }
+    if (!ok) throw CometError(f + " is supported over a list COLUMN of the source or a derived list (split, array_sort …), not over a computed array, by the MI355X native engine");
+    check_list_fn_elem(f, subject->dtype.kids[0], true);
+  }
+  const ExprP &a = e->children[0], &b = e->children[1];
+  const DType &ea = a->dtype.kids[0], &eb = b->dtype.kids[0];
+  if (!(ea == eb))
+    throw CometError(f + " over " + ea.str() + " and " + eb.str() + " elements is not supported by the MI355X native engine (the two element types must be equal: Spark casts them to one type before it sends the function)");
+  if (op == kDerivedListOverlap && (!e->has_dtype || e->dtype.id != TypeId::Bool))
+    throw CometError(f + " expects the return type Boolean, got " + (e->has_dtype ? e->dtype.str() : std::string("none")));
+  DerivedCol dc;
+  dc.kind = 6;
+  dc.op = op;
+  dc.src = a->bound_index;
+  dc.src2 = b->bound_index;
+  if (op == kDerivedListOverlap) {
+    dc.type = DType::of(TypeId::Bool);
+  } else {
+    dc.type = a->dtype;
+    dc.type.virt_parent = dc.type.virt_kid = -1;
+    dc.type.kids[0].virt_parent = dc.type.kids[0].virt_kid = -1;
+    // union's elements can be NULL where either side's can
+    if (op == 0 && !dc.type.kid_nullable.empty() && !b->dtype.kid_nullable.empty() && b->dtype.kid_nullable[0]) dc.type.kid_nullable[0] = 1;
+  }
+  size_t k = 0;
+  for (; k < g_derived->size(); k++) {
+    const DerivedCol& o = (*g_derived)[k];
+    if (o.kind == 6 && o.src == dc.src && o.src2 == dc.src2 && o.op == dc.op) break;
+  }
+  if (k == g_derived->size()) g_derived->push_back(dc);
+  auto r = std::make_shared<Expr>();
+  r->kind = ExprKind::Bound;
+  r->proto_tag = 3;
+  r->bound_index = derived_index(nsrc, k);
+  r->dtype = (*g_derived)[k].type;
+  r->has_dtype = true;
+  return r;
 }
 // map_keys(m), map_values(m) and map_entries(m) (serde/maps.scala: Spark's MapKeys / MapValues / MapEntries, sent without a return type): a derived list column
 // of kind 5, a VIEW — a map is laid out as offsets over the entries Struct(key, value), so the list shares the map's offsets and validity and its element column
@@ -532,6 +590,10 @@ ExprP substitute(const ExprP& e, const std::vector<ExprP>& cols, std::map<const 
     auto n = std::make_shared<Expr>(*e);
     for (auto& c : n->children) c = substitute(c, cols, memo);
     out = lower_list_fn(n);
+  } else if (e->kind == ExprKind::ScalarFunc && is_list_set_fn(e->func)) {
+    auto n = std::make_shared<Expr>(*e);
+    for (auto& c : n->children) c = substitute(c, cols, memo);
+    out = lower_list_set(n);
   } else if (e->kind == ExprKind::ScalarFunc && is_map_view_fn(e->func)) {
     auto n = std::make_shared<Expr>(*e);
     for (auto& c : n->children) c = substitute(c, cols, memo);
@@ -3841,11 +3903,20 @@ std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool
     d.in_types.push_back(dc.type);
     valid_all.push_back(valid_all.at((size_t)dc.src));      // (a kind 4 column's source may be a derived column before it)
     if (dc.kind == 3) continue;
+    // a set function's list is NULL where either source is; arrays_overlap answers NULL beside NULL elements too, so its one column always carries validity
+    if (dc.kind == 6) valid_all.back() = dc.op == kDerivedListOverlap || valid_all.at((size_t)dc.src) || valid_all.at((size_t)dc.src2);
+    if (!dc.is_list()) continue;
     bool elem_valid = false;      // split's pieces are never NULL; a sorted / distinct list's elements are NULL where its source's are
     // (virt_kid 0 of a List is its element column; of a Map its key column, and virt_kid 1 its value column)
-    if (dc.kind == 4)
+    auto elems_valid = [&](int src) {
+      bool v = false;
       for (size_t j = 0; j + 1 < d.in_types.size(); j++)
-        if (d.in_types[j].virt_parent == dc.src && d.in_types[j].virt_kid == 0 && d.in_types[(size_t)dc.src].id == TypeId::List) elem_valid = valid_all[j];
+        if (d.in_types[j].virt_parent == src && d.in_types[j].virt_kid == 0 && d.in_types[(size_t)src].id == TypeId::List) v = valid_all[j];
+      return v;
+    };
+    if (dc.kind == 4) elem_valid = elems_valid(dc.src);
+    // intersect and except keep elements of a; union's come from either side
+    if (dc.kind == 6) elem_valid = elems_valid(dc.src) || (dc.op == 0 && elems_valid(dc.src2));
     // map_values: keys and entries are never NULL; values carry validity bits whenever the map's type lets them be NULL (the plan does not see the value column
     // itself unless it holds a lookup, so the executor hands the elements over with a bitmap in any case — extend_derived_map_view)
     if (dc.kind == 5 && dc.op == 1) elem_valid = !dc.type.kid_nullable.empty() && dc.type.kid_nullable[0] != 0;
@@ -3861,6 +3932,10 @@ std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool
   for (auto& dc : d.derived)
     if (dc.kind == 4 && under_agg)
       throw CometError(std::string(dc.op == 0 ? "array_sort" : "array_distinct") + " inside an aggregate's chain is not supported by the MI355X native engine yet (project it below the aggregate)");
+  for (auto& dc : d.derived)
+    if (dc.kind == 6 && under_agg)
+      throw CometError(std::string(dc.op == 0 ? "array_union" : dc.op == 1 ? "array_intersect" : dc.op == 2 ? "array_except" : "spark_arrays_overlap") +
+                       " inside an aggregate's chain is not supported by the MI355X native engine yet (project it below the aggregate)");
   if (!d.derived.empty() && under_agg) throw CometError("split inside an aggregate's chain is not supported by the MI355X native engine yet");
   if (d.in_types.size() > COMET_MAX_IN) throw CometError("too many scan columns for one GPU pipeline");
   return valid_all;

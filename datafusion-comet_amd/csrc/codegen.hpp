@@ -40,6 +40,7 @@ struct OutCol {
   bool pad_left = false;
 };
 
+constexpr int kDerivedListOverlap = 3;      // DerivedCol kind 6: the op of arrays_overlap (device/list_set.hpp LS_OVERLAP), the one set function that is one column
 // A column the executor computes over the chain's SOURCE table before the fused kernel runs, addressed by the chain like a source column
 // (in_types holds it behind the source's own columns): today split(<Utf8 column>, <pattern literal>, <limit literal>) → list<string>,
 // which the chain passes through by row index like any nested column.
@@ -48,12 +49,16 @@ struct DerivedCol {
                                     // 4: array_sort / array_distinct of a list column (two columns, as split),
                                     // 5: map_keys / map_values / map_entries of a map column of the source — a view: the list shares the map's offsets and validity, its
                                     //    elements are the key column, the value column or the entries struct (two columns, as split; nothing is copied)
+                                    // 6: array_union / array_intersect / array_except (two columns, as kind 4) and arrays_overlap (one Boolean column, as kind 3 is
+                                    //    one Utf8 column) of TWO list columns, src and src2 (device/list_set.hpp)
   int op = 0;                       // kind 3: device/strfn.hpp's operation (SF_REVERSE …), or kDerivedRegexpReplace; kind 4: device/list_fn.hpp's LF_OP_SORT / LF_OP_DISTINCT;
-                                    // kind 5: 0 keys, 1 values, 2 entries
+                                    // kind 5: 0 keys, 1 values, 2 entries; kind 6: device/list_set.hpp's LS_UNION / LS_INTERSECT / LS_EXCEPT / LS_OVERLAP
   std::string arg_a, arg_b;         // kind 3: the literal arguments' bytes (regexp_replace: the pattern and the replacement as written)
   long long arg_k = 0;              // kind 3: the integer argument; kind 4 sort: LF_DESC | LF_NULLS_LAST
-  int columns() const { return kind == 3 ? 1 : 2; }
-  int src = -1;                     // the source column (kind 4: any list column of the extended table, an earlier derived list included)
+  int columns() const { return kind == 3 || (kind == 6 && op == kDerivedListOverlap) ? 1 : 2; }
+  bool is_list() const { return columns() == 2; }      // a derived LIST column: another list function may take it as its argument
+  int src = -1;                     // the source column (kind 4 and 6: any list column of the extended table, an earlier derived list included)
+  int src2 = -1;                    // kind 6: the second list column, under the same rule
   std::vector<uint32_t> prog;       // the pattern as a group-0 program of device/regex_vm.hpp
   std::vector<uint32_t> prog2;      // regexp_extract_all: the wanted group's program (empty: group 0)
   int limit = -1;

@@ -1751,6 +1751,268 @@ void ExecutionContext::extend_derived_map_view(DevTable& in, const DerivedCol& d
   in.has_valid.push_back(el_hv);
 }
 
+// A derived column of kind 6: array_union / array_intersect / array_except / arrays_overlap of two list columns of the extended table (device/list_set.hpp,
+// list_set_kernels.hip).  Built from kind 4's machinery, which comes along with both of its tiers:
+//   intersect / except   distinct(a) and b sorted ascending with NULLs first; one member flag per element of distinct(a) (a binary search of b's list); then
+//                        distinct's own tail — the flags' scan, the kept rows, the new offsets, one take_column
+//   union                a ++ b per row (the two element columns laid end to end, taken by row numbers computed from the offsets), then distinct of that
+//   overlap              b sorted; hit flags of a's non-NULL elements; one lane per row folds them with each side's "holds a NULL element"
+// The intermediates live in a scratch copy of the table's column list that is dropped at the end: they are no columns of the chain and take none of its slots.
+// A row that is NULL on either side keeps nothing (an empty list under validity 0; NULL for overlap).  The sliced-column rule of kind 4 holds for both arguments.
+void ExecutionContext::extend_derived_list_set(DevTable& in, const DerivedCol& dc) {
+  static const char* const kNames[] = {"array_union", "array_intersect", "array_except", "arrays_overlap"};
+  if (dc.op < 0 || dc.op > 3) throw CometError("internal: unknown derived column");
+  const std::string who = kNames[dc.op];
+  const int64_t rows = in.rows;
+  struct Side { int list = -1, elems = -1; DeviceColumnView sc, ec; bool hv = false, ehv = false; const int32_t* offs = nullptr; int32_t hi = 0; const uint8_t* row_bits = nullptr; };
+  auto side_of = [&](int src) {
+    Side s;
+    if (src < 0 || (size_t)src >= in.cols.size() || in.types[(size_t)src].id != TypeId::List || in.types[(size_t)src].kids.size() != 1) throw CometError("internal: unknown derived column");
+    s.list = src;
+    for (size_t j = 0; j < in.types.size(); j++)
+      if (in.types[j].virt_parent == src && in.types[j].virt_kid == 0) s.elems = (int)j;
+    if (s.elems < 0) throw CometError("internal: " + who + ": the list's elements are not a column of the chain's table");
+    s.sc = in.cols[(size_t)src];
+    s.ec = in.cols[(size_t)s.elems];
+    s.hv = in.has_valid[(size_t)src];
+    s.ehv = in.has_valid[(size_t)s.elems];
+    s.offs = s.sc.data ? (const int32_t*)s.sc.data + s.sc.offset : nullptr;
+    if (rows > 0) {
+      if (!s.offs) throw CometError(who + " over a list column without offsets is not supported");
+      int32_t lo = 0;
+      read_small(&lo, s.offs, 4);
+      read_small(&s.hi, s.offs + rows, 4);
+      if (s.sc.offset != 0 || lo != 0 || (s.hi > 0 && s.ec.offset != 0))
+        throw CometError(who + " over a sliced list column (a non-zero Arrow offset, or element offsets that do not start at 0) is not supported by the MI355X native engine");
+      if (s.hi < 0) throw CometError(who + ": the list column's offsets do not ascend (0 … " + std::to_string(s.hi) + ")");
+    }
+    if (s.hi > 0) {
+      if (!s.ec.data) throw CometError(who + " over an element column without buffers is not supported");
+      if (s.ehv && !s.ec.valid) throw CometError("internal: " + who + ": an element column marked nullable without validity bits");
+    }
+    if (s.hv && rows > 0 && !s.sc.valid) throw CometError("internal: " + who + ": a list column marked nullable without validity bits");
+    s.row_bits = s.hv ? s.sc.valid : nullptr;
+    return s;
+  };
+  const Side A = side_of(dc.src), B = side_of(dc.src2);
+  const DType& lt = in.types[(size_t)dc.src];
+  DType et = lt.kids[0];
+  et.virt_parent = et.virt_kid = -1;
+  const int kind = list_fn_elem_kind(et);
+  if (kind < 0 || list_fn_elem_kind(in.types[(size_t)dc.src2].kids[0]) != kind) throw CometError("internal: " + who + ": the two lists' elements are not of one supported type");
+  if ((int64_t)A.hi + (int64_t)B.hi > 0x7fffffffLL) throw CometError(who + ": more than 2^31 elements in one table");
+
+  // the scratch table of the kind-4 steps: the chain's columns (views: nothing is copied) with room behind them; what it comes to own goes when it does
+  DevTable tmp;
+  tmp.rows = rows;
+  tmp.types = in.types;
+  tmp.cols = in.cols;
+  tmp.has_valid = in.has_valid;
+  auto list_fn = [&](DevTable& t, int op, int src) {      // appends (list, elements) to t and returns the list's column index
+    DerivedCol d4;
+    d4.kind = 4;
+    d4.op = op;
+    d4.src = src;
+    d4.type = t.types[(size_t)src];
+    d4.type.virt_parent = d4.type.virt_kid = -1;
+    d4.type.kids[0].virt_parent = d4.type.kids[0].virt_kid = -1;
+    extend_derived_list_fn(t, d4);
+    return (int)t.cols.size() - 2;
+  };
+
+  // the result's row validity: the AND of the two lists' bitmaps, either of which may be absent
+  const bool res_hv = A.hv || B.hv;
+  const uint8_t* res_valid = A.hv ? A.row_bits : B.row_bits;
+  if (A.hv && B.hv && rows > 0) {
+    auto both = std::make_shared<DevBuf>();
+    const int64_t nb = (rows + 7) / 8;
+    both->ensure((size_t)nb + 16);
+    if (comet_launch_list_and_bits(A.row_bits, B.row_bits, nb, (uint8_t*)both->p, stream_) != 0) throw CometError(who + ": launch failed");
+    res_valid = (const uint8_t*)both->p;
+    in.owners.push_back(both);
+  }
+  list_set_rows_ += rows;
+
+  if (dc.op == LS_OVERLAP) {
+    const int sb = list_fn(tmp, LF_OP_SORT, dc.src2);      // (flags 0: ascending, NULLs first)
+    const DeviceColumnView& bs = tmp.cols[(size_t)sb + 1];
+    const bool bs_hv = tmp.has_valid[(size_t)sb + 1];
+    DevBuf hits, code;
+    auto value = std::make_shared<DevBuf>(), valid = std::make_shared<DevBuf>();
+    hits.ensure((size_t)std::max<int32_t>(A.hi, 1) * 4 + 16);
+    code.ensure((size_t)std::max<int64_t>(rows, 1) + 16);
+    value->ensure((size_t)((rows + 7) / 8) + 16);
+    valid->ensure((size_t)((rows + 7) / 8) + 16);
+    if (comet_launch_list_member(kind, A.ec.data, (const uint8_t*)A.ec.aux, A.ehv ? A.ec.valid : nullptr, bs.data, (const uint8_t*)bs.aux, bs_hv ? bs.valid : nullptr, A.offs, B.offs,
+                                 A.row_bits, B.row_bits, rows, A.hi, 1, 1, (uint32_t*)hits.p, stream_) != 0 ||
+        comet_launch_list_overlap(kind, (const uint32_t*)hits.p, A.ec.data, (const uint8_t*)A.ec.aux, A.ehv ? A.ec.valid : nullptr, bs.data, (const uint8_t*)bs.aux,
+                                  bs_hv ? bs.valid : nullptr, A.offs, B.offs, A.row_bits, B.row_bits, rows, (uint8_t*)code.p, (uint8_t*)value->p, (uint8_t*)valid->p, stream_) != 0)
+      throw CometError(who + ": launch failed");
+    HIP_CHECK(hipStreamSynchronize(stream_));      // the flags, the codes and the sorted b go back to the pool
+    DeviceColumnView cv;
+    cv.data = value->p;
+    cv.valid = (const uint8_t*)valid->p;
+    in.types.push_back(dc.type);
+    in.cols.push_back(cv);
+    in.has_valid.push_back(true);
+    in.owners.push_back(value);
+    in.owners.push_back(valid);
+    return;
+  }
+
+  DeviceColumnView lv = A.sc, el = A.ec;      // (nothing to keep: a's own offsets are all 0 then, and its empty element column serves)
+  bool el_hv = A.ehv;
+  if (dc.op == LS_UNION) {
+    el_hv = A.ehv || B.ehv;
+    if ((int64_t)A.hi + B.hi > 0) {
+      // the two element columns laid end to end
+      const int64_t n = (int64_t)A.hi + B.hi;
+      DeviceColumnView E;
+      auto data = std::make_shared<DevBuf>();
+      tmp.owners.push_back(data);
+      if (kind == LF_STR) {
+        int32_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+        if (A.hi > 0) { read_small(&a0, A.ec.data, 4); read_small(&a1, (const int32_t*)A.ec.data + A.hi, 4); }
+        if (B.hi > 0) { read_small(&b0, B.ec.data, 4); read_small(&b1, (const int32_t*)B.ec.data + B.hi, 4); }
+        if (a0 < 0 || a1 < a0 || b0 < 0 || b1 < b0) throw CometError(who + ": a Utf8 element column's offsets do not ascend");
+        const int64_t na = (int64_t)a1 - a0, nb = (int64_t)b1 - b0;
+        if (na + nb > 0x7fffffffLL) throw CometError("Utf8 column exceeds 2 GiB of string data (LargeUtf8 is not supported)");
+        auto bytes = std::make_shared<DevBuf>();
+        tmp.owners.push_back(bytes);
+        data->ensure((size_t)(n + 1) * 4 + 16);
+        bytes->ensure((size_t)(na + nb) + 16);
+        // (b's offsets go first: with no elements in a, they write entry 0 too)
+        if ((B.hi > 0 && comet_launch_list_rebase_offsets((const int32_t*)B.ec.data, B.hi, (int32_t)(na - b0), (int32_t*)data->p + A.hi, stream_) != 0) ||
+            (A.hi > 0 && comet_launch_list_rebase_offsets((const int32_t*)A.ec.data, A.hi, -a0, (int32_t*)data->p, stream_) != 0))
+          throw CometError(who + ": launch failed");
+        if (na) HIP_CHECK(hipMemcpyAsync(bytes->p, (const char*)A.ec.aux + a0, (size_t)na, hipMemcpyDeviceToDevice, stream_));
+        if (nb) HIP_CHECK(hipMemcpyAsync((char*)bytes->p + na, (const char*)B.ec.aux + b0, (size_t)nb, hipMemcpyDeviceToDevice, stream_));
+        E.aux = bytes->p;
+      } else if (kind == LF_BOOL) {
+        data->ensure((size_t)((n + 7) / 8) + 16);
+        if (comet_launch_list_concat_bits((const uint8_t*)A.ec.data, A.hi, (const uint8_t*)B.ec.data, B.hi, (uint8_t*)data->p, stream_) != 0) throw CometError(who + ": launch failed");
+      } else {
+        data->ensure((size_t)n * (size_t)kind + 16);      // (the kind of a fixed-width element is its byte width)
+        if (A.hi > 0) HIP_CHECK(hipMemcpyAsync(data->p, A.ec.data, (size_t)A.hi * (size_t)kind, hipMemcpyDeviceToDevice, stream_));
+        if (B.hi > 0) HIP_CHECK(hipMemcpyAsync((char*)data->p + (size_t)A.hi * (size_t)kind, B.ec.data, (size_t)B.hi * (size_t)kind, hipMemcpyDeviceToDevice, stream_));
+      }
+      E.data = data->p;
+      if (el_hv) {      // one side without a bitmap reads as all valid
+        auto bits = std::make_shared<DevBuf>();
+        tmp.owners.push_back(bits);
+        bits->ensure((size_t)((n + 7) / 8) + 16);
+        if (comet_launch_list_concat_bits(A.ehv ? A.ec.valid : nullptr, A.hi, B.ehv ? B.ec.valid : nullptr, B.hi, (uint8_t*)bits->p, stream_) != 0) throw CometError(who + ": launch failed");
+        E.valid = (const uint8_t*)bits->p;
+      }
+      // a ++ b: the row lengths (0 where a side is NULL), their scan, every output element's row in E
+      DevBuf lengths, tiles;
+      auto coffs = std::make_shared<DevBuf>(), idx = std::make_shared<DevBuf>();
+      tmp.owners.push_back(coffs);
+      lengths.ensure((size_t)rows * 4 + 16);
+      tiles.ensure((size_t)((rows + 1023) / 1024 + 2) * 8);
+      coffs->ensure((size_t)(rows + 2) * 4);
+      if (comet_launch_list_concat_len(A.offs, B.offs, A.row_bits, B.row_bits, rows, (uint32_t*)lengths.p, stream_) != 0) throw CometError(who + ": launch failed");
+      pq_launch_u32_scan((const uint32_t*)lengths.p, rows, (uint64_t*)tiles.p, (int32_t*)coffs->p, stream_);
+      int32_t total = 0;
+      read_small(&total, (const char*)coffs->p + (size_t)rows * 4, 4);
+      if (total < 0 || (int64_t)total > n) throw CometError("internal: " + who + ": " + std::to_string(total) + " concatenated elements of " + std::to_string(n));
+      HIP_CHECK(hipStreamSynchronize(stream_));      // the lengths and the tiles go back to the pool
+      if (total > 0) {
+        idx->ensure((size_t)total * 4 + 16);
+        if (comet_launch_list_concat_index(A.offs, B.offs, (const int32_t*)coffs->p, rows, A.hi, total, (uint32_t*)idx->p, stream_) != 0) throw CometError(who + ": launch failed");
+        bool c_hv = false;
+        DevTable cat;      // the concatenation as a table of its own: (list, elements), then distinct's two columns
+        cat.rows = rows;
+        DeviceColumnView cel = take_column(E, et, el_hv, (const uint32_t*)idx->p, nullptr, total, c_hv, tmp.owners);
+        HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
+        if (c_hv != el_hv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
+        DeviceColumnView cl;
+        cl.data = coffs->p;
+        cl.valid = res_valid;
+        cl.kids.assign(1, cel);
+        cl.kid_has_valid.assign(1, c_hv ? 1 : 0);
+        cl.kid_rows = total;
+        DType clt = dc.type, cet = et;
+        cet.virt_parent = 0;
+        cet.virt_kid = 0;
+        cat.types = {clt, cet};
+        cat.cols = {cl, cel};
+        cat.has_valid = {res_hv, c_hv};
+        const int d = list_fn(cat, LF_OP_DISTINCT, 0);
+        lv = cat.cols[(size_t)d];
+        el = cat.cols[(size_t)d + 1];
+        if (cat.has_valid[(size_t)d + 1] != el_hv) throw CometError("internal: " + who + ": the distinct elements lost their validity bits");
+        for (auto& o : cat.owners) in.owners.push_back(o);      // distinct's offsets and elements
+      } else {
+        // every row is NULL on a side or empty on both: the all-zero offsets over an element column of no rows
+        lv.data = coffs->p;
+        lv.offset = 0;
+        lv.kid_rows = 0;
+        el = E;
+        for (auto& o : tmp.owners) in.owners.push_back(o);
+      }
+    } else if (!A.ehv && B.ehv) {
+      el = B.ec;      // (no element on either side: the empty column that has the planned validity bits)
+    }
+  } else {
+    const int da = list_fn(tmp, LF_OP_DISTINCT, dc.src), sb = list_fn(tmp, LF_OP_SORT, dc.src2);
+    const DeviceColumnView dl = tmp.cols[(size_t)da], de = tmp.cols[(size_t)da + 1], bs = tmp.cols[(size_t)sb + 1];
+    const bool de_hv = tmp.has_valid[(size_t)da + 1], bs_hv = tmp.has_valid[(size_t)sb + 1];
+    if (de_hv != A.ehv) throw CometError("internal: " + who + ": the distinct elements lost their validity bits");
+    const int32_t* doffs = dl.data ? (const int32_t*)dl.data + dl.offset : nullptr;
+    int32_t hi = 0;
+    if (rows > 0 && doffs) read_small(&hi, doffs + rows, 4);
+    if (hi < 0 || hi > A.hi) throw CometError("internal: " + who + ": " + std::to_string(hi) + " distinct elements of " + std::to_string(A.hi));
+    lv = dl;
+    el = de;
+    if (hi > 0) {
+      DevBuf flags, tiles, C;
+      flags.ensure((size_t)hi * 4 + 16);
+      tiles.ensure((size_t)((hi + 1023) / 1024 + 2) * 8);
+      C.ensure((size_t)(hi + 2) * 4);
+      HIP_CHECK(hipMemsetAsync(C.p, 0, 8, stream_));
+      if (comet_launch_list_member(kind, de.data, (const uint8_t*)de.aux, de_hv ? de.valid : nullptr, bs.data, (const uint8_t*)bs.aux, bs_hv ? bs.valid : nullptr, doffs, B.offs, A.row_bits,
+                                   B.row_bits, rows, hi, dc.op == LS_INTERSECT ? 1 : 0, 0, (uint32_t*)flags.p, stream_) != 0)
+        throw CometError(who + ": launch failed");
+      pq_launch_u32_scan((const uint32_t*)flags.p, hi, (uint64_t*)tiles.p, (int32_t*)C.p, stream_);
+      int32_t kept = 0;
+      read_small(&kept, (const char*)C.p + (size_t)hi * 4, 4);
+      if (kept < 0 || kept > hi) throw CometError("internal: " + who + ": " + std::to_string(kept) + " kept elements of " + std::to_string(hi));
+      auto idx = std::make_shared<DevBuf>(), noffs = std::make_shared<DevBuf>();
+      idx->ensure((size_t)std::max<int32_t>(kept, 1) * 4 + 16);
+      noffs->ensure((size_t)(rows + 1) * 4 + 16);
+      if (comet_launch_collect_index((const uint32_t*)flags.p, (const int32_t*)C.p, hi, (uint32_t*)idx->p, stream_) != 0 ||
+          comet_launch_list_offsets(doffs, (const int32_t*)C.p, rows, (int32_t*)noffs->p, stream_) != 0)
+        throw CometError(who + ": launch failed");
+      HIP_CHECK(hipStreamSynchronize(stream_));      // the flags, the tiles and the scan go back to the pool
+      bool t_hv = false;
+      el = take_column(de, et, de_hv, (const uint32_t*)idx->p, nullptr, kept, t_hv, in.owners);
+      HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
+      if (t_hv != de_hv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
+      lv.data = noffs->p;
+      lv.offset = 0;
+      lv.kid_rows = kept;
+      in.owners.push_back(noffs);
+    } else {
+      for (auto& o : tmp.owners) in.owners.push_back(o);      // (distinct's all-zero offsets, if it made any)
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(stream_));      // the scratch table's buffers go back to the pool
+  lv.valid = res_valid;
+  lv.kids.assign(1, el);
+  lv.kid_has_valid.assign(1, el_hv ? 1 : 0);
+  if ((int64_t)A.hi + B.hi == 0) lv.kid_rows = 0;
+  in.types.push_back(dc.type);
+  in.cols.push_back(lv);
+  in.has_valid.push_back(res_hv);
+  DType vt = dc.type.kids[0];      // the elements as a column of their own, as split's are
+  vt.virt_parent = (int)in.types.size() - 1;
+  vt.virt_kid = 0;
+  in.types.push_back(vt);
+  in.cols.push_back(el);
+  in.has_valid.push_back(el_hv);
+}
+
 // The chain's derived columns (codegen.hpp DerivedCol) computed over its source table and appended to it.  split: two passes of the matcher per
 // row (regex_kernels.hip) — the pieces counted, a prefix sum, every piece described as a view of its source value — and the element column
 // assembled from the views like every string view's result.
@@ -1759,6 +2021,7 @@ void ExecutionContext::extend_derived(DevTable& in, const std::vector<DerivedCol
     if (dc.kind == 3) { extend_derived_strfn(in, dc); continue; }
     if (dc.kind == 4) { extend_derived_list_fn(in, dc); continue; }
     if (dc.kind == 5) { extend_derived_map_view(in, dc); continue; }
+    if (dc.kind == 6) { extend_derived_list_set(in, dc); continue; }
     if ((dc.kind != 1 && dc.kind != 2) || dc.src < 0 || (size_t)dc.src >= in.cols.size()) throw CometError("internal: unknown derived column");
     const DeviceColumnView sc = in.cols[(size_t)dc.src];
     const bool hv = in.has_valid[(size_t)dc.src];
@@ -2525,6 +2788,7 @@ std::string ExecutionContext::metrics_proto() {
     }
     if (root && list_fn_rank_lists_ > 0) n.metrics.emplace_back("list_fn_rank_lists", list_fn_rank_lists_);      // lists array_sort / array_distinct ranked (only when there are any)
     if (root && list_fn_sort_lists_ > 0) n.metrics.emplace_back("list_fn_sort_lists", list_fn_sort_lists_);      // … and lists that took the radix sort
+    if (root && list_set_rows_ > 0) n.metrics.emplace_back("list_set_rows", list_set_rows_);      // rows the two-list set functions computed (only when there are any)
     if (root && sort_runs_ > 0) {      // the paths sort_table took (only when the plan sorted at all): see DESIGN.md, Sort
       n.metrics.emplace_back("sort_select_passes", sort_select_passes_);
       n.metrics.emplace_back("sort_small_sorts", sort_small_sorts_);

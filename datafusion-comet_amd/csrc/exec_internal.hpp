@@ -32,6 +32,20 @@ extern "C" int comet_launch_list_rows(const int32_t* offs, int64_t rows, int64_t
 extern "C" int comet_launch_list_scatter_keep(const uint32_t* src, const uint32_t* fpeer, int64_t hi, uint32_t* keep, void* stream);
 extern "C" int comet_launch_list_offsets(const int32_t* offs, const int32_t* C, int64_t rows, int32_t* out, void* stream);
 extern "C" int comet_launch_collect_index(const uint32_t* keep, const int32_t* C, int64_t n, uint32_t* idx, void* stream);
+// array_union / array_intersect / array_except / arrays_overlap (device/list_set.hpp, list_set_kernels.hip)
+#include "device/list_set.hpp"
+extern "C" int comet_launch_list_member(int kind, const void* a_data, const uint8_t* a_aux, const uint8_t* a_valid, const void* b_data, const uint8_t* b_aux, const uint8_t* b_valid,
+                                        const int32_t* offs_a, const int32_t* offs_b, const uint8_t* a_rows, const uint8_t* b_rows, int64_t rows, int64_t hi_a, int want,
+                                        int values_only, uint32_t* out, void* stream);
+extern "C" int comet_launch_list_overlap(int kind, const uint32_t* hits, const void* a_data, const uint8_t* a_aux, const uint8_t* a_valid, const void* b_data, const uint8_t* b_aux,
+                                         const uint8_t* b_valid, const int32_t* offs_a, const int32_t* offs_b, const uint8_t* a_rows, const uint8_t* b_rows, int64_t rows,
+                                         uint8_t* code, uint8_t* value, uint8_t* valid, void* stream);
+extern "C" int comet_launch_list_concat_len(const int32_t* offs_a, const int32_t* offs_b, const uint8_t* a_rows, const uint8_t* b_rows, int64_t rows, uint32_t* len, void* stream);
+extern "C" int comet_launch_list_concat_index(const int32_t* offs_a, const int32_t* offs_b, const int32_t* offs_out, int64_t rows, int64_t hi_a, int64_t total, uint32_t* idx,
+                                              void* stream);
+extern "C" int comet_launch_list_concat_bits(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb, uint8_t* out, void* stream);
+extern "C" int comet_launch_list_rebase_offsets(const int32_t* in, int64_t n, int32_t by, int32_t* out, void* stream);
+extern "C" int comet_launch_list_and_bits(const uint8_t* a, const uint8_t* b, int64_t bytes, uint8_t* out, void* stream);
 constexpr int64_t kListFnMaxElements = 256;       // the longest list the rank kernel takes (every lane of a list walks all of it); beyond, the radix sort is faster
 extern "C" void pq_launch_u32_scan(const uint32_t* in, int64_t n, uint64_t* tiles, int32_t* out, void* st);
 extern "C" void pq_launch_pack(const uint8_t* bytes, uint8_t* bitmap, int64_t n, void* st);

@@ -161,6 +161,8 @@ def _load() -> ctypes.CDLL:
     lib.comet_strfn_host.argtypes = [c.c_int32, c.c_char_p, c.c_int32, c.c_char_p, c.c_int32, c.c_char_p, c.c_int32, c.c_int64, c.c_void_p, c.c_int64]
     lib.comet_list_fn_host.restype = c.c_int32
     lib.comet_list_fn_host.argtypes = [c.c_int32, c.c_char_p, c.c_char_p, c.c_void_p, c.c_int64, c.c_int32, c.c_int32, c.c_void_p]
+    lib.comet_list_set_host.restype = c.c_int32
+    lib.comet_list_set_host.argtypes = [c.c_int32, c.c_int32, c.c_char_p, c.c_char_p, c.c_char_p, c.c_int64, c.c_char_p, c.c_char_p, c.c_char_p, c.c_int64, c.c_void_p]
     lib.comet_plan_codegen.restype = c.c_int64
     lib.comet_plan_codegen.argtypes = [c.c_char_p, c.c_size_t, c.c_char_p, c.c_int32, c.c_void_p, c.c_int64]
     lib.comet_error_site_json.restype = c.c_int64
@@ -1253,10 +1255,8 @@ def strfn_host(op: int, value: bytes, a: bytes = b"", b: bytes = b"", k: int = 0
     return buf.raw[:n]
 
 
-def list_fn_host(kind: int, values: Sequence, op: int, flags: int = 0) -> List[int]:
-    """csrc/device/list_fn.hpp on the host over ONE list (comet_list_fn_host).  kind: 0 Boolean, 1 / 2 / 4 / 8 / 16 signed integers of that many bytes, 32 Utf8
-    (bytes values); None is a NULL element.  op 0 sort (flags: 1 descending | 2 NULLs last) → the element index that stands in every slot; op 1 distinct →
-    a keep flag per element"""
+def _list_buffers(kind: int, values: Sequence):
+    """one list's elements as the (data, aux, validity) bytes of comet_list_fn_host / comet_list_set_host"""
     n = len(values)
     valid = bytearray((n + 7) // 8 + 1)
     for i, v in enumerate(values):
@@ -1277,11 +1277,34 @@ def list_fn_host(kind: int, values: Sequence, op: int, flags: int = 0) -> List[i
         data, aux = struct.pack("<%di" % len(offs), *offs), b"".join(parts)
     else:
         data = b"".join(int(v or 0).to_bytes(kind, "little", signed=True) for v in values)
+    return data or b"\0", aux or b"\0", valid
+
+
+def list_fn_host(kind: int, values: Sequence, op: int, flags: int = 0) -> List[int]:
+    """csrc/device/list_fn.hpp on the host over ONE list (comet_list_fn_host).  kind: 0 Boolean, 1 / 2 / 4 / 8 / 16 signed integers of that many bytes, 32 Utf8
+    (bytes values); None is a NULL element.  op 0 sort (flags: 1 descending | 2 NULLs last) → the element index that stands in every slot; op 1 distinct →
+    a keep flag per element"""
+    n = len(values)
+    data, aux, valid = _list_buffers(kind, values)
     out = (ctypes.c_uint32 * max(n, 1))()
     vbuf = (ctypes.c_uint8 * len(valid)).from_buffer(valid)
-    if lib().comet_list_fn_host(kind, data or b"\0", aux or b"\0", vbuf, n, op, flags, out) != 0:
+    if lib().comet_list_fn_host(kind, data, aux, vbuf, n, op, flags, out) != 0:
         _raise_last(0)
     return list(out[:n])
+
+
+def list_set_host(op: int, kind: int, a: Sequence, b: Sequence):
+    """csrc/device/list_set.hpp on the host over ONE pair of lists (comet_list_set_host); kind and values as for list_fn_host.  op 0 union, 1 intersect, 2 except →
+    the result as a list of picks: i < len(a) is a[i], else b[i - len(a)].  op 3 overlap → True, False or None"""
+    da, xa, va = _list_buffers(kind, a)
+    db, xb, vb = _list_buffers(kind, b)
+    out = (ctypes.c_uint32 * max(len(a) + len(b), 1))()
+    r = lib().comet_list_set_host(op, kind, da, xa, bytes(va), len(a), db, xb, bytes(vb), len(b), out)
+    if r < 0:
+        _raise_last(0)
+    if op == 3:
+        return [False, True, None][r]
+    return list(out[:r])
 
 
 def plan_codegen(plan: bytes, has_valid: Sequence[bool]) -> dict:

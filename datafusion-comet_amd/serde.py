@@ -452,6 +452,26 @@ def array_position(child: Expr, key: Expr) -> Expr:
     return scalar_func("spark_array_position", [child, key])
 
 
+def array_union(a: Expr, b: Expr) -> Expr:
+    """ArrayUnion(a, b): ScalarFunc array_union, no return type (serde/arrays.scala)"""
+    return scalar_func("array_union", [a, b])
+
+
+def array_intersect(a: Expr, b: Expr) -> Expr:
+    """ArrayIntersect(a, b): ScalarFunc array_intersect (sent under spark.comet.expression.ArrayIntersect.allowIncompatible)"""
+    return scalar_func("array_intersect", [a, b])
+
+
+def array_except(a: Expr, b: Expr) -> Expr:
+    """ArrayExcept(a, b): ScalarFunc array_except (sent under spark.comet.expression.ArrayExcept.allowIncompatible)"""
+    return scalar_func("array_except", [a, b])
+
+
+def arrays_overlap(a: Expr, b: Expr) -> Expr:
+    """ArraysOverlap(a, b): ScalarFunc spark_arrays_overlap with the return type Boolean, as the JVM sends it"""
+    return scalar_func("spark_arrays_overlap", [a, b], T_BOOL)
+
+
 def map_keys(m: Expr) -> Expr:
     """MapKeys(m): ScalarFunc map_keys, no return type (serde/maps.scala)"""
     return scalar_func("map_keys", [m])

@@ -270,6 +270,12 @@ int64_t comet_strfn_host(int32_t op, const uint8_t* value, int32_t n, const uint
  * elements' validity bits or NULL; op 0 sort (flags: 1 descending | 2 NULLs last) → out[slot] = the element that stands there; op 1 distinct → out[i] = 1 when
  * element i stays.  out holds n entries.  0, or -2 and comet_last_error(0).  Needs no GPU. */
 int32_t comet_list_fn_host(int32_t kind, const void* data, const uint8_t* aux, const uint8_t* valid, int64_t n, int32_t op, int32_t flags, uint32_t* out);
+/* (TEST ABI) array_union / array_intersect / array_except / arrays_overlap of ONE pair of lists by csrc/device/list_set.hpp's find, member, overlap and concatenation code on
+ * the host, in the executor's steps — diagnostic entry.  op 0 union, 1 intersect, 2 except, 3 overlap; kind and the two element arrays (a: na elements, b: nb) as for
+ * comet_list_fn_host.  op 0 - 2: the number of elements of the result, out[i] = where its i-th element comes from — element out[i] of a when out[i] < na, else element
+ * out[i] - na of b (out holds na + nb entries).  op 3: 0 false, 1 true, 2 NULL.  -2 and comet_last_error(0).  Needs no GPU. */
+int32_t comet_list_set_host(int32_t op, int32_t kind, const void* a_data, const uint8_t* a_aux, const uint8_t* a_valid, int64_t na, const void* b_data, const uint8_t* b_aux,
+                            const uint8_t* b_valid, int64_t nb, uint32_t* out);
 #endif /* COMET_TEST_ABI */
 
 /* regexp_extract_all(value, pattern, group) (string_funcs/regexp_extract_all.rs) by the device's two passes (rx_find_all) on the host: the number of matches,

@@ -137,6 +137,16 @@ def probes():
         "ArrayMin": (S.array_min(S.col(7, S.list_type(S.T_INT64))), "of a list COLUMN or a derived list of Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal elements, any length; Utf8 is refused (`sort_array(x)[0]` serves)"),
         "ArrayMax": (S.array_max(S.col(7, S.list_type(S.T_INT64))), "as ArrayMin"),
         "ArrayPosition": (S.array_position(S.col(7, S.list_type(S.T_INT64)), L(3, S.T_INT64)), "`spark_array_position` → Int64: elements of Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal of any precision (beyond 18 digits compared as 128-bit values) with a key of the element's type, literal or column; lists of strings with a literal key"),
+        "ArrayUnion": (S.array_union(S.col(7, S.list_type(S.T_INT64)), S.col(7, S.list_type(S.T_INT64))),
+                       "`array_union(a, b)`: distinct(a ++ b), first occurrences, a's before b's, NULL elements as one value, NULL when either list is; both arguments list COLUMNS or derived "
+                       "lists with exactly equal element types of Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal / Utf8, lists of any length; a derived list column of the chain's source (§4)"),
+        "ArraysOverlap": (S.arrays_overlap(S.col(7, S.list_type(S.T_INT64)), S.col(7, S.list_type(S.T_INT64))),
+                          "`spark_arrays_overlap(a, b)` → Boolean, three-valued: true for a common non-NULL value, else NULL beside a NULL element unless a side is empty, else false; arguments as ArrayUnion; "
+                          "a derived Boolean column, usable in a Filter"),
+        "ArrayIntersect": (S.array_intersect(S.col(7, S.list_type(S.T_INT64)), S.col(7, S.list_type(S.T_INT64))),
+                           "under spark.comet.expression.ArrayIntersect.allowIncompatible: the distinct elements of a, in a's order, that occur in b — Spark's answer (§5); arguments as ArrayUnion"),
+        "ArrayExcept": (S.array_except(S.col(7, S.list_type(S.T_INT64)), S.col(7, S.list_type(S.T_INT64))),
+                        "under spark.comet.expression.ArrayExcept.allowIncompatible: the distinct elements of a, in a's order, that do not occur in b, a NULL element included — Spark's answer (§5); arguments as ArrayUnion"),
         "GetMapValue": (S.map_extract(S.col(8, MSL), L("k", S.T_STRING)),
                         "`map_extract(m, k)` — `m[k]` and `element_at(m, k)`: the value of the first entry whose key equals k, NULL for a NULL map / key and when there is none, never an error; "
                         "a map COLUMN of the chain's source with Boolean / integer / Date / Timestamp / TimestampNTZ / Decimal (any precision) / Utf8 keys, the key a literal or a column of "
@@ -324,9 +334,9 @@ def render() -> str:
     w("  than 4096 rows, lag / lead defaults of Utf8 / Boolean type.")
     w("* Nested types: struct-of-flat, list-of-flat, list-of-flat-struct and map columns are read from Parquet, passed through Filter / Projection / Sort /")
     w("  Limit / ShuffleWriter, taken apart by `GetStructField` and exported; struct / list columns of any depth arrive through Scan / ShuffleScan inputs;")
-    w("  `Explode` of a list column runs; `size`, `arr[i]` / `element_at`, `array_contains`, `sort_array`, `array_distinct`, `array_min` / `array_max` and `array_position` over a")
-    w("  list COLUMN of flat elements run; `m[k]` / `element_at(m, k)`, `map_keys`, `map_values`, `map_entries` and `map_contains_key` over a map COLUMN run;")
-    w("  deeper trees in the Parquet scan, `Explode` of a map (the JVM never sends one), the other array / map functions (`map_from_arrays`, `map_from_entries`, `map_concat`,")
+    w("  `Explode` of a list column runs; `size`, `arr[i]` / `element_at`, `array_contains`, `sort_array`, `array_distinct`, `array_min` / `array_max`, `array_position`,")
+    w("  `array_union`, `array_intersect`, `array_except` and `arrays_overlap` over list COLUMNS of flat elements run; `m[k]` / `element_at(m, k)`, `map_keys`, `map_values`, `map_entries` and `map_contains_key` over a map COLUMN run;")
+    w("  deeper trees in the Parquet scan, `Explode` of a map (the JVM never sends one), the other array / map functions (`array_remove`, `slice`, `array_join`, `flatten`, `array_repeat`, `array_append` / `array_insert`, `map_from_arrays`, `map_from_entries`, `map_concat`,")
     w("  `str_to_map`, the lambda functions) and everything that builds a struct / an array / a map are refused.")
     w("  Parquet: TIMESTAMP(NANOS) / TIME, encrypted files.")
     w("* `SortArray`, `ArrayDistinct`, `ArrayMin`, `ArrayMax`, `ArrayPosition`: Float32 / Float64 elements (Spark and the reference disagree on signed zeros there, the")
@@ -338,6 +348,14 @@ def render() -> str:
     w("  1000-byte sort key (values are padded to the column's longest) fails the task with that operator's message.  Both refuse a sliced list column — a non-zero Arrow offset on")
     w("  the list or its elements, or element offsets that do not start at 0 — at run time, by name; no producer in this engine delivers one (a Scan leaf rebases what it")
     w("  uploads, device-resident inputs carry no lists), so no plan meets this today.")
+    w("* `ArrayUnion`, `ArrayIntersect`, `ArrayExcept`, `ArraysOverlap`: what the list functions above refuse — Float32 / Float64, Binary, struct, list and map elements; a map")
+    w("  argument; an argument that is neither a list COLUMN of the chain's source nor a derived list (a computed or literal `array(3, 4, 5)`) —, an argument count other than")
+    w("  two, two element types that are not exactly equal, a decimal's precision and scale included (both are named; Spark casts the sides to one type before it sends the")
+    w("  function), `spark_arrays_overlap` with a return type other than Boolean; inside an aggregate's fused chain (project them below it; under a join the side that holds")
+    w("  them is materialised instead of fused, and runs).  They are built from `array_distinct` and `array_sort` and a binary search per element, so lists of any length run and")
+    w("  the limits of those two come along: a column that holds a list beyond 256 elements goes through the Sort operator's radix sort, where a Utf8 element beyond the")
+    w("  1000-byte sort key fails the task with that operator's message; a sliced list column on either side is refused at run time, by name.  2^31 elements of both sides")
+    w("  together and a Utf8 result beyond 2 GiB fail the task by name.  A set function takes the column slots of its result — two, one for `arrays_overlap` — of a pipeline's 24.")
     w("* `GetMapValue` / `ElementAt` over a map (`map_extract`), `MapKeys`, `MapValues`, `MapEntries`: a map argument that is not a map COLUMN of the chain's source (a computed")
     w("  map, a map inside a struct); for `map_extract`, `map_keys` and `map_values` a map with a nested key or a nested value (`map_entries` takes any map the engine passes")
     w("  through).  `map_extract`: Float32 / Float64 keys (Spark's ordering and an array comparison disagree on -0.0 and NaN keys), Binary keys, Binary values; a key")
@@ -388,6 +406,11 @@ def render() -> str:
     w("  defined: a `collect_list`'s elements stand in the plan's input order — Partial: batches in the order pulled, rows in batch order; merging: state rows in input")
     w("  order, each list's elements in list order —, a `collect_set`'s in ascending order of the engine's sort key (value order; Utf8 by bytes, then length).  Both are the")
     w("  same bits for every batch size and grid (`tests/test_collect_gpu.py`).  A set's equality is equality of those key bytes, which is value equality for every type it takes.")
+    w("* `array_intersect` / `array_except`: the reference calls its own native path Incompatible and sends the functions only under `allowIncompatible` — DataFusion orders")
+    w("  an intersection by the LONGER side (`array_intersect([2, 1], [3, 1, 2])` is `[1, 2]` there; the reference's SQL test sorts such results before it compares), and its")
+    w("  except differs from Spark in NULL handling.  Here both give Spark's answer — the distinct elements of the left argument in the left argument's order, a NULL element")
+    w("  kept or dropped like a value — which is what the JVM's fallback gives and what the reference's SQL tests expect (`tests/test_list_set_gpu.py`).  `array_union` and")
+    w("  `arrays_overlap` are Compatible on both sides.")
     w("* Join and hash-aggregate OUTPUT ORDER is unspecified in the reference (hash-table order per batch); tests compare multisets.  A sort-merge join's output is")
     w("  ordered by its keys only where that order is observable (plan output, Limit, shuffle file).")
     w("* Everything else on the path — integers, decimals (HALF_UP, overflow → NULL / ANSI error), dates, timestamps, strings, hashes (murmur3 / xxhash64), partition")
