@@ -518,7 +518,24 @@ int64_t comet_plan_codegen(const uint8_t* plan, size_t plan_len, const uint8_t* 
         if (op->children.size() != 1 || op->children[0]->kind != OpKind::Scan) throw CometError("comet_plan_codegen: a Sort root is expected directly over its Scan leaf");
         d = generate_sort_keys(*op, types, hv);
       } else {
-        d = nested ? generate_pipeline(*op, hv, &types) : generate_pipeline(*op, hv);
+        // COMET_CODEGEN_STR_FIXED_LEN="col:len,col:len" (a generator switch): the text of the variant the executor generates once it has verified (or
+        // predicted) a uniform length for those Utf8 columns — the only way to read that text without a GPU (tests/test_grouped_packed_key_cpu.py)
+        std::vector<int> fixed;
+        if (const char* e = getenv("COMET_CODEGEN_STR_FIXED_LEN")) {
+          fixed.assign(types.size(), -1);
+          for (const char* p = e; *p;) {
+            char* q = nullptr;
+            const long c = strtol(p, &q, 10);
+            if (q == p || *q != ':') throw CometError("COMET_CODEGEN_STR_FIXED_LEN: expected col:len[,col:len...]");
+            p = q + 1;
+            const long l = strtol(p, &q, 10);
+            if (q == p || c < 0 || (size_t)c >= types.size() || types[(size_t)c].id != TypeId::String || l < 0 || l > 15)
+              throw CometError("COMET_CODEGEN_STR_FIXED_LEN: column " + std::to_string(c) + " is not a Utf8 column of this scan, or its length is not in [0, 15]");
+            fixed[(size_t)c] = (int)l;
+            p = *q == ',' ? q + 1 : q;
+          }
+        }
+        d = nested ? generate_pipeline(*op, hv, &types) : generate_pipeline(*op, hv, nullptr, fixed.empty() ? nullptr : &fixed);
       }
     }
     std::string j = "{\"sink\":" + std::to_string((int)d.sink) + ",\"has_filter\":" + (d.has_filter ? "true" : "false") + ",\"R\":" + std::to_string(d.R) + ",\"derived\":" + std::to_string(d.derived.size()) +

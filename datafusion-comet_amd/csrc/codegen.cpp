@@ -4132,6 +4132,8 @@ struct AggSink {
   int out_j = 0;            // the next output column's slot
   // group keys → packed key words (word 0 = NULL bitmask of the keys)
   std::string key_code, key_emit;
+  struct PackedKey { int word, len; };      // a Utf8 key of verified length `len`: its first key word
+  std::vector<PackedKey> packed_keys;       // every key, if this is the fixed-length-key variant; else empty
   std::vector<ExprP> synthetic_exprs;
   int nk = 0;
   PrimSlot rowcnt;          // rows that reach the aggregate
@@ -4182,7 +4184,9 @@ struct AggSink {
     nk = 1;
     key_code += "        key[0] = 0;\n";
     int kj = 0;
+    bool packs = !g.str_fixed_len.empty();      // the fixed-length-key variant: every key a Utf8 column of a verified length, null bits + bytes ≤ 63 bits
     for (auto& ge : group_exprs) {
+      const int kw0 = nk;
       OutCol oc;
       std::string ok_expr;
       const std::string vb = out_val((size_t)out_j), ob = out_ok((size_t)out_j);
@@ -4251,9 +4255,33 @@ struct AggSink {
       oc.nullable = true;
       add_out(oc);
       ex << "  group key: " << explain_expr(ge) << " : " << oc.type.str() << "\n";
+      const int flen = direct_str && id_col < 0 && (size_t)ge->bound_index < g.str_fixed_len.size() ? g.str_fixed_len[(size_t)ge->bound_index] : -1;
+      if (flen < 0 || flen > 7 || d.in_types[(size_t)ge->bound_index].id != TypeId::String) packs = false;
+      else packed_keys.push_back({kw0, flen});
       kj++;
       if (kj > 60) throw CometError("too many group keys");
     }
+    int bits = kj;
+    for (auto& pk : packed_keys) bits += 8 * pk.len;
+    packs = packs && kj > 0 && bits <= 63;
+    if (!packs) packed_keys.clear();
+    d.fixed_key_variant = packs;
+  }
+  // P::pack_key / P::unpack_key of the fixed-length-key variant: word = the null bits (key[0]), then each key's L bytes (its first word; the second is the
+  // length byte L << 56, or 0 under a NULL, where lower_group_keys zeroes both)
+  void emit_packed_key(std::ostringstream& src) {
+    std::string pack = "key[0]", unpack = "    key[0] = w & " + std::to_string((1ull << packed_keys.size()) - 1) + "ull;\n";
+    int sh = (int)packed_keys.size();
+    for (size_t j = 0; j < packed_keys.size(); j++) {
+      const PackedKey& pk = packed_keys[j];
+      const std::string k0 = std::to_string(pk.word), k1 = std::to_string(pk.word + 1), s = std::to_string(sh);
+      if (pk.len > 0) pack += " | (key[" + k0 + "] << " + s + ")";
+      unpack += "    key[" + k0 + "] = " + (pk.len > 0 ? "(w >> " + s + ") & " + std::to_string((1ull << (8 * pk.len)) - 1) + "ull" : std::string("0ull")) + "; key[" + k1 + "] = (w & " +
+                std::to_string(1ull << j) + "ull) ? 0ull : " + std::to_string((unsigned long long)pk.len << 56) + "ull;\n";
+      sh += 8 * pk.len;
+    }
+    src << "#if COMET_GAGG_PACK_KEY\n  static __device__ __forceinline__ u64 pack_key(const u64* key) { return " << pack << "; }\n"
+        << "  static __device__ __forceinline__ void unpack_key(u64 w, u64* key) {\n" << unpack << "  }\n#endif\n";
   }
 
   // ---- count ----
@@ -4926,6 +4954,7 @@ struct AggSink {
     emit_switch("int kop(int k)", al.kops, "comet::", "comet::G_OR64");
     src << "  static __device__ __forceinline__ void kinit(u64* kacc) { for (int k = 0; k < (NKW > 0 ? NKW : 1); k++) kacc[k] = 0; }\n";
     src << "  static __device__ __forceinline__ void fold(const u64* pw, u64* val) {\n" << al.fold_code << "  }\n";
+    if (!packed_keys.empty()) emit_packed_key(src);
     const std::string update = "    _Pragma(\"unroll\") for (int r = 0; r < R; r++) {\n      if (k[r]) {\n        u64 key[NK]; u64 pv[NPW];\n" + key_code + al.pv_code +
                                al.kfeed_code + "        comet::group_update<P>(grp, true, key, pv);\n      }\n    }\n  }\n";
     emit_tile(src, "tile_grouped", "const comet::GroupCtx<P>& grp, u64* kacc", update);

@@ -112,6 +112,9 @@ struct PipelineDesc {
   // grouped aggregates: source columns that serve DIRECTLY as Utf8 group keys (the executor measures their longest value: above 15
   // bytes the key travels as a representative row index instead of packed bytes, see dict_id_col)
   std::vector<int> str_key_cols;
+  // grouped aggregate generated on verified Utf8 lengths whose keys pack into one word (the fixed-length-key variant: packed LDS probe; the
+  // executor sizes its k_gagg grid from the loaded function's occupancy)
+  bool fixed_key_variant = false;
   // exact Float64 sums (comet_device.hpp "Exact Float64 sums"): per sum f its first canonical accumulator word (3 words, 192-bit fixed
   // point) and the aux words (u64 index after the 16-byte error header) that collect the exponent range seen; the scales travel packed
   // 16 bits each in prm.iarg[kFixScaleArg]

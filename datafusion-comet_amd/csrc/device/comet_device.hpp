@@ -2222,9 +2222,22 @@ struct LSlot {
   u64 pad[((1 + NK + NPW) % 2 == 0) ? 1 : 0];
 };
 
+// the grouped aggregate's fixed-length-key variant (COMET_JIT_DEFINES switches): probe the LDS table on the packed key word
+#ifndef COMET_GAGG_PACK_KEY
+#define COMET_GAGG_PACK_KEY 1
+#endif
+// A grouped aggregate whose keys are all Utf8 columns of a known uniform length (the executor's fixed-length variant) and whose bytes and null bits fit
+// one word has P::pack_key(key[NK]) → u64, injective, and P::unpack_key(u64, key[NK]), its inverse.  The block's LDS table then hashes, stores and compares
+// that ONE word — a Q1 row's probe was five 64-bit hash rounds and five compares for two bytes of key —, and the NK words are rebuilt only where a key leaves
+// the block: the global table, k_gemit, k_grehash, the Partial state and the partitioned kernels keep them.  (COMET_GAGG_PACK_KEY=0: the generator leaves
+// pack_key out.)
+template <class P, class = void> struct has_pack { static constexpr bool value = false; };
+template <class P> struct has_pack<P, decltype((void)&P::pack_key)> { static constexpr bool value = true; };
+template <class P> struct LSlotOf { typedef LSlot<has_pack<P>::value ? 1 : P::NK, P::NPW> type; };
+
 template <class P>
 struct GroupCtx {
-  COMET_LDS LSlot<P::NK, P::NPW>* lds;  // per-block table (LDS)
+  COMET_LDS typename LSlotOf<P>::type* lds;  // per-block table (LDS)
   COMET_LDS u32* lds_count;             // number of groups inserted into the LDS table (dense ordinals)
   COMET_LDS u32* ord_slot;              // ordinal (< P::GC) → LDS slot index
   COMET_LDS u64* priv;                  // [GC][NPW][COPIES] private accumulator copies
@@ -2292,9 +2305,10 @@ CDEV u64 pword_combine(int k, u64 a, u64 b) {
 // agent-scope acquire/release (= L1/L2 invalidate + write-back per row) is needed here.
 // Returns the slot and its dense ordinal (order of first insertion within the block).
 template <class P>
-CDEV COMET_LDS LSlot<P::NK, P::NPW>* lds_find_or_insert(const GroupCtx<P>& g, const u64* key, u32& ordinal) {
-  typedef COMET_LDS LSlot<P::NK, P::NPW> S;
-  u32 h = (u32)hash_key<P::NK>(key) & (u32)(P::LDS_CAP - 1);
+CDEV COMET_LDS typename LSlotOf<P>::type* lds_find_or_insert(const GroupCtx<P>& g, const u64* key, u32& ordinal) {
+  typedef COMET_LDS typename LSlotOf<P>::type S;
+  constexpr int LK = has_pack<P>::value ? 1 : P::NK;      // the key words of an LDS slot (`key` holds as many: the packed word, or the NK words)
+  u32 h = (u32)hash_key<LK>(key) & (u32)(P::LDS_CAP - 1);
   for (int probes = 0; probes < 16;) {
     S* s = g.lds + h;
     u32 st = __hip_atomic_load(&s->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2303,7 +2317,7 @@ CDEV COMET_LDS LSlot<P::NK, P::NPW>* lds_find_or_insert(const GroupCtx<P>& g, co
       if (__hip_atomic_compare_exchange_strong(&s->state, &expected, kSlotBusy, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_WORKGROUP)) {
 #pragma unroll
-        for (int k = 0; k < P::NK; k++) s->key[k] = key[k];
+        for (int k = 0; k < LK; k++) s->key[k] = key[k];
 #pragma unroll
         for (int k = 0; k < P::NPW; k++) s->acc[k] = P::pidentity(k);
         u32 ord = __hip_atomic_fetch_add(g.lds_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2318,7 +2332,7 @@ CDEV COMET_LDS LSlot<P::NK, P::NPW>* lds_find_or_insert(const GroupCtx<P>& g, co
     if (st == kSlotBusy) continue;  // owner is publishing; it never waits on us
     bool eq = true;
 #pragma unroll
-    for (int k = 0; k < P::NK; k++) eq &= (s->key[k] == key[k]);
+    for (int k = 0; k < LK; k++) eq &= (s->key[k] == key[k]);
     if (eq) {
       ordinal = s->ord;
       return s;
@@ -2351,8 +2365,14 @@ CDEV void group_update(const GroupCtx<P>& g, bool active, const u64* key, const 
     return;
   }
   u32 ord = kNoOrdinal;
-  COMET_LDS LSlot<P::NK, P::NPW>* ls = nullptr;
-  if (P::LDS_CAP > 0) ls = lds_find_or_insert<P>(g, key, ord);
+  COMET_LDS typename LSlotOf<P>::type* ls = nullptr;
+  u64 packed = 0;      // (a packed key: from here on the row carries this word, not its NK words)
+  if constexpr (has_pack<P>::value) {
+    packed = P::pack_key(key);
+    if (P::LDS_CAP > 0) ls = lds_find_or_insert<P>(g, &packed, ord);
+  } else {
+    if (P::LDS_CAP > 0) ls = lds_find_or_insert<P>(g, key, ord);
+  }
   if (ord < (u32)P::GC) {
     COMET_LDS u64* base = g.priv + (u32)(ord * P::NPW) * P::COPIES + (threadIdx.x & (P::COPIES - 1));
 #pragma unroll
@@ -2368,7 +2388,13 @@ CDEV void group_update(const GroupCtx<P>& g, bool active, const u64* key, const 
   u64 val[P::NW];
   P::fold(pv, val);
   bool fresh = false;
-  Slot<P::NK, P::NW>* s = table_find_or_insert<P::NK, P::NW>(g.glb, g.glb_cap, key, SlotInitWith<P>{val}, kMaxGlobalProbes, g.counter(), &fresh);
+  u64 fkey[P::NK];
+  const u64* gkey = key;
+  if constexpr (has_pack<P>::value) {      // (rebuilt from the word, so that the NK words are not live across the LDS probe)
+    P::unpack_key(packed, fkey);
+    gkey = fkey;
+  }
+  Slot<P::NK, P::NW>* s = table_find_or_insert<P::NK, P::NW>(g.glb, g.glb_cap, gkey, SlotInitWith<P>{val}, kMaxGlobalProbes, g.counter(), &fresh);
   if (!s) { g.set_full(); return; }
   if (!fresh) slot_apply<P, __HIP_MEMORY_SCOPE_AGENT>(&s->acc[0], val);
 }
@@ -2398,7 +2424,7 @@ CDEV bool utf8_guard_ok(const CometKParams& prm, u64 guard) {
 template <class P>
 CDEV void agg_grouped_body(const CometKParams& prm) {
   typedef Slot<P::NK, P::NW> S;
-  typedef LSlot<P::NK, P::NPW> LS;
+  typedef typename LSlotOf<P>::type LS;
   if (prm.iarg[kGuardArg] != 0 && !utf8_guard_ok(prm, (u64)prm.iarg[kGuardArg])) {      // (uniform over the launch: every workgroup leaves, nothing is touched)
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr((unsigned int*)prm.out[2], kErrUtf8Guard);
     return;
@@ -2460,8 +2486,12 @@ CDEV void agg_grouped_body(const CometKParams& prm) {
     LS* ls = &s_tbl[i];
     if (ls->state == kSlotReady) {
       u64 key[P::NK], pw[P::NPW], val[P::NW];
+      if constexpr (has_pack<P>::value) {
+        P::unpack_key(ls->key[0], key);
+      } else {
 #pragma unroll
-      for (int k = 0; k < P::NK; k++) key[k] = ls->key[k];
+        for (int k = 0; k < P::NK; k++) key[k] = ls->key[k];
+      }
 #pragma unroll
       for (int k = 0; k < P::NPW; k++) pw[k] = ls->acc[k];
       P::fold(pw, val);

@@ -101,8 +101,16 @@ void ExecutionContext::process_chunk(const std::vector<DeviceColumnView>& cols, 
     }
     const int64_t tile = (int64_t)d.R * 256;
     int grid_mult = 4;
+    int64_t grid_cap = 0;
     if (const char* e = getenv("COMET_GROUPED_GRID_MULT")) grid_mult = std::max(1, atoi(e));
-    int grid = (int)std::min<int64_t>((n + tile - 1) / tile, 256 * grid_mult);
+    else if (d.fixed_key_variant) {
+      // the fixed-length-key variant streams a fact table: as many workgroups as are resident at once, so that every compute unit holds the same number
+      // (SF100 Q1: 5 per CU fit, 1280 — the 1154 that the row bound below asks for left 126 CUs with five and 130 with four).  COMET_GROUPED_GRID_FILL=0: as before
+      static const bool fill = !getenv("COMET_GROUPED_GRID_FILL") || atoi(getenv("COMET_GROUPED_GRID_FILL")) != 0;
+      if (fill) grid_cap = v.mod->resident_blocks("k_gagg", 256);
+    }
+    if (grid_cap <= 0) grid_cap = 256 * grid_mult;
+    int grid = (int)std::min<int64_t>((n + tile - 1) / tile, grid_cap);
     // carry-save LDS accumulation bounds the rows one block may add (comet::kMaxRowsPerBlock = 2^19)
     const int64_t per_block_cap = ((int64_t)1 << 19) - 2 * tile;
     grid = (int)std::max<int64_t>(grid, (n + per_block_cap - 1) / per_block_cap);

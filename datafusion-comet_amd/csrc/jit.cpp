@@ -221,6 +221,18 @@ hipFunction_t LoadedModule::fn(const std::string& name) {
   return f;
 }
 
+int LoadedModule::resident_blocks(const std::string& name, int block) {
+  hipFunction_t f = fn(name);
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = resident.find(name);
+  if (it != resident.end()) return it->second;
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, block, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 || cus <= 0)
+    per_cu = cus = 0;
+  return resident[name] = per_cu * cus;
+}
+
 LoadedModule::~LoadedModule() {
   if (mod) (void)hipModuleUnload(mod);
 }

@@ -28,6 +28,10 @@ struct LoadedModule {
   std::mutex mu;
   std::shared_ptr<CodeObject> keepalive;
   hipFunction_t fn(const std::string& name);
+  // workgroups of `block` threads of kernel `name` that are resident at once on the module's device (occupancy × compute units); asked once per kernel.
+  // 0: the runtime could not say
+  int resident_blocks(const std::string& name, int block);
+  std::map<std::string, int> resident;
   ~LoadedModule();
 };
 
