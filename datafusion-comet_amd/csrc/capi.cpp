@@ -31,6 +31,7 @@ namespace comet_strfn_host_ns {
 }
 #include "device/list_fn.hpp"      // (array_sort / array_distinct's per-element code, as the host sees it: comet_list_fn_host below)
 #include "device/list_set.hpp"     // (… and the two-list set functions': comet_list_set_host)
+#include "device/list_pick.hpp"    // (… and the one-list functions that pick elements or join them: comet_list_pick_host)
 #include "row_shuffle.hpp"
 #include "tz.hpp"
 
@@ -863,6 +864,71 @@ int32_t comet_list_set_host(int32_t op, int32_t kind, const void* a_data, const 
     int32_t kept = 0;
     for (size_t e = 0; e < first.size(); e++)
       if (lf_member(da, (int64_t)e, bs, 0, nb, nullptr, nullptr, 0, op == LS_INTERSECT, false)) out[kept++] = (uint32_t)first[e];
+    return kept;
+  });
+}
+
+int64_t comet_list_pick_host(int32_t op, int32_t kind, const void* data, const uint8_t* aux, const uint8_t* valid, int64_t n, const void* key_data, const uint8_t* key_aux,
+                             const uint8_t* key_valid, int32_t key_is_column, int64_t start, int64_t length, const uint8_t* d, int32_t dn, const uint8_t* r, int32_t rn, void* out,
+                             int64_t cap) {
+  return guarded(nullptr, (int64_t)-2, [&]() -> int64_t {
+    if (kind != LF_BOOL && kind != LF_I8 && kind != LF_I16 && kind != LF_I32 && kind != LF_I64 && kind != LF_I128 && kind != LF_STR) throw CometError("comet_list_pick_host: unknown element kind");
+    if (op < LP_REMOVE || op > LP_JOIN || n < 0 || (n > 0 && (!data || !out)) || n > 0x7fffffffLL || (op == LP_REMOVE && !key_data) || (op == LP_JOIN && (kind != LF_STR || dn < 0 || (dn > 0 && !d) || (rn > 0 && !r))) ||
+        (op == LP_SLICE && (start == 0 || length < 0)))
+      throw CometError("comet_list_pick_host: bad arguments");
+    LfCol c;
+    c.data = data; c.aux = aux; c.valid = valid; c.offset = 0; c.kind = kind;
+    // the steps of exec.cpp extend_derived_list_pick over one row: one valid list of n elements
+    const int64_t offs[2] = {0, n};
+    if (op == LP_REVERSE) {
+      uint32_t* o = (uint32_t*)out;
+      for (int64_t e = 0; e < n; e++) o[lp_reverse_slot(offs[lf_list_of(offs, 1, e)], n, e)] = (uint32_t)e;
+      return n;
+    }
+    if (op == LP_JOIN) {
+      const bool has_rep = rn >= 0;
+      const int32_t rl = has_rep ? rn : 0;
+      std::vector<uint32_t> flag((size_t)n + 1, 0u), len((size_t)n + 1, 0u);
+      std::vector<int32_t> F((size_t)n + 1, 0), P((size_t)n + 1, 0);
+      for (int64_t e = 0; e < n; e++) flag[(size_t)e] = lp_is_piece(c, e, has_rep) ? 1u : 0u;
+      for (int64_t e = 0; e < n; e++) F[(size_t)e + 1] = F[(size_t)e] + (int32_t)flag[(size_t)e];
+      for (int64_t e = 0; e < n; e++)
+        if (lp_is_piece(c, e, has_rep)) len[(size_t)e] = lp_piece_len(c, e, F[(size_t)e] == F[(size_t)offs[lf_list_of(offs, 1, e)]], dn, rl);
+      for (int64_t e = 0; e < n; e++) P[(size_t)e + 1] = P[(size_t)e] + (int32_t)len[(size_t)e];
+      const int64_t total = P[(size_t)n];
+      if (total > cap) throw CometError("comet_list_pick_host: the output buffer is too small");
+      std::vector<uint8_t> bytes((size_t)total);      // exactly sized: a write past the end is a sanitizer report
+      for (int64_t e = 0; e < n; e++)
+        if (lp_is_piece(c, e, has_rep)) lp_piece_write(c, e, F[(size_t)e] == F[(size_t)offs[lf_list_of(offs, 1, e)]], d, dn, r, rl, bytes.data() + P[(size_t)e]);
+      if (total) memcpy(out, bytes.data(), (size_t)total);
+      return total;
+    }
+    LpKey k;
+    memset(&k, 0, sizeof k);
+    if (op == LP_REMOVE) {
+      LfCol kc;
+      kc.data = key_data; kc.aux = key_aux; kc.valid = key_valid; kc.offset = 0; kc.kind = kind;
+      if (key_is_column) {
+        if (kind == LF_STR) throw CometError("comet_list_pick_host: a key column over Utf8 elements");
+        if (lf_is_null(kc, 0)) return -1;      // the row is NULL
+        k.col = kc;
+        k.use_col = 1;
+      } else {
+        if (lf_is_null(kc, 0)) throw CometError("comet_list_pick_host: a NULL literal key");
+        k.key = lf_key(kc, 0);
+        if (kind == LF_STR) {
+          const int32_t* ko = (const int32_t*)key_data;
+          k.bytes = key_aux + ko[0];
+          k.len = ko[1] - ko[0];
+        }
+      }
+    }
+    uint32_t* o = (uint32_t*)out;
+    int64_t kept = 0;
+    for (int64_t e = 0; e < n; e++) {
+      const int64_t row = lf_list_of(offs, 1, e);
+      if (lp_keep(op, c, row, offs[row], offs[row + 1], e, k, start, length)) o[kept++] = (uint32_t)e;
+    }
     return kept;
   });
 }

@@ -15,6 +15,7 @@
 #include "regex.hpp"
 #include "tz.hpp"
 #include "kparams.h"
+#include "device/list_pick.hpp"      // (LP_REMOVE … LP_JOIN: the operations of DerivedCol kind 7)
 static_assert(comet::kErrBytes == COMET_ERR_BYTES && comet::kErrAuxWords == COMET_ERR_AUX_WORDS && comet::kErrDetailWord == COMET_ERR_DETAIL_WORD &&
               comet::kErrDetailStrBytes == COMET_ERR_DETAIL_STR_BYTES && 16 + 8 * COMET_ERR_AUX_WORDS <= 8 * COMET_ERR_DETAIL_WORD &&
               8 * COMET_ERR_DETAIL_WORD + 32 + COMET_ERR_DETAIL_STR_BYTES <= COMET_ERR_BYTES - 64, "the error block's layout (kparams.h) and codegen.hpp disagree");
@@ -514,6 +515,133 @@ ExprP lower_list_set(const ExprP& e) {
   r->has_dtype = true;
   return r;
 }
+// array_remove_all(arr, key), array_compact(arr), spark_array_slice(arr, start, length) → list, array_reverse(arr) and array_to_string(arr, delimiter[, replacement])
+// (serde/arrays.scala: what Spark's ArrayRemove, array_compact — an ArrayFilter by then —, Slice, Reverse of an array and ArrayJoin are sent as): a derived column of
+// kind 7 over ONE list — for the first four a list column and its elements as kind 4 is, for the join one Utf8 column as kind 3 is.  The list argument follows
+// lower_list_fn's rule.  remove compares, so its elements are those of check_list_fn_elem and its key follows spark_array_position's rule, tightened to what the
+// executor can hand a kernel: a non-NULL literal of exactly the element type, or for fixed-width elements a column of the chain's source of that type.  compact,
+// slice and reverse only move elements and take Float32 / Float64 too.  slice's start and length are literals (under the Cast … AS LONG the JVM wraps them in): a
+// start of 0 or a negative length raises in Spark only for rows it evaluates, and a derived column is computed before the chain's Filters (COMPAT.md §4).
+static int list_pick_op(const std::string& f);
+bool is_list_pick_fn(const std::string& f) { return list_pick_op(f) >= 0; }
+// the one table of the five names, by device/list_pick.hpp's operation (LP_REMOVE … LP_JOIN): the lowering, the aggregate-chain refusal and the executor read it
+static const char* const kListPickNames[] = {"array_remove_all", "array_compact", "spark_array_slice", "array_reverse", "array_to_string"};
+static int list_pick_op(const std::string& f) {
+  for (int op = LP_REMOVE; op <= LP_JOIN; op++)
+    if (f == kListPickNames[op]) return op;
+  return -1;
+}
+static_assert(kDerivedListJoin == LP_JOIN, "codegen.hpp names array_to_string's operation for DerivedCol::columns()");
+ExprP lower_list_pick(const ExprP& e) {
+  const std::string& f = e->func;
+  const int op = list_pick_op(f);
+  // (as for array_sort: a join materialises a side whose fold throws, so there this wording never reaches a user)
+  if (!g_derived || !g_source_cols)
+    throw CometError(f + " inside a join's or an aggregate's fused chain is not supported by the MI355X native engine yet (a derived list is computed over the source of a Projection / Filter chain)");
+  const size_t argc = e->children.size();
+  if (op == LP_REMOVE && argc != 2) throw CometError(f + " expects 2 arguments (array, key), got " + std::to_string(argc));
+  if ((op == LP_COMPACT || op == LP_REVERSE) && argc != 1) throw CometError(f + " expects one argument, got " + std::to_string(argc));
+  if (op == LP_SLICE && argc != 3) throw CometError(f + " expects 3 arguments (array, start, length), got " + std::to_string(argc));
+  if (op == LP_JOIN && argc != 2 && argc != 3) throw CometError(f + " expects 2 or 3 arguments (array, delimiter, [null replacement]), got " + std::to_string(argc));
+  const ExprP& subject = e->children[0];
+  const int nsrc = (int)g_source_cols->size();
+  if (subject->has_dtype && subject->dtype.id == TypeId::Map) throw CometError(f + " of a map is not supported by the MI355X native engine");
+  bool ok = subject->kind == ExprKind::Bound && subject->has_dtype && subject->dtype.id == TypeId::List && subject->dtype.kids.size() == 1 && subject->bound_index >= 0;
+  if (ok && subject->bound_index >= nsrc) {      // … a derived list: the index of one's first column
+    ok = false;
+    for (size_t k = 0; k < g_derived->size(); k++) ok |= (*g_derived)[k].is_list() && derived_index(nsrc, k) == subject->bound_index;
+  }
+  if (!ok) throw CometError(f + " is supported over a list COLUMN of the source or a derived list (split, array_sort …), not over a computed array, by the MI355X native engine");
+  DType et = subject->dtype.kids[0];
+  et.virt_parent = et.virt_kid = -1;
+  if (op == LP_JOIN) {
+    if (et.id != TypeId::String) throw CometError(f + " over " + et.str() + " elements is not supported by the MI355X native engine (a list of Utf8 only: Spark casts the elements before it sends the function)");
+  } else if (op == LP_REMOVE || !et.is_float()) {
+    check_list_fn_elem(f, et, true);      // (compact, slice and reverse only move elements: Float32 / Float64 pass, bit for bit)
+  }
+  DerivedCol dc;
+  dc.kind = 7;
+  dc.op = op;
+  dc.src = subject->bound_index;
+  if (op == LP_REMOVE) {
+    const ExprP& key = e->children[1];
+    DType kt = key->dtype;
+    kt.virt_parent = kt.virt_kid = -1;
+    if (key->kind == ExprKind::Literal) {
+      if (key->lit_null) throw CometError(f + " with a NULL literal key (NULL for every row) is not supported by the MI355X native engine");
+      if (!key->has_dtype || !(kt == et)) throw CometError(f + ": the key's type " + (key->has_dtype ? kt.str() : std::string("none")) + " is not the elements' " + et.str());
+      if (et.id == TypeId::String) {
+        dc.arg_a = key->lit_bytes;
+      } else {
+        // the literal as lf_key gives an element of its value (device/list_fn.hpp): the sign-flipped value, a decimal's in two halves
+        const uint64_t sign = 1ull << 63;
+        uint64_t hi = 0, lo = 0;
+        if (et.id == TypeId::Bool) lo = key->lit_bool ? 1 : 0;
+        else if (et.id == TypeId::Decimal) {
+          lo = (uint64_t)(u128)key->lit_dec;
+          hi = (uint64_t)((u128)key->lit_dec >> 64) ^ sign;
+        } else lo = (uint64_t)key->lit_i64 ^ sign;
+        dc.arg_a.assign((const char*)&hi, 8);
+        dc.arg_a.append((const char*)&lo, 8);
+      }
+    } else if (key->kind == ExprKind::Bound && key->bound_index >= 0 && key->bound_index < nsrc && key->has_dtype) {
+      if (!(kt == et)) throw CometError(f + ": the key's type " + kt.str() + " is not the elements' " + et.str());
+      if (et.id == TypeId::String) throw CometError(f + " over a list of strings is supported with a literal key");
+      dc.src2 = key->bound_index;
+    } else {
+      throw CometError(f + ": the key must be a literal or a column of the chain's source, not a computed value (MI355X native engine)");
+    }
+  } else if (op == LP_SLICE) {
+    auto int_lit = [&](size_t i, const char* what) -> long long {
+      ExprP x = e->children[i];
+      if (x->kind == ExprKind::Cast && x->children.size() == 1 && x->has_dtype && x->dtype.id == TypeId::Int64) x = x->children[0];
+      if (x->kind != ExprKind::Literal || !x->has_dtype || !x->dtype.is_integer())
+        throw CometError(f + ": " + what + " must be an integer literal, not a column or a computed value (Spark raises for a 0 start or a negative length per evaluated row: COMPAT.md)");
+      if (x->lit_null) throw CometError(f + ": a NULL " + what + " (NULL for every row) is not supported by the MI355X native engine");
+      return x->lit_i64;
+    };
+    dc.arg_k = int_lit(1, "the start");
+    dc.arg_n = int_lit(2, "the length");
+    if (dc.arg_k == 0) throw CometError(f + ": a start of 0 is not supported by the MI355X native engine (Spark raises \"Unexpected value for start\" for the rows it evaluates)");
+    if (dc.arg_n < 0) throw CometError(f + ": a negative length (" + std::to_string(dc.arg_n) + ") is not supported by the MI355X native engine (Spark raises \"Unexpected value for length\" for the rows it evaluates)");
+    DType rt = e->dtype;
+    if (e->has_dtype && rt.id == TypeId::List && rt.kids.size() == 1) rt.kids[0].virt_parent = rt.kids[0].virt_kid = -1;
+    if (!e->has_dtype || rt.id != TypeId::List || rt.kids.size() != 1 || !(rt.kids[0] == et))
+      throw CometError(f + " expects the return type list<" + et.str() + ">, got " + (e->has_dtype ? e->dtype.str() : std::string("none")));
+  } else if (op == LP_JOIN) {
+    auto str_lit = [&](size_t i, const char* what) -> std::string {
+      const ExprP& x = e->children[i];
+      if (x->kind != ExprKind::Literal || (x->dtype.id != TypeId::String && !x->lit_null)) throw CometError(f + ": " + what + " must be a string literal");
+      if (x->lit_null) throw CometError(f + " with a NULL " + what + " is not supported by the MI355X native engine");
+      return x->lit_bytes;
+    };
+    dc.arg_a = str_lit(1, "the delimiter");
+    if (argc == 3) {
+      dc.arg_b = str_lit(2, "the null replacement");
+      dc.has_b = true;
+    }
+  }
+  if (op == LP_JOIN) {
+    dc.type = DType::of(TypeId::String);
+  } else {
+    dc.type = subject->dtype;
+    dc.type.virt_parent = dc.type.virt_kid = -1;
+    dc.type.kids[0].virt_parent = dc.type.kids[0].virt_kid = -1;
+  }
+  size_t k = 0;
+  for (; k < g_derived->size(); k++) {
+    const DerivedCol& o = (*g_derived)[k];
+    if (o.kind == 7 && o.op == dc.op && o.src == dc.src && o.src2 == dc.src2 && o.arg_a == dc.arg_a && o.arg_b == dc.arg_b && o.has_b == dc.has_b && o.arg_k == dc.arg_k && o.arg_n == dc.arg_n) break;
+  }
+  if (k == g_derived->size()) g_derived->push_back(dc);
+  auto r = std::make_shared<Expr>();
+  r->kind = ExprKind::Bound;
+  r->proto_tag = 3;
+  r->bound_index = derived_index(nsrc, k);
+  r->dtype = (*g_derived)[k].type;
+  r->has_dtype = true;
+  return r;
+}
 // map_keys(m), map_values(m) and map_entries(m) (serde/maps.scala: Spark's MapKeys / MapValues / MapEntries, sent without a return type): a derived list column
 // of kind 5, a VIEW — a map is laid out as offsets over the entries Struct(key, value), so the list shares the map's offsets and validity and its element column
 // IS the key column, the value column or the entries struct.  Nothing is copied and no kernel runs (exec.cpp extend_derived_map_view).  The argument is a map
@@ -594,6 +722,10 @@ ExprP substitute(const ExprP& e, const std::vector<ExprP>& cols, std::map<const 
     auto n = std::make_shared<Expr>(*e);
     for (auto& c : n->children) c = substitute(c, cols, memo);
     out = lower_list_set(n);
+  } else if (e->kind == ExprKind::ScalarFunc && is_list_pick_fn(e->func)) {
+    auto n = std::make_shared<Expr>(*e);
+    for (auto& c : n->children) c = substitute(c, cols, memo);
+    out = lower_list_pick(n);
   } else if (e->kind == ExprKind::ScalarFunc && is_map_view_fn(e->func)) {
     auto n = std::make_shared<Expr>(*e);
     for (auto& c : n->children) c = substitute(c, cols, memo);
@@ -3905,6 +4037,8 @@ std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool
     if (dc.kind == 3) continue;
     // a set function's list is NULL where either source is; arrays_overlap answers NULL beside NULL elements too, so its one column always carries validity
     if (dc.kind == 6) valid_all.back() = dc.op == kDerivedListOverlap || valid_all.at((size_t)dc.src) || valid_all.at((size_t)dc.src2);
+    // array_remove over a key column is NULL where the list or the key is
+    if (dc.kind == 7 && dc.src2 >= 0) valid_all.back() = valid_all.at((size_t)dc.src) || valid_all.at((size_t)dc.src2);
     if (!dc.is_list()) continue;
     bool elem_valid = false;      // split's pieces are never NULL; a sorted / distinct list's elements are NULL where its source's are
     // (virt_kid 0 of a List is its element column; of a Map its key column, and virt_kid 1 its value column)
@@ -3914,7 +4048,7 @@ std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool
         if (d.in_types[j].virt_parent == src && d.in_types[j].virt_kid == 0 && d.in_types[(size_t)src].id == TypeId::List) v = valid_all[j];
       return v;
     };
-    if (dc.kind == 4) elem_valid = elems_valid(dc.src);
+    if (dc.kind == 4 || dc.kind == 7) elem_valid = elems_valid(dc.src);      // (array_compact's elements keep their declared nullability: a bitmap of ones)
     // intersect and except keep elements of a; union's come from either side
     if (dc.kind == 6) elem_valid = elems_valid(dc.src) || (dc.op == 0 && elems_valid(dc.src2));
     // map_values: keys and entries are never NULL; values carry validity bits whenever the map's type lets them be NULL (the plan does not see the value column
@@ -3936,6 +4070,9 @@ std::vector<bool> append_derived_columns(PipelineDesc& d, const std::vector<bool
     if (dc.kind == 6 && under_agg)
       throw CometError(std::string(dc.op == 0 ? "array_union" : dc.op == 1 ? "array_intersect" : dc.op == 2 ? "array_except" : "spark_arrays_overlap") +
                        " inside an aggregate's chain is not supported by the MI355X native engine yet (project it below the aggregate)");
+  for (auto& dc : d.derived)
+    if (dc.kind == 7 && under_agg)
+      throw CometError(std::string(list_pick_name(dc.op)) + " inside an aggregate's chain is not supported by the MI355X native engine yet (project it below the aggregate)");
   if (!d.derived.empty() && under_agg) throw CometError("split inside an aggregate's chain is not supported by the MI355X native engine yet");
   if (d.in_types.size() > COMET_MAX_IN) throw CometError("too many scan columns for one GPU pipeline");
   return valid_all;
@@ -5011,6 +5148,9 @@ struct AggSink {
 };
 
 }  // namespace
+
+// (declared in codegen.hpp: the executor names the function in its messages by the same table)
+const char* list_pick_name(int op) { return op >= LP_REMOVE && op <= LP_JOIN ? kListPickNames[op] : "a list function"; }
 
 // ---------------------------------------------------------------------------------------------
 // generate_pipeline

@@ -41,6 +41,7 @@ struct OutCol {
 };
 
 constexpr int kDerivedListOverlap = 3;      // DerivedCol kind 6: the op of arrays_overlap (device/list_set.hpp LS_OVERLAP), the one set function that is one column
+constexpr int kDerivedListJoin = 4;         // DerivedCol kind 7: the op of array_to_string (device/list_pick.hpp LP_JOIN), the one function of its family that is one column
 // A column the executor computes over the chain's SOURCE table before the fused kernel runs, addressed by the chain like a source column
 // (in_types holds it behind the source's own columns): today split(<Utf8 column>, <pattern literal>, <limit literal>) → list<string>,
 // which the chain passes through by row index like any nested column.
@@ -51,14 +52,20 @@ struct DerivedCol {
                                     //    elements are the key column, the value column or the entries struct (two columns, as split; nothing is copied)
                                     // 6: array_union / array_intersect / array_except (two columns, as kind 4) and arrays_overlap (one Boolean column, as kind 3 is
                                     //    one Utf8 column) of TWO list columns, src and src2 (device/list_set.hpp)
+                                    // 7: array_remove_all / array_compact / spark_array_slice / array_reverse (two columns, as kind 4) and array_to_string (one Utf8
+                                    //    column, as kind 3) of ONE list column (device/list_pick.hpp)
   int op = 0;                       // kind 3: device/strfn.hpp's operation (SF_REVERSE …), or kDerivedRegexpReplace; kind 4: device/list_fn.hpp's LF_OP_SORT / LF_OP_DISTINCT;
-                                    // kind 5: 0 keys, 1 values, 2 entries; kind 6: device/list_set.hpp's LS_UNION / LS_INTERSECT / LS_EXCEPT / LS_OVERLAP
-  std::string arg_a, arg_b;         // kind 3: the literal arguments' bytes (regexp_replace: the pattern and the replacement as written)
-  long long arg_k = 0;              // kind 3: the integer argument; kind 4 sort: LF_DESC | LF_NULLS_LAST
-  int columns() const { return kind == 3 || (kind == 6 && op == kDerivedListOverlap) ? 1 : 2; }
+                                    // kind 5: 0 keys, 1 values, 2 entries; kind 6: device/list_set.hpp's LS_UNION / LS_INTERSECT / LS_EXCEPT / LS_OVERLAP;
+                                    // kind 7: device/list_pick.hpp's LP_REMOVE / LP_COMPACT / LP_SLICE / LP_REVERSE / LP_JOIN
+  std::string arg_a, arg_b;         // kind 3: the literal arguments' bytes (regexp_replace: the pattern and the replacement as written); kind 7 remove: arg_a the literal
+                                    // key — a Utf8 key's bytes, else the 16 bytes of its LfKey (hi, lo) —, join: arg_a the delimiter, arg_b the replacement (has_b: given)
+  long long arg_k = 0;              // kind 3: the integer argument; kind 4 sort: LF_DESC | LF_NULLS_LAST; kind 7 slice: the start
+  long long arg_n = 0;              // kind 7 slice: the length
+  bool has_b = false;               // kind 7 join: a replacement for NULL elements is given (it may be the empty string)
+  int columns() const { return kind == 3 || (kind == 6 && op == kDerivedListOverlap) || (kind == 7 && op == kDerivedListJoin) ? 1 : 2; }
   bool is_list() const { return columns() == 2; }      // a derived LIST column: another list function may take it as its argument
   int src = -1;                     // the source column (kind 4 and 6: any list column of the extended table, an earlier derived list included)
-  int src2 = -1;                    // kind 6: the second list column, under the same rule
+  int src2 = -1;                    // kind 6: the second list column, under the same rule; kind 7 remove: the key column of the chain's source, or -1 for a literal key
   std::vector<uint32_t> prog;       // the pattern as a group-0 program of device/regex_vm.hpp
   std::vector<uint32_t> prog2;      // regexp_extract_all: the wanted group's program (empty: group 0)
   int limit = -1;
@@ -70,6 +77,7 @@ struct DerivedCol {
   DType type;
 };
 constexpr int kDerivedRegexpReplace = 30;
+const char* list_pick_name(int op);      // DerivedCol kind 7: the function's name as the JVM sends it, by device/list_pick.hpp's operation (codegen.cpp)
 
 // How the host must treat each group-key word / accumulator word of a grouped aggregate.
 struct PipelineDesc {

@@ -1615,6 +1615,33 @@ void ExecutionContext::list_fn_sort_route(const DerivedCol& dc, const int32_t* o
   HIP_CHECK(hipStreamSynchronize(stream_));      // the sorted table and the flags may go
 }
 
+// Keep flags → a list (array_distinct's tail, which array_remove, array_compact and slice share): the flags' exclusive scan C, the kept element rows, the new
+// offsets — C read at the old ones —, and one take_column of the element column.  keep: hi flags of 0 / 1 on the device; lv gets the new offsets, el the elements
+void ExecutionContext::list_keep_tail(const std::string& who, const uint32_t* keep, const int32_t* offs, int64_t rows, int64_t hi, const DeviceColumnView& ec, const DType& et, bool ehv,
+                                      DeviceColumnView& lv, DeviceColumnView& el, bool& el_hv, std::vector<std::shared_ptr<void>>& owners) {
+  DevBuf tiles, C;
+  tiles.ensure((size_t)((hi + 1023) / 1024 + 2) * 8);
+  C.ensure((size_t)(hi + 2) * 4);
+  HIP_CHECK(hipMemsetAsync(C.p, 0, 8, stream_));
+  pq_launch_u32_scan(keep, hi, (uint64_t*)tiles.p, (int32_t*)C.p, stream_);
+  int32_t kept = 0;
+  read_small(&kept, (const char*)C.p + (size_t)hi * 4, 4);
+  if (kept < 0 || kept > hi) throw CometError("internal: " + who + ": " + std::to_string(kept) + " kept elements of " + std::to_string(hi));
+  auto idx = std::make_shared<DevBuf>(), noffs = std::make_shared<DevBuf>();
+  idx->ensure((size_t)std::max<int32_t>(kept, 1) * 4 + 16);
+  noffs->ensure((size_t)(rows + 1) * 4 + 16);
+  if (comet_launch_collect_index(keep, (const int32_t*)C.p, hi, (uint32_t*)idx->p, stream_) != 0 || comet_launch_list_offsets(offs, (const int32_t*)C.p, rows, (int32_t*)noffs->p, stream_) != 0)
+    throw CometError(who + ": launch failed");
+  HIP_CHECK(hipStreamSynchronize(stream_));      // the tiles and the scan go back to the pool
+  el = take_column(ec, et, ehv, (const uint32_t*)idx->p, nullptr, kept, el_hv, owners);
+  HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
+  if (el_hv != ehv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
+  lv.data = noffs->p;
+  lv.offset = 0;
+  lv.kid_rows = kept;
+  owners.push_back(noffs);
+}
+
 void ExecutionContext::extend_derived_list_fn(DevTable& in, const DerivedCol& dc) {
   const std::string who = dc.op == LF_OP_SORT ? "array_sort" : "array_distinct";
   if (dc.src < 0 || (size_t)dc.src >= in.cols.size() || in.types[(size_t)dc.src].id != TypeId::List || dc.type.kids.size() != 1) throw CometError("internal: unknown derived column");
@@ -1662,36 +1689,14 @@ void ExecutionContext::extend_derived_list_fn(DevTable& in, const DerivedCol& dc
     }
     if (force_sort || too_long) list_fn_sort_route(dc, offs, rows, hi, ec, ehv, (uint32_t*)rowsbuf->p);      // a list beyond the rank kernel's: the whole column takes the sort
     (force_sort || too_long ? list_fn_sort_lists_ : list_fn_rank_lists_) += rows;
-    const uint32_t* take = (const uint32_t*)rowsbuf->p;
-    int64_t taken = hi;
-    std::shared_ptr<DevBuf> idx;
     if (distinct) {
-      DevBuf tiles, C;
-      tiles.ensure((size_t)((hi + 1023) / 1024 + 2) * 8);
-      C.ensure((size_t)(hi + 2) * 4);
-      HIP_CHECK(hipMemsetAsync(C.p, 0, 8, stream_));
-      pq_launch_u32_scan((const uint32_t*)rowsbuf->p, hi, (uint64_t*)tiles.p, (int32_t*)C.p, stream_);
-      int32_t kept = 0;
-      read_small(&kept, (const char*)C.p + (size_t)hi * 4, 4);
-      if (kept < 0 || kept > hi) throw CometError("internal: array_distinct: " + std::to_string(kept) + " kept elements of " + std::to_string(hi));
-      idx = std::make_shared<DevBuf>();
-      idx->ensure((size_t)std::max<int32_t>(kept, 1) * 4 + 16);
-      auto noffs = std::make_shared<DevBuf>();
-      noffs->ensure((size_t)(rows + 1) * 4 + 16);
-      if (comet_launch_collect_index((const uint32_t*)rowsbuf->p, (const int32_t*)C.p, hi, (uint32_t*)idx->p, stream_) != 0 ||
-          comet_launch_list_offsets(offs, (const int32_t*)C.p, rows, (int32_t*)noffs->p, stream_) != 0)
-        throw CometError("array_distinct: launch failed");
-      HIP_CHECK(hipStreamSynchronize(stream_));      // the tiles and the scan go back to the pool
-      take = (const uint32_t*)idx->p;
-      taken = kept;
-      lv.data = noffs->p;
-      lv.offset = 0;
-      in.owners.push_back(noffs);
+      list_keep_tail(who, (const uint32_t*)rowsbuf->p, offs, rows, hi, ec, dc.type.kids[0], ehv, lv, el, el_hv, in.owners);
+    } else {
+      el = take_column(ec, dc.type.kids[0], ehv, (const uint32_t*)rowsbuf->p, nullptr, hi, el_hv, in.owners);
+      HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
+      if (el_hv != ehv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
+      lv.kid_rows = hi;
     }
-    el = take_column(ec, dc.type.kids[0], ehv, take, nullptr, taken, el_hv, in.owners);
-    HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
-    if (el_hv != ehv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
-    lv.kid_rows = taken;
   }
   lv.kids.assign(1, el);
   lv.kid_has_valid.assign(1, el_hv ? 1 : 0);
@@ -1966,33 +1971,13 @@ void ExecutionContext::extend_derived_list_set(DevTable& in, const DerivedCol& d
     lv = dl;
     el = de;
     if (hi > 0) {
-      DevBuf flags, tiles, C;
+      DevBuf flags;
       flags.ensure((size_t)hi * 4 + 16);
-      tiles.ensure((size_t)((hi + 1023) / 1024 + 2) * 8);
-      C.ensure((size_t)(hi + 2) * 4);
-      HIP_CHECK(hipMemsetAsync(C.p, 0, 8, stream_));
       if (comet_launch_list_member(kind, de.data, (const uint8_t*)de.aux, de_hv ? de.valid : nullptr, bs.data, (const uint8_t*)bs.aux, bs_hv ? bs.valid : nullptr, doffs, B.offs, A.row_bits,
                                    B.row_bits, rows, hi, dc.op == LS_INTERSECT ? 1 : 0, 0, (uint32_t*)flags.p, stream_) != 0)
         throw CometError(who + ": launch failed");
-      pq_launch_u32_scan((const uint32_t*)flags.p, hi, (uint64_t*)tiles.p, (int32_t*)C.p, stream_);
-      int32_t kept = 0;
-      read_small(&kept, (const char*)C.p + (size_t)hi * 4, 4);
-      if (kept < 0 || kept > hi) throw CometError("internal: " + who + ": " + std::to_string(kept) + " kept elements of " + std::to_string(hi));
-      auto idx = std::make_shared<DevBuf>(), noffs = std::make_shared<DevBuf>();
-      idx->ensure((size_t)std::max<int32_t>(kept, 1) * 4 + 16);
-      noffs->ensure((size_t)(rows + 1) * 4 + 16);
-      if (comet_launch_collect_index((const uint32_t*)flags.p, (const int32_t*)C.p, hi, (uint32_t*)idx->p, stream_) != 0 ||
-          comet_launch_list_offsets(doffs, (const int32_t*)C.p, rows, (int32_t*)noffs->p, stream_) != 0)
-        throw CometError(who + ": launch failed");
-      HIP_CHECK(hipStreamSynchronize(stream_));      // the flags, the tiles and the scan go back to the pool
       bool t_hv = false;
-      el = take_column(de, et, de_hv, (const uint32_t*)idx->p, nullptr, kept, t_hv, in.owners);
-      HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
-      if (t_hv != de_hv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
-      lv.data = noffs->p;
-      lv.offset = 0;
-      lv.kid_rows = kept;
-      in.owners.push_back(noffs);
+      list_keep_tail(who, (const uint32_t*)flags.p, doffs, rows, hi, de, et, de_hv, lv, el, t_hv, in.owners);      // distinct's own tail
     } else {
       for (auto& o : tmp.owners) in.owners.push_back(o);      // (distinct's all-zero offsets, if it made any)
     }
@@ -2013,6 +1998,187 @@ void ExecutionContext::extend_derived_list_set(DevTable& in, const DerivedCol& d
   in.has_valid.push_back(el_hv);
 }
 
+// A derived column of kind 7: array_remove / array_compact / slice / reverse of an array / array_join of one list column of the extended table
+// (device/list_pick.hpp, list_pick_kernels.hip).  One lane per element row; no operation depends on a list's length.
+//   remove / compact / slice   keep flags, then array_distinct's tail (list_keep_tail)
+//   reverse                    a permutation inside every list, then array_sort's tail: one take_column, the source's offsets and validity kept
+//   join                       piece flags, their scan (is a piece its list's first?), piece lengths, their scan (where its bytes go), the result's Utf8 offsets
+//                              = that scan read at the list offsets (list_offsets_kernel), and the bytes.  One Utf8 column with the list's validity
+// For remove, a row whose key column is NULL keeps nothing: an empty list under validity 0.  The LIST's validity is never read: a NULL list whose offsets span
+// elements (Arrow allows it; this engine's producers repeat the offset) has them picked like any other's, under validity 0, which is valid Arrow and read by nobody.
+// The sliced-column rule of kind 4 holds.
+void ExecutionContext::extend_derived_list_pick(DevTable& in, const DerivedCol& dc) {
+  if (dc.op < LP_REMOVE || dc.op > LP_JOIN) throw CometError("internal: unknown derived column");
+  const std::string who = list_pick_name(dc.op);
+  if (dc.src < 0 || (size_t)dc.src >= in.cols.size() || in.types[(size_t)dc.src].id != TypeId::List || in.types[(size_t)dc.src].kids.size() != 1) throw CometError("internal: unknown derived column");
+  int se = -1;
+  for (size_t j = 0; j < in.types.size(); j++)
+    if (in.types[j].virt_parent == dc.src && in.types[j].virt_kid == 0) se = (int)j;      // (dc.src is a List: virt_kid 0 is its element column, not a map's keys)
+  if (se < 0) throw CometError("internal: " + who + ": the list's elements are not a column of the chain's table");
+  DType et = in.types[(size_t)dc.src].kids[0];
+  et.virt_parent = et.virt_kid = -1;
+  // (only remove compares values, and join reads Utf8: the others move elements of any flat type and never look at `kind`)
+  const int kind = dc.op == LP_JOIN ? LF_STR : dc.op == LP_REMOVE ? list_fn_elem_kind(et) : 0;
+  if (kind < 0 || (dc.op == LP_JOIN && et.id != TypeId::String)) throw CometError("internal: " + who + ": unsupported element type");
+  const DeviceColumnView sc = in.cols[(size_t)dc.src], ec = in.cols[(size_t)se];
+  const bool hv = in.has_valid[(size_t)dc.src], ehv = in.has_valid[(size_t)se];
+  const int64_t rows = in.rows;
+  int32_t lo = 0, hi = 0;
+  const int32_t* offs = sc.data ? (const int32_t*)sc.data + sc.offset : nullptr;
+  if (rows > 0) {
+    if (!offs) throw CometError(who + " over a list column without offsets is not supported");
+    read_small(&lo, offs, 4);
+    read_small(&hi, offs + rows, 4);
+    if (sc.offset != 0 || lo != 0 || (hi > 0 && ec.offset != 0))
+      throw CometError(who + " over a sliced list column (a non-zero Arrow offset, or element offsets that do not start at 0) is not supported by the MI355X native engine");
+    if (hi < 0) throw CometError(who + ": the list column's offsets do not ascend (0 … " + std::to_string(hi) + ")");
+  }
+  if (hi > 0) {
+    if (!ec.data) throw CometError(who + " over an element column without buffers is not supported");
+    if (ehv && !ec.valid) throw CometError("internal: " + who + ": an element column marked nullable without validity bits");
+  }
+  if (hv && rows > 0 && !sc.valid) throw CometError("internal: " + who + ": a list column marked nullable without validity bits");
+  const uint8_t* evalid = ehv ? ec.valid : nullptr;
+
+  if (dc.op == LP_JOIN) {
+    const size_t dn = dc.arg_a.size(), rn = dc.has_b ? dc.arg_b.size() : 0;
+    auto offsets = std::make_shared<DevBuf>(), bytes = std::make_shared<DevBuf>();
+    offsets->ensure((size_t)(rows + 2) * 4);
+    int32_t total = 0;
+    if (hi <= 0) list_pick_rows_ += rows;
+    if (hi > 0) {
+      // the conservative bound, from what the host has read anyway: every element's bytes, and a delimiter and a replacement for every element
+      int32_t b0 = 0, b1 = 0;
+      read_small(&b0, ec.data, 4);
+      read_small(&b1, (const int32_t*)ec.data + hi, 4);
+      if (b0 < 0 || b1 < b0) throw CometError(who + ": the Utf8 element column's offsets do not ascend");
+      if ((int64_t)b1 - b0 + (int64_t)hi * (int64_t)(dn + rn) >= 0x80000000LL)
+        throw CometError(who + ": the result may exceed 2 GiB of string data (" + std::to_string((int64_t)b1 - b0) + " element bytes and " + std::to_string(hi) +
+                         " elements with a delimiter and a replacement of " + std::to_string(dn + rn) + " bytes; LargeUtf8 is not supported)");
+      list_pick_rows_ += rows;      // (counted once the bound holds: a refused column has launched nothing)
+      DevBuf args, flags, lens, tiles, F;
+      auto P = std::make_shared<DevBuf>();
+      args.ensure(dn + rn + 16);
+      if (dn) HIP_CHECK(hipMemcpyAsync(args.p, dc.arg_a.data(), dn, hipMemcpyHostToDevice, stream_));
+      if (rn) HIP_CHECK(hipMemcpyAsync((char*)args.p + dn, dc.arg_b.data(), rn, hipMemcpyHostToDevice, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));      // (the literals came from pageable memory)
+      const uint8_t *d = (const uint8_t*)args.p, *r = (const uint8_t*)args.p + dn;
+      flags.ensure((size_t)hi * 4 + 16);
+      lens.ensure((size_t)hi * 4 + 16);
+      tiles.ensure((size_t)((hi + 1023) / 1024 + 2) * 8);
+      F.ensure((size_t)(hi + 2) * 4);
+      P->ensure((size_t)(hi + 2) * 4);
+      HIP_CHECK(hipMemsetAsync(F.p, 0, 8, stream_));
+      HIP_CHECK(hipMemsetAsync(P->p, 0, 8, stream_));
+      if (comet_launch_list_join_flags(ec.data, (const uint8_t*)ec.aux, evalid, hi, dc.has_b ? 1 : 0, (uint32_t*)flags.p, stream_) != 0) throw CometError(who + ": launch failed");
+      pq_launch_u32_scan((const uint32_t*)flags.p, hi, (uint64_t*)tiles.p, (int32_t*)F.p, stream_);
+      if (comet_launch_list_join_len(ec.data, (const uint8_t*)ec.aux, evalid, offs, rows, hi, (const int32_t*)F.p, (int32_t)dn, (int32_t)rn, dc.has_b ? 1 : 0, (uint32_t*)lens.p, stream_) != 0)
+        throw CometError(who + ": launch failed");
+      pq_launch_u32_scan((const uint32_t*)lens.p, hi, (uint64_t*)tiles.p, (int32_t*)P->p, stream_);
+      read_small(&total, (const char*)P->p + (size_t)hi * 4, 4);
+      if (total < 0) throw CometError("Utf8 column exceeds 2 GiB of string data (LargeUtf8 is not supported)");
+      bytes->ensure((size_t)total + 16);
+      if (comet_launch_list_offsets(offs, (const int32_t*)P->p, rows, (int32_t*)offsets->p, stream_) != 0 ||
+          comet_launch_list_join_write(ec.data, (const uint8_t*)ec.aux, evalid, offs, rows, hi, (const int32_t*)F.p, (const int32_t*)P->p, d, (int32_t)dn, r, (int32_t)rn, dc.has_b ? 1 : 0,
+                                       (uint8_t*)bytes->p, stream_) != 0)
+        throw CometError(who + ": launch failed");
+      HIP_CHECK(hipStreamSynchronize(stream_));      // the literals, flags, lengths and scans go back to the pool
+    } else {
+      bytes->ensure(16);
+      HIP_CHECK(hipMemsetAsync(offsets->p, 0, (size_t)(rows + 2) * 4, stream_));      // every list is empty or NULL: every string is empty
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    DeviceColumnView cv;
+    cv.data = offsets->p;
+    cv.aux = bytes->p;
+    cv.valid = sc.valid;
+    in.types.push_back(dc.type);
+    in.cols.push_back(cv);
+    in.has_valid.push_back(hv);
+    in.owners.push_back(offsets);
+    in.owners.push_back(bytes);
+    return;
+  }
+
+  if (dc.type.kids.size() != 1) throw CometError("internal: unknown derived column");
+  list_pick_rows_ += rows;
+  // remove over a key column: the row is NULL where the key is (its bits ANDed with the list's); a literal key shares the source's validity
+  bool res_hv = hv;
+  const uint8_t* res_valid = sc.valid;
+  DeviceColumnView kc;
+  bool khv = false;
+  if (dc.op == LP_REMOVE && dc.src2 >= 0) {
+    if ((size_t)dc.src2 >= in.cols.size()) throw CometError("internal: unknown derived column");
+    DType kt = in.types[(size_t)dc.src2];
+    kt.virt_parent = kt.virt_kid = -1;
+    if (!(kt == et) || kind == LF_STR) throw CometError("internal: " + who + ": the key column is not of the elements' type");
+    kc = in.cols[(size_t)dc.src2];
+    khv = in.has_valid[(size_t)dc.src2];
+    if (rows > 0 && !kc.data) throw CometError(who + " over a key column without buffers is not supported");
+    if (khv && rows > 0 && !kc.valid) throw CometError("internal: " + who + ": a key column marked nullable without validity bits");
+    if (khv) {
+      if (kc.offset != 0) throw CometError(who + " with a sliced key column (a non-zero Arrow offset) that holds NULLs is not supported by the MI355X native engine");
+      res_hv = true;
+      res_valid = kc.valid;
+      if (hv && rows > 0) {
+        auto both = std::make_shared<DevBuf>();
+        const int64_t nb = (rows + 7) / 8;
+        both->ensure((size_t)nb + 16);
+        if (comet_launch_list_and_bits(sc.valid, kc.valid, nb, (uint8_t*)both->p, stream_) != 0) throw CometError(who + ": launch failed");
+        res_valid = (const uint8_t*)both->p;
+        in.owners.push_back(both);
+      }
+    }
+  }
+  DeviceColumnView el = ec, lv = sc;
+  bool el_hv = ehv;
+  if (hi > 0) {
+    DevBuf rowsbuf, keybuf;      // reverse: the source row of every slot; the others: the keep flags
+    rowsbuf.ensure((size_t)hi * 4 + 16);
+    if (dc.op == LP_REVERSE) {
+      if (comet_launch_list_reverse(offs, rows, hi, (uint32_t*)rowsbuf.p, stream_) != 0) throw CometError(who + ": launch failed");
+      el = take_column(ec, et, ehv, (const uint32_t*)rowsbuf.p, nullptr, hi, el_hv, in.owners);
+      HIP_CHECK(hipStreamSynchronize(stream_));      // the row numbers have been read
+      if (el_hv != ehv) throw CometError("internal: " + who + ": the taken elements lost their validity bits");
+      lv.kid_rows = hi;
+    } else {
+      uint64_t key_hi = 0, key_lo = 0;
+      const uint8_t* key_bytes = nullptr;
+      int32_t key_len = 0;
+      if (dc.op == LP_REMOVE && dc.src2 < 0) {
+        if (kind == LF_STR) {
+          key_len = (int32_t)dc.arg_a.size();
+          for (int b = 0; b < 8; b++) key_hi = (key_hi << 8) | (b < key_len ? (uint64_t)(uint8_t)dc.arg_a[(size_t)b] : 0ull);      // (lf_key's prefix word)
+          keybuf.ensure(dc.arg_a.size() + 16);
+          if (key_len) HIP_CHECK(hipMemcpyAsync(keybuf.p, dc.arg_a.data(), dc.arg_a.size(), hipMemcpyHostToDevice, stream_));
+          HIP_CHECK(hipStreamSynchronize(stream_));      // (the literal came from pageable memory)
+          key_bytes = (const uint8_t*)keybuf.p;
+        } else {
+          if (dc.arg_a.size() != 16) throw CometError("internal: " + who + ": a literal key without its words");
+          memcpy(&key_hi, dc.arg_a.data(), 8);
+          memcpy(&key_lo, dc.arg_a.data() + 8, 8);
+        }
+      }
+      if (comet_launch_list_pick(dc.op, kind, ec.data, (const uint8_t*)ec.aux, evalid, offs, rows, hi, key_hi, key_lo, key_bytes, key_len, dc.src2 >= 0 ? kc.data : nullptr,
+                                 khv ? kc.valid : nullptr, kc.offset, dc.arg_k, dc.arg_n, (uint32_t*)rowsbuf.p, stream_) != 0)
+        throw CometError(who + ": launch failed");
+      list_keep_tail(who, (const uint32_t*)rowsbuf.p, offs, rows, hi, ec, et, ehv, lv, el, el_hv, in.owners);
+    }
+  }
+  lv.valid = res_valid;
+  lv.kids.assign(1, el);
+  lv.kid_has_valid.assign(1, el_hv ? 1 : 0);
+  in.types.push_back(dc.type);
+  in.cols.push_back(lv);
+  in.has_valid.push_back(res_hv);
+  DType vt = dc.type.kids[0];      // the elements as a column of their own, as split's are
+  vt.virt_parent = (int)in.types.size() - 1;
+  vt.virt_kid = 0;
+  in.types.push_back(vt);
+  in.cols.push_back(el);
+  in.has_valid.push_back(el_hv);
+}
+
 // The chain's derived columns (codegen.hpp DerivedCol) computed over its source table and appended to it.  split: two passes of the matcher per
 // row (regex_kernels.hip) — the pieces counted, a prefix sum, every piece described as a view of its source value — and the element column
 // assembled from the views like every string view's result.
@@ -2022,6 +2188,7 @@ void ExecutionContext::extend_derived(DevTable& in, const std::vector<DerivedCol
     if (dc.kind == 4) { extend_derived_list_fn(in, dc); continue; }
     if (dc.kind == 5) { extend_derived_map_view(in, dc); continue; }
     if (dc.kind == 6) { extend_derived_list_set(in, dc); continue; }
+    if (dc.kind == 7) { extend_derived_list_pick(in, dc); continue; }
     if ((dc.kind != 1 && dc.kind != 2) || dc.src < 0 || (size_t)dc.src >= in.cols.size()) throw CometError("internal: unknown derived column");
     const DeviceColumnView sc = in.cols[(size_t)dc.src];
     const bool hv = in.has_valid[(size_t)dc.src];
@@ -2789,6 +2956,7 @@ std::string ExecutionContext::metrics_proto() {
     if (root && list_fn_rank_lists_ > 0) n.metrics.emplace_back("list_fn_rank_lists", list_fn_rank_lists_);      // lists array_sort / array_distinct ranked (only when there are any)
     if (root && list_fn_sort_lists_ > 0) n.metrics.emplace_back("list_fn_sort_lists", list_fn_sort_lists_);      // … and lists that took the radix sort
     if (root && list_set_rows_ > 0) n.metrics.emplace_back("list_set_rows", list_set_rows_);      // rows the two-list set functions computed (only when there are any)
+    if (root && list_pick_rows_ > 0) n.metrics.emplace_back("list_pick_rows", list_pick_rows_);    // rows array_remove / array_compact / slice / reverse / array_join computed (only when there are any)
     if (root && sort_runs_ > 0) {      // the paths sort_table took (only when the plan sorted at all): see DESIGN.md, Sort
       n.metrics.emplace_back("sort_select_passes", sort_select_passes_);
       n.metrics.emplace_back("sort_small_sorts", sort_small_sorts_);

@@ -272,6 +272,9 @@ class ExecutionContext {
   void extend_derived_list_fn(DevTable& in, const DerivedCol& dc);
   void extend_derived_map_view(DevTable& in, const DerivedCol& dc);
   void extend_derived_list_set(DevTable& in, const DerivedCol& dc);
+  void extend_derived_list_pick(DevTable& in, const DerivedCol& dc);
+  void list_keep_tail(const std::string& who, const uint32_t* keep, const int32_t* offs, int64_t rows, int64_t hi, const DeviceColumnView& ec, const DType& et, bool ehv,
+                      DeviceColumnView& lv, DeviceColumnView& el, bool& el_hv, std::vector<std::shared_ptr<void>>& owners);
   void list_fn_sort_route(const DerivedCol& dc, const int32_t* offs, int64_t rows, int64_t hi, const DeviceColumnView& ec, bool ehv, uint32_t* out);
   DevTable hash_join(const Operator& j, const DevTable& l, const DevTable& r);
   DevTable hash_join_impl(const Operator& node, const Operator& j, const DevTable& l, const DevTable& r, const std::string& key_suffix,
@@ -394,6 +397,7 @@ class ExecutionContext {
   int64_t list_fn_rank_lists_ = 0;  // lists array_sort / array_distinct ranked on the device (list_kernels.hip)
   int64_t list_fn_sort_lists_ = 0;  // … and lists of columns that took the radix sort instead (a list beyond kListFnMaxElements)
   int64_t list_set_rows_ = 0;       // rows array_union / array_intersect / array_except / arrays_overlap computed on the device (list_set_kernels.hip)
+  int64_t list_pick_rows_ = 0;      // rows array_remove / array_compact / slice / reverse / array_join computed on the device (list_pick_kernels.hip)
   std::map<int, std::shared_ptr<Operator>> list_fn_sorts_;      // the sort route's Sort operators, by element type and flags
   bool materialize_root_ = false;   // plain Scan chain whose outputs need the materialising path (Utf8 pass-through)
   bool compile_in_infer_ = false;

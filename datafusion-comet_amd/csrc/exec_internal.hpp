@@ -46,6 +46,17 @@ extern "C" int comet_launch_list_concat_index(const int32_t* offs_a, const int32
 extern "C" int comet_launch_list_concat_bits(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb, uint8_t* out, void* stream);
 extern "C" int comet_launch_list_rebase_offsets(const int32_t* in, int64_t n, int32_t by, int32_t* out, void* stream);
 extern "C" int comet_launch_list_and_bits(const uint8_t* a, const uint8_t* b, int64_t bytes, uint8_t* out, void* stream);
+// array_remove / array_compact / slice / reverse of an array / array_join (device/list_pick.hpp, list_pick_kernels.hip)
+#include "device/list_pick.hpp"
+extern "C" int comet_launch_list_pick(int op, int kind, const void* data, const uint8_t* aux, const uint8_t* valid, const int32_t* offs, int64_t rows, int64_t hi, uint64_t key_hi,
+                                      uint64_t key_lo, const uint8_t* key_bytes, int32_t key_len, const void* key_col_data, const uint8_t* key_col_valid, int64_t key_col_offset,
+                                      int64_t start, int64_t length, uint32_t* out, void* stream);
+extern "C" int comet_launch_list_reverse(const int32_t* offs, int64_t rows, int64_t hi, uint32_t* out, void* stream);
+extern "C" int comet_launch_list_join_flags(const void* data, const uint8_t* aux, const uint8_t* valid, int64_t hi, int has_rep, uint32_t* out, void* stream);
+extern "C" int comet_launch_list_join_len(const void* data, const uint8_t* aux, const uint8_t* valid, const int32_t* offs, int64_t rows, int64_t hi, const int32_t* F, int32_t dn,
+                                          int32_t rn, int has_rep, uint32_t* out, void* stream);
+extern "C" int comet_launch_list_join_write(const void* data, const uint8_t* aux, const uint8_t* valid, const int32_t* offs, int64_t rows, int64_t hi, const int32_t* F,
+                                            const int32_t* P, const uint8_t* d, int32_t dn, const uint8_t* r, int32_t rn, int has_rep, uint8_t* dst, void* stream);
 constexpr int64_t kListFnMaxElements = 256;       // the longest list the rank kernel takes (every lane of a list walks all of it); beyond, the radix sort is faster
 extern "C" void pq_launch_u32_scan(const uint32_t* in, int64_t n, uint64_t* tiles, int32_t* out, void* st);
 extern "C" void pq_launch_pack(const uint8_t* bytes, uint8_t* bitmap, int64_t n, void* st);

@@ -163,6 +163,9 @@ def _load() -> ctypes.CDLL:
     lib.comet_list_fn_host.argtypes = [c.c_int32, c.c_char_p, c.c_char_p, c.c_void_p, c.c_int64, c.c_int32, c.c_int32, c.c_void_p]
     lib.comet_list_set_host.restype = c.c_int32
     lib.comet_list_set_host.argtypes = [c.c_int32, c.c_int32, c.c_char_p, c.c_char_p, c.c_char_p, c.c_int64, c.c_char_p, c.c_char_p, c.c_char_p, c.c_int64, c.c_void_p]
+    lib.comet_list_pick_host.restype = c.c_int64
+    lib.comet_list_pick_host.argtypes = [c.c_int32, c.c_int32, c.c_char_p, c.c_char_p, c.c_char_p, c.c_int64, c.c_char_p, c.c_char_p, c.c_char_p, c.c_int32, c.c_int64, c.c_int64,
+                                         c.c_char_p, c.c_int32, c.c_char_p, c.c_int32, c.c_void_p, c.c_int64]
     lib.comet_plan_codegen.restype = c.c_int64
     lib.comet_plan_codegen.argtypes = [c.c_char_p, c.c_size_t, c.c_char_p, c.c_int32, c.c_void_p, c.c_int64]
     lib.comet_error_site_json.restype = c.c_int64
@@ -1305,6 +1308,29 @@ def list_set_host(op: int, kind: int, a: Sequence, b: Sequence):
     if op == 3:
         return [False, True, None][r]
     return list(out[:r])
+
+
+def list_pick_host(op: int, kind: int, values: Sequence, key=None, key_is_column: bool = False, start: int = 1, length: int = 0, delimiter: bytes = b"",
+                   replacement: Optional[bytes] = None):
+    """csrc/device/list_pick.hpp on the host over ONE list (comet_list_pick_host); kind and values as for list_fn_host.  op 0 remove (key: a value of the kind, as a
+    literal or — key_is_column — as a row of a key column, where None answers None), 1 compact, 2 slice (start, length) → the indices of the elements that stay;
+    op 3 reverse → the element index that stands in every slot; op 4 join (Utf8 only: delimiter, replacement or None) → the joined bytes"""
+    n = len(values)
+    data, aux, valid = _list_buffers(kind, values)
+    kd, ka, kv = _list_buffers(kind, [key]) if op == 0 else (None, None, bytearray(1))
+    if op == 4:
+        cap = sum(len(v or b"") for v in values) + n * (len(delimiter) + len(replacement or b"")) + 1
+        out = ctypes.create_string_buffer(cap)
+    else:
+        cap = 0
+        out = (ctypes.c_uint32 * max(n, 1))()
+    r = lib().comet_list_pick_host(op, kind, data, aux, bytes(valid), n, kd, ka, bytes(kv), 1 if key_is_column else 0, start, length, delimiter, len(delimiter), replacement,
+                                   -1 if replacement is None else len(replacement), out, cap)
+    if r == -1 and op == 0:
+        return None
+    if r < 0:
+        _raise_last(0)
+    return out.raw[:r] if op == 4 else list(out[:r])
 
 
 def plan_codegen(plan: bytes, has_valid: Sequence[bool]) -> dict:

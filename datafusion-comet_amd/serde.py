@@ -472,6 +472,38 @@ def arrays_overlap(a: Expr, b: Expr) -> Expr:
     return scalar_func("spark_arrays_overlap", [a, b], T_BOOL)
 
 
+def array_remove(arr: Expr, key: Expr) -> Expr:
+    """ArrayRemove(arr, key): ScalarFunc array_remove_all, no return type (serde/arrays.scala)"""
+    return scalar_func("array_remove_all", [arr, key])
+
+
+def array_compact(arr: Expr) -> Expr:
+    """array_compact(arr) — by then ArrayFilter(arr, x -> x IS NOT NULL): ScalarFunc array_compact, no return type"""
+    return scalar_func("array_compact", [arr])
+
+
+def array_slice(arr: Expr, start, length, element: Optional[DataType] = None) -> Expr:
+    """Slice(arr, start, length): ScalarFunc spark_array_slice over (arr, Cast(start AS LONG), Cast(length AS LONG)) with the return type list<element>, elements
+    nullable.  start and length: Python integers (sent as Int32 literals, what Spark's parser makes of them) or expressions; element: the list's element type
+    when `arr` does not carry its type (a function's result)"""
+    if element is None:
+        element = arr.dtype.element
+    wrap = lambda x: cast(lit(x, T_INT32) if isinstance(x, int) else x, T_INT64)
+    return scalar_func("spark_array_slice", [arr, wrap(start), wrap(length)], list_type(element, True))
+
+
+def array_reverse(arr: Expr) -> Expr:
+    """Reverse(arr) of an array: ScalarFunc array_reverse, no return type"""
+    return scalar_func("array_reverse", [arr])
+
+
+def array_join(arr: Expr, delimiter: str, null_replacement: Optional[str] = None) -> Expr:
+    """ArrayJoin(arr, delimiter[, nullReplacement]): ScalarFunc array_to_string with Utf8 literals, no return type (sent under
+    spark.comet.expression.ArrayJoin.allowIncompatible)"""
+    args = [arr, lit(delimiter, T_STRING)] + ([] if null_replacement is None else [lit(null_replacement, T_STRING)])
+    return scalar_func("array_to_string", args)
+
+
 def map_keys(m: Expr) -> Expr:
     """MapKeys(m): ScalarFunc map_keys, no return type (serde/maps.scala)"""
     return scalar_func("map_keys", [m])

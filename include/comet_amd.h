@@ -276,6 +276,16 @@ int32_t comet_list_fn_host(int32_t kind, const void* data, const uint8_t* aux, c
  * out[i] - na of b (out holds na + nb entries).  op 3: 0 false, 1 true, 2 NULL.  -2 and comet_last_error(0).  Needs no GPU. */
 int32_t comet_list_set_host(int32_t op, int32_t kind, const void* a_data, const uint8_t* a_aux, const uint8_t* a_valid, int64_t na, const void* b_data, const uint8_t* b_aux,
                             const uint8_t* b_valid, int64_t nb, uint32_t* out);
+/* (TEST ABI) array_remove / array_compact / slice / reverse of an array / array_join of ONE list by csrc/device/list_pick.hpp's per-element code on the host — diagnostic entry.
+ * The list is the only row (offsets {0, n}), so the search for an element's list among several (lf_list_of) is not exercised here: tests/host/list_pick_check.cpp and the
+ * GPU tests do that.  op 0 remove, 1 compact, 2 slice, 3 reverse, 4 join; kind and the element arrays as for comet_list_fn_host.  op 0: the key is
+ * element 0 of the one-element column (key_data, key_aux, key_valid) of the same kind — taken as a literal, or with key_is_column as row 0 of a key column, where a NULL
+ * key answers -1 (the row is NULL).  op 2: start != 0, length >= 0.  op 0 - 2: the number of elements that stay, out[i] (uint32) = the element that is the result's i-th;
+ * op 3: n, out[slot] = the element that stands there (out holds n entries).  op 4 (kind 32 only): the delimiter d of dn bytes, the replacement r of rn bytes or
+ * rn = -1 for none; the number of bytes of the joined string, written to out (cap bytes).  -2 and comet_last_error(0).  Needs no GPU. */
+int64_t comet_list_pick_host(int32_t op, int32_t kind, const void* data, const uint8_t* aux, const uint8_t* valid, int64_t n, const void* key_data, const uint8_t* key_aux,
+                             const uint8_t* key_valid, int32_t key_is_column, int64_t start, int64_t length, const uint8_t* d, int32_t dn, const uint8_t* r, int32_t rn, void* out,
+                             int64_t cap);
 #endif /* COMET_TEST_ABI */
 
 /* regexp_extract_all(value, pattern, group) (string_funcs/regexp_extract_all.rs) by the device's two passes (rx_find_all) on the host: the number of matches,

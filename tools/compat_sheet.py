@@ -67,6 +67,10 @@ OTHER_KEYS = [
     ("spark.comet.parquet.write.enabled", "false", "ParquetWriter is not implemented"),
     ("spark.comet.exec.columnarToRow.native.enabled", "true", "Native.columnarToRow* is implemented (flat types on the device, nested types on a host writer)"),
     ("spark.comet.exec.shuffle.enabled", "true", "ShuffleWriter / ShuffleScan are implemented for flat columns (hash, single, round-robin, range)"),
+    ("spark.comet.exec.scalaUDF.codegen.enabled", "false", "the JVM's codegen dispatcher (`CometScalaUDF.emitJvmCodegenDispatch`) is not implemented: with `ArrayFilter` enabled for "
+     "`array_compact`, any other `filter(arr, lambda)` would be sent through it.  The switch is global: every class the reference routes through that dispatcher when its native "
+     "path does not apply (its `CodegenDispatchFallback` serdes: regular expressions, collated `reverse`, `array_join` without `allowIncompatible` …) goes back to Spark as well; "
+     "it has no effect on what §2 lists"),
 ]
 
 
@@ -147,6 +151,19 @@ def probes():
                            "under spark.comet.expression.ArrayIntersect.allowIncompatible: the distinct elements of a, in a's order, that occur in b — Spark's answer (§5); arguments as ArrayUnion"),
         "ArrayExcept": (S.array_except(S.col(7, S.list_type(S.T_INT64)), S.col(7, S.list_type(S.T_INT64))),
                         "under spark.comet.expression.ArrayExcept.allowIncompatible: the distinct elements of a, in a's order, that do not occur in b, a NULL element included — Spark's answer (§5); arguments as ArrayUnion"),
+        "ArrayRemove": (S.array_remove(S.col(7, S.list_type(S.T_INT64)), L(3, S.T_INT64)),
+                        "`array_remove_all(arr, key)`: the list without its non-NULL elements equal to the key, NULL elements kept, NULL when the list or the key is; a list COLUMN or a derived list of "
+                        "Boolean / integers / Date / Timestamp / TimestampNTZ / Decimal / Utf8 elements, any length; the key a non-NULL literal of exactly the element type or, for fixed-width elements, a column "
+                        "of the chain's source of that type; a derived list column of the chain's source (§4)"),
+        "ArrayFilter": (S.array_compact(S.col(7, S.list_type(S.T_INT64))),
+                        "ONLY in the form `filter(arr, x -> x IS NOT NULL)`, which is what Catalyst makes of `array_compact` and the JVM sends as `array_compact(arr)`: the list without its NULL elements, "
+                        "elements of any flat type `Slice` takes.  Any other lambda goes through the JVM's codegen dispatcher, which §3 turns off (`spark.comet.exec.scalaUDF.codegen.enabled=false`), so the stage falls back to Spark"),
+        "Slice": (S.array_slice(S.col(7, S.list_type(S.T_INT64)), 2, 3),
+                  "`spark_array_slice(arr, start, length)` with literal `start` != 0 and `length` >= 0 (§4): Spark's answer — from the end for a negative start, empty for a start outside the list, the length clamped; "
+                  "elements are moved, never compared: Boolean / integers / Float32 / Float64 (bit for bit) / Date / Timestamp / TimestampNTZ / Decimal / Utf8, lists of any length"),
+        "ArrayJoin": (S.array_join(f("split", [s, L(",", S.T_STRING), L(-1, S.T_INT32)], S.list_type(S.T_STRING, False)), ","),
+                      "under spark.comet.expression.ArrayJoin.allowIncompatible: `array_to_string(arr, delimiter[, nullReplacement])` over a list of Utf8 with literal delimiter and replacement — Spark's answer (§5): "
+                      "NULL elements skipped without a replacement, written as it with one, the empty string for an empty list; a derived Utf8 column (usable as an operand, any length)"),
         "GetMapValue": (S.map_extract(S.col(8, MSL), L("k", S.T_STRING)),
                         "`map_extract(m, k)` — `m[k]` and `element_at(m, k)`: the value of the first entry whose key equals k, NULL for a NULL map / key and when there is none, never an error; "
                         "a map COLUMN of the chain's source with Boolean / integer / Date / Timestamp / TimestampNTZ / Decimal (any precision) / Utf8 keys, the key a literal or a column of "
@@ -155,7 +172,7 @@ def probes():
                                                 "list function works on it (`map_contains_key(m, k)` arrives as `array_contains(map_keys(m), k)`) (§4)"),
         "MapValues": (S.map_values(S.col(8, MSL)), "as MapKeys; floats bit for bit"),
         "MapEntries": (S.map_entries(S.col(8, MSL)), "as MapKeys, of any map column the engine passes through: `List<Struct<key, value>>`, passed through, exported and exploded"),
-        "Reverse": (f("reverse", [s], S.T_STRING), "of a Utf8 COLUMN: a derived column of the chain's source (usable as an operand, any length); arrays are refused"),
+        "Reverse": (f("reverse", [s], S.T_STRING), "of a Utf8 COLUMN: a derived column of the chain's source (usable as an operand, any length); of an array (`array_reverse(arr)`): the elements in reverse order, the list's offsets and validity kept, arguments and element types as Slice"),
         "StringRepeat": (f("repeat", [s, L(2, S.T_INT64)], S.T_STRING), "literal count >= 0; derived column"), "StringReplace": (f("replace", [s, L("a", S.T_STRING), L("b", S.T_STRING)], S.T_STRING), "under allowIncompatible (Rust's str::replace for an empty search string); literal arguments; derived column"),
         "SubstringIndex": (f("substring_index", [s, L(".", S.T_STRING), L(2, S.T_INT64)], S.T_STRING), "literal delimiter and count; derived column"),
         "Md5": (f("md5", [S.cast(s, S.DataType(S.BYTES))], S.T_STRING), "of a Utf8 column (under Cast AS BINARY too); derived column"), "Sha1": (f("sha1", [S.cast(s, S.DataType(S.BYTES))], S.T_STRING), ""),
@@ -335,8 +352,8 @@ def render() -> str:
     w("* Nested types: struct-of-flat, list-of-flat, list-of-flat-struct and map columns are read from Parquet, passed through Filter / Projection / Sort /")
     w("  Limit / ShuffleWriter, taken apart by `GetStructField` and exported; struct / list columns of any depth arrive through Scan / ShuffleScan inputs;")
     w("  `Explode` of a list column runs; `size`, `arr[i]` / `element_at`, `array_contains`, `sort_array`, `array_distinct`, `array_min` / `array_max`, `array_position`,")
-    w("  `array_union`, `array_intersect`, `array_except` and `arrays_overlap` over list COLUMNS of flat elements run; `m[k]` / `element_at(m, k)`, `map_keys`, `map_values`, `map_entries` and `map_contains_key` over a map COLUMN run;")
-    w("  deeper trees in the Parquet scan, `Explode` of a map (the JVM never sends one), the other array / map functions (`array_remove`, `slice`, `array_join`, `flatten`, `array_repeat`, `array_append` / `array_insert`, `map_from_arrays`, `map_from_entries`, `map_concat`,")
+    w("  `array_union`, `array_intersect`, `array_except`, `arrays_overlap`, `array_remove`, `array_compact`, `slice`, `reverse` and `array_join` over list COLUMNS of flat elements run; `m[k]` / `element_at(m, k)`, `map_keys`, `map_values`, `map_entries` and `map_contains_key` over a map COLUMN run;")
+    w("  deeper trees in the Parquet scan, `Explode` of a map (the JVM never sends one), the other array / map functions (`flatten`, `array_repeat`, `array_append` / `array_insert`, `map_from_arrays`, `map_from_entries`, `map_concat`,")
     w("  `str_to_map`, the lambda functions) and everything that builds a struct / an array / a map are refused.")
     w("  Parquet: TIMESTAMP(NANOS) / TIME, encrypted files.")
     w("* `SortArray`, `ArrayDistinct`, `ArrayMin`, `ArrayMax`, `ArrayPosition`: Float32 / Float64 elements (Spark and the reference disagree on signed zeros there, the")
@@ -356,6 +373,16 @@ def render() -> str:
     w("  the limits of those two come along: a column that holds a list beyond 256 elements goes through the Sort operator's radix sort, where a Utf8 element beyond the")
     w("  1000-byte sort key fails the task with that operator's message; a sliced list column on either side is refused at run time, by name.  2^31 elements of both sides")
     w("  together and a Utf8 result beyond 2 GiB fail the task by name.  A set function takes the column slots of its result — two, one for `arrays_overlap` — of a pipeline's 24.")
+    w("* `ArrayRemove`, `ArrayFilter` (`array_compact`), `Slice`, `Reverse` of an array, `ArrayJoin`: a map argument; an argument that is neither a list COLUMN of the chain's")
+    w("  source nor a derived list (a computed or literal `array(3, 4, 5)`); Binary, struct, list and map elements; inside an aggregate's fused chain (project them below it;")
+    w("  under a join the side that holds them is materialised instead of fused, and runs); a sliced list column at run time, by name, as for `SortArray`.")
+    w("  `array_remove_all`: Float32 / Float64 elements (the open question of `ArrayPosition`: NaN and -0.0 equality); a NULL literal key, a computed key, a key whose type is")
+    w("  not exactly the elements' (both are named), a key column over Utf8 elements.")
+    w("  `spark_array_slice`: a `start` of 0, a negative `length`, a NULL literal, and a `start` or `length` that is a column or a computed value, all at `createPlan` — Spark")
+    w("  raises for a 0 start or a negative length only for rows it evaluates; a derived column is computed over the chain's source before the chain's Filters; so a row that")
+    w("  raises could not be told from a row a Filter dropped (§6), and the fallback gives Spark's own error —; a return type that is not a list of the argument's element type.")
+    w("  `array_to_string`: elements other than Utf8, a non-literal or NULL delimiter or replacement; the task fails by name, before any launch, when the elements' bytes plus")
+    w("  (delimiter + replacement bytes) per element reach 2 GiB (a conservative bound).  Each takes the column slots of its result — two, one for `array_to_string` — of a pipeline's 24.")
     w("* `GetMapValue` / `ElementAt` over a map (`map_extract`), `MapKeys`, `MapValues`, `MapEntries`: a map argument that is not a map COLUMN of the chain's source (a computed")
     w("  map, a map inside a struct); for `map_extract`, `map_keys` and `map_values` a map with a nested key or a nested value (`map_entries` takes any map the engine passes")
     w("  through).  `map_extract`: Float32 / Float64 keys (Spark's ordering and an array comparison disagree on -0.0 and NaN keys), Binary keys, Binary values; a key")
@@ -411,6 +438,11 @@ def render() -> str:
     w("  except differs from Spark in NULL handling.  Here both give Spark's answer — the distinct elements of the left argument in the left argument's order, a NULL element")
     w("  kept or dropped like a value — which is what the JVM's fallback gives and what the reference's SQL tests expect (`tests/test_list_set_gpu.py`).  `array_union` and")
     w("  `arrays_overlap` are Compatible on both sides.")
+    w("* `array_join`: the reference marks its own path Incompatible (\"Null handling may differ from Spark\") and sends `array_to_string` to DataFusion only under")
+    w("  `allowIncompatible`.  Here the answer is Spark's: without a replacement a NULL element is skipped and brings no delimiter (`['a', NULL, 'c']` is `a,c`, `[NULL, 'a']` is `a`),")
+    w("  with one it is written as the replacement; an empty list, or only NULL elements without a replacement, gives the empty string, never NULL (`tests/test_list_pick_gpu.py`).")
+    w("  `array_remove`: the reference sends `array_remove_all` to DataFusion as Compatible and its SQL test expects Spark's answers — NULL for a NULL key, NULL elements kept —, which")
+    w("  are the answers here; the reference's own tree holds no code for the function to compare further.")
     w("* Join and hash-aggregate OUTPUT ORDER is unspecified in the reference (hash-table order per batch); tests compare multisets.  A sort-merge join's output is")
     w("  ordered by its keys only where that order is observable (plan output, Limit, shuffle file).")
     w("* Everything else on the path — integers, decimals (HALF_UP, overflow → NULL / ANSI error), dates, timestamps, strings, hashes (murmur3 / xxhash64), partition")
